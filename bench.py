@@ -69,6 +69,8 @@ def parse_args():
     ap.add_argument('--no-autotune', action='store_true', help="keep the conv stack in the executor's default configuration instead of the fastest per crop count")
     ap.add_argument('--pose-streams', type=int, default=1, choices=[1, 2], help='2: the forwards of consecutive frames alternate between two streams / replay slots and overlap')
     ap.add_argument('--no-overlap', action='store_true', help='run the tracker of frame t on the pose stream instead of under frame t+1')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64, <= 64 MB in all)')
     return ap.parse_args()
 
 
@@ -556,8 +558,23 @@ def main():
     inp = build_inputs(torch, synth, seq, size, max_dets, world, rank, shard, dev, nF)
     torch.cuda.synchronize()
 
+    last_features = {}
+    if args.dump_outputs and pipe.net is not None:
+        features = pipe.net.features
+
+        def features_kept(x, slot=0):      # the replay's output tensor of the newest forward, for dump_outputs()
+            f = features(x, slot)
+            last_features['f'] = f
+            return f
+        pipe.net.features = features_kept
+
     # ---- the timed region: exactly K frames ------------------------------------------------------------------------------------
     elapsed, evs, final = timed_run(torch, dist, pipe, make_step(pipe, inp, shard), inp, K, W, world, dev)
+    if args.dump_outputs:
+        if pipe.net is not None:
+            pipe.net.features = features
+        if rank == 0:
+            dump_outputs(torch, pipe, inp, shard, final, last_features.get('f'), W + K - 1, args.dump_outputs)
 
     # ---- throughput mode: TWO consecutive frames per conv-stack replay (40 crops on Shelf), trackers of the two frames in order ----------
     pair = None
@@ -730,6 +747,52 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 64 << 20
+DUMP_SAMPLE_BYTES = 48 << 20        # the conv-stack features above this size: a fixed, seeded sample of the crops
+
+
+def dump_outputs(torch, pipe, inp, shard, final, features, t, root):
+    """What the last timed step (frame t) computed, as a caller of the timed path receives it, in DIR/<name>.npy:
+      tracks_int (n_tracks, 9) track_id, state, hits, age, time_since_update, emitted, V, nhist, last_time; tracks_pose3d / tracks_velocity
+      (n_tracks, 17, 3); tracks_nviews (n_tracks, 17); tracks_matched_det / tracks_time2d (n_tracks, C) -- the tracker record after frame t;
+      hrnet_features (n, 48, 96, 72): the conv stack's output for frame t's n crops (bf16 values in float32); above DUMP_SAMPLE_BYTES
+      hrnet_features_sample (a seeded sample of the crops) + hrnet_features_sample_crops (their indices);
+      hrnet_keypoints: frame t's head + arg-max decode of those features in the tracker's row layout (y, x, score), the same kernel on
+      the same features as inside the step (the timed loop then hands the tracker the seeded synthetic keypoints instead).
+    Inputs are seeded: the same arguments give the same inputs."""
+    os.makedirs(root, exist_ok=True)
+    tr = final['tracks']
+    C = pipe.C
+    ints = ('track_id', 'state', 'hits', 'age', 'time_since_update', 'emitted', 'V', 'nhist', 'last_time')
+    arrays = {
+        'tracks_int': np.array([[float(x[k]) for k in ints] for x in tr], dtype=np.float64).reshape(-1, len(ints)),
+        'tracks_pose3d': np.array([x['pose3d'] for x in tr], dtype=np.float64).reshape(-1, 17, 3),
+        'tracks_velocity': np.array([x['velocity'] for x in tr], dtype=np.float64).reshape(-1, 17, 3),
+        'tracks_nviews': np.array([x['nviews'] for x in tr], dtype=np.float64).reshape(-1, 17),
+        'tracks_matched_det': np.array([x['matched_det'] for x in tr], dtype=np.float64).reshape(-1, C),
+        'tracks_time2d': np.array([x['time2d'] for x in tr], dtype=np.float64).reshape(-1, C),
+    }
+    e = inp['per_frame'][t]
+    n = int(e['vl'].numel())
+    if pipe.net is not None and n > 0:
+        assert features is not None
+        torch.cuda.synchronize()
+        target = pipe.crop_gather.send if shard == 'crops' else pipe.det_local
+        det = torch.zeros_like(target)
+        pipe.net.head_decode(features, e['vl'], e['sl'], e['bx'], det, n=n)
+        f = features[:n].float().cpu().numpy()
+        arrays['hrnet_keypoints'] = det.cpu().numpy().astype(np.float64)
+        if f.nbytes <= DUMP_SAMPLE_BYTES:
+            arrays['hrnet_features'] = f
+        else:
+            keep = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE_BYTES // (f.nbytes // n), replace=False))
+            arrays['hrnet_features_sample'] = f[keep]
+            arrays['hrnet_features_sample_crops'] = keep.astype(np.float64)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(root, name + '.npy'), np.ascontiguousarray(a))
 
 
 def summary_of(out, pipe, n_med):

@@ -29,6 +29,13 @@ def cameras(size):
     return load('cameras_%s.npz' % size)
 
 
+def camera_variants(size):
+    """The reference's camera set-up on each of MKL's kernel paths: cameras_<S>.npz (AVX-512, Intel), cameras_<S>_mkl_avx2.npz (AVX2,
+    Intel without AVX-512) and cameras_<S>_mkl_compatible.npz (MKL's baseline path, the one it runs on other vendors' CPUs, e.g. AMD
+    EPYC).  Their float32 3x3 products round differently; only F differs."""
+    return [cameras(size), load('cameras_%s_mkl_avx2.npz' % size), load('cameras_%s_mkl_compatible.npz' % size)]
+
+
 def trace_frames(tr):
     """list[frame][view] -> (n,17,3) arrays in the dump layout (x, y, score)."""
     n_det = tr['in.n_det']

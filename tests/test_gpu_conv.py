@@ -60,20 +60,27 @@ def eng():
     return hrnet_hip.HipHRNet.__new__(hrnet_hip.HipHRNet), hrnet_hip
 
 
+def _refused(case, tile):
+    """(case, tile) pairs that pam_conv2d_nhwc_bf16_ex refuses with PAM_E_ARG before it launches anything: a stated tile whose shape does
+    not divide the layer (1 / 3: two N tiles per workgroup, 5 / 7: three, 6: four; NTW = 3 when Cout % 48 == 0, else 4), the 96-channel-slab
+    streamed implicit GEMM (9) without whole 96-channel slabs or with a residual (its wide slab has no registers left for the residual rows),
+    the 128- / 64-pixel-tile forms (10, 11, 12) without whole 48-channel slabs or with a residual."""
+    n, h, w, cin, cout, k, stride, use_res, relu = case
+    if tile in (10, 11, 12):
+        return bool(use_res or cout % 48)
+    if tile == 9:
+        return bool(use_res or cout % 96)
+    nb = cout // (48 if cout % 48 == 0 else 64)
+    return bool((tile in (1, 3) and nb % 2) or (tile in (5, 7) and nb % 3) or (tile == 6 and nb % 4))
+
+
 @pytest.mark.parametrize('case', CASES)
 @pytest.mark.parametrize('tile', [-1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12])
 def test_conv_vs_torch(eng, case, tile):
+    """Every tile the library accepts for a layer matches the fp32 reference; every tile it cannot run that layer with is refused
+    (PamError) instead of launching."""
     from pam import _lib, hrnet_hip
     n, h, w, cin, cout, k, stride, use_res, relu = case
-    if tile in (10, 11, 12) and (cout % 48 or use_res or cin == 8):
-        pytest.skip('128- / 64-pixel-tile streamed implicit GEMM: 48-channel slabs, no residual')
-    if tile == 9 and (cout % 96 or use_res or cin == 8 or (k == 3 and stride == 1)):
-        pytest.skip('96-channel-slab streamed implicit GEMM: fuse-layer shapes (Cout % 96 == 0, no residual)')
-    nb = cout // (48 if cout % 48 == 0 else 64)
-    if (tile in (1, 3) and nb % 2) or (tile in (5, 7) and nb % 3) or (tile == 6 and nb % 4):
-        pytest.skip('tile needs a matching number of N tiles')
-    if 5 <= tile <= 7 and (k != 3 or stride != 2 or cout % 48):
-        pytest.skip('wide-N tiles are exercised on the strided fuse-layer shapes')
     dev = torch.device('cuda:0')
     g = torch.Generator().manual_seed(hash(case) % 1000)
     conv = nn.Conv2d(cin, cout, k, stride, k // 2, bias=True)
@@ -87,6 +94,10 @@ def test_conv_vs_torch(eng, case, tile):
     e = hrnet_hip.HipHRNet.__new__(hrnet_hip.HipHRNet)
     e.lib = _lib.load(); e.device = dev; e.tile_cfg = tile
     e.down48 = tile == -1                        # a stated tile keeps the strided 48-channel layers on the generic kernels (k_down48: tests/test_gpu_fuse.py)
+    if _refused(case, tile):
+        with pytest.raises(_lib.PamError, match=r'failed \(-1\)'):         # PAM_E_ARG (include/pam.h)
+            e.conv(op, x, res=res, relu=relu)
+        return
     y = e.conv(op, x, res=res, relu=relu)
     wq = conv.weight.detach().to(torch.bfloat16).float().to(dev)
     ref = F.conv2d(x.float(), wq, conv.bias.detach().to(dev), stride, k // 2)

@@ -18,6 +18,10 @@ def _cams(size):
 def test_camera_setup(size):
     c = G.cameras(size)
     cams = O.make_cameras({'P': c['P'], 'K': c['K'], 'RT': c['RT']})
+    # the reference's numbers on the MKL kernel path this CPU takes (AVX-512, AVX2 or baseline: their 3x3 products round
+    # differently), one path for the whole rig; the first one when none fits, so that the assertions below report the difference
+    close = lambda a, b: np.allclose(a, b, rtol=5e-7, atol=1e-12)
+    c = next((v for v in G.camera_variants(size) if all(close(cam.F, v['F'][j]) for j, cam in enumerate(cams))), c)
     for j, cam in enumerate(cams):
         assert cam.P.dtype == np.float32 and cam.RK_INV.dtype == np.float32 and cam.position.dtype == np.float64
         # bit-equal on this image (same torch CPU algebra as the reference); a few float32 ulps are allowed for other BLAS builds

@@ -10,6 +10,11 @@ Fixtures:
   ops_<S>.npz       per-function input/output records captured INSIDE a real tracker run      (a3-a16)
   trace_<S>.npz     whole sequences: per-frame detections in, the 9-tuple + tracker state out (a2-a17)
   pcp_S2.npz        Evaluate3DPose_PCP on a synthetic actorsGT.mat                              (gate)
+  cameras_<S>_mkl_avx2.npz, cameras_<S>_mkl_compatible.npz  the same camera set-up on MKL's other kernel paths (AVX2: Intel CPUs
+                    without AVX-512; compatible: MKL's baseline path, which it takes on other vendors' CPUs), whose float32 3x3
+                    products round differently:
+                    MKL_ENABLE_INSTRUCTIONS=AVX2 python tools/make_goldens.py --cameras-only mkl_avx2
+                    MKL_CBWR=COMPATIBLE python tools/make_goldens.py --cameras-only mkl_compatible
 """
 import argparse
 import os
@@ -414,23 +419,32 @@ def make_panoptic(out_path):
     print('panoptic golden: AP', aps, 'recall', recs, 'MPJPE', mpjpe)
 
 
+CAMERA_PLANS = [
+    ('S1', 160, 0, dict(blank_frames=(60,))),
+    ('S2', 160, 0, {}),
+    # round 5: the two hardest rigs at >= 80 frames with a track death + a birth every 22 / 20 frames (churn: one person invisible for 12 frames > MAX_AGE), denser occlusions, empty views and blank frames
+    ('S3', 132, 1, dict(birth_death_frame=30, occlusion_every=9, empty_view_every=7, blank_frames=(40, 41, 77), churn_every=22, churn_len=12)),
+    ('S4', 100, 2, dict(birth_death_frame=12, occlusion_every=5, empty_view_every=4, blank_frames=(33,), churn_every=20, churn_len=12)),
+]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(ROOT, 'tests', 'golden'))
     ap.add_argument('--only-panoptic', action='store_true')
+    ap.add_argument('--cameras-only', metavar='SUFFIX', default=None, help='write only cameras_<S>_<SUFFIX>.npz')
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
+    if args.cameras_only:
+        for size, nf, seed, kw in CAMERA_PLANS:
+            _, cam_rec, _, _ = run_trace(size, nf, seed, **kw)
+            np.savez_compressed(os.path.join(args.out, 'cameras_%s_%s.npz' % (size, args.cameras_only)), **cam_rec)
+        return
     if args.only_panoptic:
         make_panoptic(os.path.join(args.out, 'panoptic_eval.npz'))
         return
     install_recorders()
-    plans = [
-        ('S1', 160, 0, dict(blank_frames=(60,))),
-        ('S2', 160, 0, {}),
-        # round 5: the two hardest rigs at >= 80 frames with a track death + a birth every 22 / 20 frames (churn: one person invisible for 12 frames > MAX_AGE), denser occlusions, empty views and blank frames
-        ('S3', 132, 1, dict(birth_death_frame=30, occlusion_every=9, empty_view_every=7, blank_frames=(40, 41, 77), churn_every=22, churn_len=12)),
-        ('S4', 100, 2, dict(birth_death_frame=12, occlusion_every=5, empty_view_every=4, blank_frames=(33,), churn_every=20, churn_len=12)),
-    ]
+    plans = CAMERA_PLANS
     for size, nf, seed, kw in plans:
         REC.clear()
         COUNT.clear()
