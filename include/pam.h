@@ -103,6 +103,12 @@ int pam_reset(PamHandle* h);
 
 int pam_out_layout(const PamHandle* h, PamOutLayout* out);
 
+/* How the per-frame step runs on this handle (read-only, fixed by pam_create's arguments): block = threads per workgroup (256, or
+ * 1024 on rigs of more than 8 views), launches = kernel launches per frame (3 for a single-scene rig of more than 8 views: association,
+ * the conflict sets over the whole chip, the rest; else 1, one workgroup per scene), hot_in_lds = 1 when a scene's hot scratch and
+ * integer state fit in 128 KB and are held in LDS for the frame, 0 when the kernel works on them in global memory. */
+int pam_frame_plan(const PamHandle* h, int32_t* block, int32_t* launches, int32_t* hot_in_lds);
+
 /* ---- the per-frame step ------------------------------------------------------------------------------------
  * replaces: IterativeTracker.tracking (IterativeTracker.py:115-180) + output collection (ivclabpose.py:259-287):
  * association, per-track part-aware view filter + weighted DLT + smoothing + motion, greedy hypothesis

@@ -45,6 +45,7 @@ _SIGS = {
     'pam_set_cameras': (_I, [_P, _P, _P, _P, _P]),
     'pam_reset': (_I, [_P]),
     'pam_out_layout': (_I, [_P, C.POINTER(PamOutLayout)]),
+    'pam_frame_plan': (_I, [_P, _P, _P, _P]),
     'pam_frame': (_I, [_P, _I, _P, _P, _P, _P]),
     'pam_frame_dev': (_I, [_P, _P, _I, _P, _P]),
     'pam_frame_dev_views': (_I, [_P, _P, _I, _P, _P]),
@@ -273,6 +274,13 @@ class Handle(object):
 
     def reset(self):
         self._chk(self.lib.pam_reset(self._h))
+
+    def plan(self):
+        """How the frame step runs on this handle: dict(block=threads per workgroup, launches=kernel launches per frame,
+        hot_in_lds=whether the hot scratch and integer state live in LDS during the frame) (pam_frame_plan)."""
+        v = [C.c_int32() for _ in range(3)]
+        self._chk(self.lib.pam_frame_plan(self._h, *[C.byref(x) for x in v]))
+        return dict(block=v[0].value, launches=v[1].value, hot_in_lds=v[2].value)
 
     def frame(self, frame_id, n_det, det):
         """n_det (S,C) int32, det (S,C,max_dets,17,3) float64 (y,x,score) host arrays -> (out_i, out_d)."""

@@ -125,12 +125,15 @@ __host__ __device__ inline char* carve_ws_bulk(char* base, const Dims& d, Scratc
     w.rpart = c.take<double>((size_t)d.MAXT * J * 4 * 10);
     return c.bytes(0);
 }
-__host__ __device__ inline char* carve_ws(char* base, const Dims& d, Scratch& w) {
-    return carve_ws_bulk(carve_ws_hot(base, d, w), d, w);
-}
 __host__ __device__ inline size_t hot_bytes(const Dims& d) {
     Scratch w;
     return ((size_t)(uintptr_t)carve_ws_hot((char*)0, d, w) + 15) & ~(size_t)15;      // offset from a zero base
+}
+// the bulk arrays start hot_bytes() behind the hot ones: the 16-byte rounded copies of the hot scratch between LDS and its home in
+// global memory (launches 1 and 3 of the split step) then never touch hyp_size
+__host__ __device__ inline char* carve_ws(char* base, const Dims& d, Scratch& w) {
+    carve_ws_hot(base, d, w);
+    return carve_ws_bulk(base + hot_bytes(d), d, w);
 }
 // integer part of the scene state (everything before `vel`): contiguous, copied to LDS for the duration of a frame
 __host__ __device__ inline size_t state_int_bytes(const Dims& d) {
@@ -165,8 +168,8 @@ __device__ __forceinline__ double now_s() { return (double)__builtin_amdgcn_s_me
 // =====================================================================================================================
 // PART: 0 = the whole step in one launch.  Rigs with more than 8 cameras run it as THREE launches (round 6): 1 = P0-P4a (association,
 // view selection), 2 = P4b (the epipolar conflict sets: nT x V(V-1)/2 x 17 independent items -- 55 000 on the 31-camera rig, which one
-// workgroup walked in 54 passes of dependent L2 loads, 136 of its 297 us) spread over MANY workgroups, 3 = P4c-P7.  The split forms keep
-// all scratch and the integer state in global memory (hot_in_lds = 0); one scene per handle.
+// workgroup walked in 54 passes of dependent L2 loads, 136 of its 297 us) spread over MANY workgroups, 3 = P4c-P7.  Launch 2 works on
+// the global copy of the scratch and state; launches 1 and 3 hold them in LDS when they fit (hot_in_lds); one scene per handle.
 template <int NTHREADS, int PART = 0>
 __global__ __launch_bounds__(NTHREADS, 4) void k_frame(FrameArgs A) {      // 4 waves per SIMD: four 256-thread scenes per CU (<= 128 VGPRs)
     const Dims d = A.d;
@@ -1001,6 +1004,29 @@ extern "C" int pam_set_input_guard(PamHandle* h, const int32_t* dev_word) {
     return PAM_OK;
 }
 
+// How the step runs on a handle: one helper for launch_frame and pam_frame_plan
+struct FramePlan { int block, launches, hot_in_lds; size_t hot; };
+static FramePlan frame_plan(const PamHandle* h) {
+    FramePlan p;
+    // hot scratch + integer state: kept in LDS for the frame when they fit
+    p.hot = hot_bytes(h->d) + ((state_int_bytes(h->d) + 15) & ~(size_t)15);
+    p.hot_in_lds = p.hot <= 128 * 1024 ? 1 : 0;
+    // one workgroup per scene; many-camera rigs have ~10^4-10^5 independent (track, view pair, joint) items per frame, so
+    // they get the largest workgroup (16 waves hide the L2 latency of the pose / fundamental-matrix reads)
+    p.block = h->d.C > 8 ? 1024 : BLOCK;
+    // wide rigs, one scene: three launches, the conflict sets of P4b over the whole chip (PAM_FRAME_SPLIT=0: the single launch, for A/B runs)
+    static const int split_ok = getenv("PAM_FRAME_SPLIT") ? atoi(getenv("PAM_FRAME_SPLIT")) : 1;
+    p.launches = (p.block == 1024 && h->d.S == 1 && split_ok) ? 3 : 1;
+    return p;
+}
+
+extern "C" int pam_frame_plan(const PamHandle* h, int32_t* block, int32_t* launches, int32_t* hot_in_lds) {
+    if (!h || !block || !launches || !hot_in_lds) return PAM_E_ARG;
+    const FramePlan p = frame_plan(h);
+    *block = p.block; *launches = p.launches; *hot_in_lds = p.hot_in_lds;
+    return PAM_OK;
+}
+
 static int launch_frame(PamHandle* h, hipStream_t s, int frame_id, const int* d_ndet, const double* d_det, const int* d_view_row = nullptr) {
     if (!h->cams_set) { h->err = "pam_set_cameras has not been called"; return PAM_E_STATE; }
     FrameArgs A;
@@ -1008,11 +1034,10 @@ static int launch_frame(PamHandle* h, hipStream_t s, int frame_id, const int* d_
     A.state = h->d_state; A.state_stride = h->state_stride; A.ws = h->d_ws; A.ws_stride = h->ws_stride;
     A.guard = h->d_guard;
     A.n_det = d_ndet; A.det = d_det; A.view_row = d_view_row; A.out_i = h->d_out_i; A.out_d = h->d_out_d; A.ol = h->ol; A.frame_id = frame_id;
-    const size_t hot = hot_bytes(h->d) + ((state_int_bytes(h->d) + 15) & ~(size_t)15);
-    A.hot_in_lds = hot <= 128 * 1024 ? 1 : 0;
-    // one workgroup per scene; many-camera rigs have ~10^4-10^5 independent (track, view pair, joint) items per frame, so
-    // they get the largest workgroup (16 waves hide the L2 latency of the pose / fundamental-matrix reads)
-    const int block = h->d.C > 8 ? 1024 : BLOCK;
+    const FramePlan plan = frame_plan(h);
+    const size_t hot = plan.hot;
+    A.hot_in_lds = plan.hot_in_lds;
+    const int block = plan.block;
     // each workgroup size is its own instantiation with its own __launch_bounds__: under a shared bound of 1024 the 256-thread
     // form was held to 128 VGPRs (occupancy 4) and spilled 211 SGPRs
 #ifdef PAM_DIAG
@@ -1023,9 +1048,7 @@ static int launch_frame(PamHandle* h, hipStream_t s, int frame_id, const int* d_
     if (dblock == 64) { hipLaunchKernelGGL(k_frame<64>, dim3(h->d.S), dim3(64), A.hot_in_lds ? hot : 0, s, A); HIPCHK(h, hipGetLastError()); return PAM_OK; }
     if (dblock == 128) { hipLaunchKernelGGL(k_frame<128>, dim3(h->d.S), dim3(128), A.hot_in_lds ? hot : 0, s, A); HIPCHK(h, hipGetLastError()); return PAM_OK; }
 #endif
-    // wide rigs, one scene: three launches, the conflict sets of P4b over the whole chip (PAM_FRAME_SPLIT=0: the single launch, for A/B runs)
-    static const int split_ok = getenv("PAM_FRAME_SPLIT") ? atoi(getenv("PAM_FRAME_SPLIT")) : 1;
-    if (block == 1024 && h->d.S == 1 && split_ok) {
+    if (plan.launches == 3) {
         // launches 1 and 3 keep the hot scratch and the integer state in LDS (the serial LSAP walks live there) and hand them over through
         // their home in global memory; launch 2 works on the global copy
         const int in_lds = A.hot_in_lds;

@@ -30,6 +30,23 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.EXPORTS) == names
 
 
+def test_frame_plan_query_is_bound_and_rejects_a_null_handle():
+    """pam_frame_plan (which launch form k_frame takes on a handle) is declared, bound with four pointer arguments, reachable from
+    Handle.plan, and answers PAM_E_ARG without touching a device when the handle or an output is missing."""
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    assert _lib._SIGS['pam_frame_plan'] == (ctypes.c_int, [ctypes.c_void_p] * 4)
+    assert callable(getattr(_lib.Handle, 'plan'))
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    fn = lib.pam_frame_plan
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_void_p] * 4
+    v = [ctypes.c_int32(-7) for _ in range(3)]
+    assert fn(None, *[ctypes.byref(x) for x in v]) == -1
+    assert [x.value for x in v] == [-7, -7, -7]
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(_lib, '_lib', None)
     monkeypatch.setattr(_lib, 'LIB_PATH', '/nonexistent/libpam_hip.so')
