@@ -274,6 +274,15 @@ def _folded_random_model(c, nof_joints, seed):
     return copy.deepcopy(_FOLDED_RANDOM[key])
 
 
+def load_folded_checkpoint(path, c, nof_joints):
+    """A checkpoint file in the official key layout (the state dict itself or wrapped as {'model': ...}) -> the folded fp32 module
+    HRNetPose packs (CPU)."""
+    model = PoseHighResolutionNet(c, nof_joints)
+    sd = torch.load(path, map_location='cpu')
+    model.load_state_dict(sd.get('model', sd) if isinstance(sd, dict) else sd)
+    return fold_batchnorm(model)
+
+
 class HRNetPose(object):
     """Mirror of ``backend.HRPose.SimpleHRNet.HRNetPose``: ctor (c, nof_joints, checkpoint, model_name, resolution, ...),
     ``predict(person_bbox_list, batch_size, conf_threshold) -> dump_results`` (ivclabpose.py:131-132,210)."""
@@ -306,11 +315,8 @@ class HRNetPose(object):
         self.dtype = dtype
         self.max_dets = max_dets
         if checkpoint_path and os.path.exists(checkpoint_path):
-            model = PoseHighResolutionNet(c, nof_joints)
-            sd = torch.load(checkpoint_path, map_location='cpu')
-            model.load_state_dict(sd.get('model', sd) if isinstance(sd, dict) else sd)
+            model = load_folded_checkpoint(checkpoint_path, c, nof_joints)
             self.weights = checkpoint_path
-            model = fold_batchnorm(model)
         else:
             model = _folded_random_model(c, nof_joints, seed)
             self.weights = 'random(seed=%d)' % seed

@@ -1,0 +1,335 @@
+"""GPU: the HIP HRNet executor's wiring against the fp32 torch network, piece by piece -- stem + layer1, the four transitions (plain
+and as the lazy first conv of a new branch), every output of all eight HR modules -- on the calibrated network of hrnet_calibrated.py,
+whose folded biases and per-channel scales are non-trivial (the product's random weights fold to zero biases: a bias packed into
+the wrong part of a merged conv, dropped from a fused tail or zeroed in a fused sum cannot show on them).
+
+Each piece reads the fp32 reference forward's own input to that piece rounded to bf16 (the same tensor on both sides) and is
+compared with the fp32 torch submodule whose conv weights are rounded to bf16 as the packing rounds them (biases fp32).  The error
+left is the bf16 storage of the piece's intermediate activations.  Per output branch the relative L2 error is bounded over the
+whole tensor, per crop, on each edge strip (first / last row, first / last column) and per 16-channel group: a fault confined to
+one term of one output, one border column or one part of a merged conv moves its own metric by many times the noise while the
+whole-network heat-map error barely moves (tolerances: TOL)."""
+import contextlib
+import itertools
+import json
+import os
+
+import pytest
+import torch
+
+import hrnet_calibrated as HC
+
+pytestmark = pytest.mark.gpu
+
+# (resolution, crops): 384 x 288 -> branches 96x72 / 48x36 / 24x18 / 12x9 (odd coarse width), 256 x 192 -> 64x48 / ... / 8x6
+SHAPES = [((384, 288), 1), ((384, 288), 3), ((384, 288), 20), ((256, 192), 1), ((256, 192), 5)]
+SHAPE_IDS = ['%dx%d-n%d' % (r[0], r[1], n) for r, n in SHAPES]
+
+METRICS = ('all', 'crop', 'row0', 'rowL', 'col0', 'colL', 'ch16')
+# Largest relative L2 error allowed per family and metric: 2.5 x the largest error the MI355X showed over every shape and executor case
+# of this file (2405 compared outputs), rounded up.  Observed maxima (all / crop / row0 / rowL / col0 / colL / ch16, in 1e-3):
+#   stem 2.6 2.6 2.5 2.7 2.5 2.6 2.7 | head 5.8 5.8 5.2 5.3 5.2 5.4 6.4 | transitions 1.7 1.7 1.7 1.7 1.7 1.7 1.8
+#   stage 2 5.2 5.2 5.3 5.5 5.1 5.3 5.6 | stage 3 5.5 5.6 4.8 5.6 5.1 5.4 6.0 | stage 4 6.0 6.0 5.3 6.1 5.5 6.1 6.7
+# Planted faults (not committed) exceeded these bounds by 15-100 x on the 384x288, 3-crop cases alone (each one also failed the
+# whole-network test below; test_gpu_image.py::test_bf16_stack_vs_fp32 caught the k_upsample_add one only):
+#   merged conv biases concatenated in reverse part order     -> modules (every case with merged fuse convs), lazy transitions
+#   first Bottleneck's downsample bias dropped from PackedTail -> head (fused tail)
+#   the coarsest source's bias zeroed in PackedUp              -> modules (every fused_sums case)
+#   k_upsample_add skips the last term column at odd widths    -> modules (every case with k_upsample_add sums), lazy transitions
+#   output 1 of _hr_module drops its plain term when fused     -> modules (fused_sums 15 / 10)
+TOL = {
+    'stem':       dict(all=0.007, crop=0.007, row0=0.007, rowL=0.007, col0=0.007, colL=0.007, ch16=0.007),
+    'head':       dict(all=0.015, crop=0.015, row0=0.013, rowL=0.014, col0=0.014, colL=0.014, ch16=0.017),
+    'transition': dict(all=0.005, crop=0.005, row0=0.005, rowL=0.005, col0=0.005, colL=0.005, ch16=0.005),
+    'stage2':     dict(all=0.014, crop=0.014, row0=0.014, rowL=0.014, col0=0.013, colL=0.014, ch16=0.014),
+    'stage3':     dict(all=0.014, crop=0.014, row0=0.013, rowL=0.014, col0=0.013, colL=0.014, ch16=0.015),
+    'stage4':     dict(all=0.015, crop=0.016, row0=0.014, rowL=0.016, col0=0.014, colL=0.016, ch16=0.017),
+}
+
+
+def rel(d, r):
+    return float(d.norm() / r.norm().clamp_min(1e-30))
+
+
+def metrics(got, ref):
+    """Relative L2 errors of one output branch (N, C, H, W): whole tensor, worst crop, the four edge strips, worst 16-channel group."""
+    g, r = got.float(), ref.float()
+    d = g - r
+    return dict(all=rel(d, r),
+                crop=max(rel(d[i], r[i]) for i in range(r.shape[0])),
+                row0=rel(d[:, :, 0], r[:, :, 0]), rowL=rel(d[:, :, -1], r[:, :, -1]),
+                col0=rel(d[:, :, :, 0], r[:, :, :, 0]), colL=rel(d[:, :, :, -1], r[:, :, :, -1]),
+                ch16=max(rel(d[:, c:c + 16], r[:, c:c + 16]) for c in range(0, r.shape[1], 16)))
+
+
+class Checker(object):
+    """Collects the metrics of every compared output of one test, prints them (one JSON line each: `pytest -s` shows the observed
+    errors next to TOL) and fails with every bound that was exceeded."""
+
+    def __init__(self, test):
+        self.test, self.bad = test, []
+
+    def __call__(self, family, where, got, ref):
+        assert tuple(got.shape) == tuple(ref.shape), (where, tuple(got.shape), tuple(ref.shape))
+        m = metrics(got, ref)
+        print('PARITY ' + json.dumps(dict(test=self.test, family=family, where=where, **{k: round(v, 6) for k, v in m.items()})))
+        self.bad += ['%s %s: %s %.4g > %.4g' % (family, where, k, m[k], TOL[family][k]) for k in METRICS if not m[k] <= TOL[family][k]]
+
+    def done(self):
+        assert not self.bad, '\n'.join(self.bad[:40])
+
+
+class Env(object):
+    pass
+
+
+@pytest.fixture(scope='module')
+def env():
+    """ONE eager executor for every case of this file (a construction packs 63 M weights), the fp32 reference on the device and, per
+    shape, the reference forward's taps (computed once)."""
+    from pam import hrnet_hip
+    saved = (torch.backends.cudnn.allow_tf32, torch.backends.cuda.matmul.allow_tf32)
+    torch.backends.cudnn.allow_tf32 = False                           # the reference is fp32 arithmetic, not TF32
+    torch.backends.cuda.matmul.allow_tf32 = False
+    e = Env()
+    e.dev = torch.device('cuda:0')
+    folded = HC.folded_copy()
+    e.ref = HC.bf16_weights(folded).to(e.dev).eval()
+    e.hip = hrnet_hip.HipHRNet(folded, e.dev)
+    e.taps, e.mod_ref = {}, {}
+    try:
+        yield e
+    finally:
+        torch.backends.cudnn.allow_tf32, torch.backends.cuda.matmul.allow_tf32 = saved
+
+
+def bf(t):
+    """bf16 channels-last copy (the HIP side's input); .float() of it is the reference side's."""
+    return t.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+
+
+def taps(e, res, n):
+    """(bf16 input crops, the fp32 reference forward on them tapped per piece: hrnet_calibrated.stage_inputs)."""
+    key = (res, n)
+    if key not in e.taps:
+        g = torch.Generator().manual_seed(1000 + 31 * n + res[0])
+        x = torch.randn((n, 3) + tuple(res), generator=g).to(torch.bfloat16).to(e.dev)
+        e.taps[key] = (x, HC.stage_inputs(e.ref, x.float()))
+    return e.taps[key]
+
+
+STAGES = [('stage2', 0), ('stage3', 0), ('stage3', 1), ('stage3', 2), ('stage3', 3), ('stage4', 0), ('stage4', 1), ('stage4', 2)]
+
+
+def module_ref(e, res, n, stage, m):
+    """(bf16 inputs, fp32 outputs) of HR module m of `stage` on the reference's own input to it rounded to bf16."""
+    key = (res, n, stage, m)
+    if key not in e.mod_ref:
+        xs = [bf(t) for t in taps(e, res, n)[1][stage][m]]
+        with torch.no_grad():
+            out = getattr(e.ref, stage)[m]([t.float() for t in xs])
+        e.mod_ref[key] = (xs, out)
+    return e.mod_ref[key]
+
+
+_UNSET = object()
+
+
+@contextlib.contextmanager
+def knobs(hip, **kw):
+    """Executor attributes set for one case and restored (instance attributes removed again) afterwards."""
+    saved = {k: hip.__dict__.get(k, _UNSET) for k in kw}
+    for k, v in kw.items():
+        setattr(hip, k, v)
+    try:
+        yield
+    finally:
+        for k, v in saved.items():
+            if v is _UNSET:
+                hip.__dict__.pop(k, None)
+            else:
+                setattr(hip, k, v)
+
+
+def issue(hip, fn):
+    """One piece of the executor, eager, on its own: every tensor it makes is kept until the device is idle."""
+    torch.cuda.synchronize()
+    hip._keep, hip.arena = [], None
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+    finally:
+        hip._keep = None
+    return out
+
+
+# -- stem + layer1 ----------------------------------------------------------------------------------------------------------------
+HEAD_FLAGS = ('fuse_stem', 'fuse_tail', 'fuse_bneck', 'fuse_bneck0')
+
+
+@pytest.mark.parametrize('res,n', SHAPES, ids=SHAPE_IDS)
+def test_head_vs_fp32_in_every_fusion_combination(env, res, n):
+    """hip._head (stem + layer1) in all 16 combinations of the fusion switches (fuse_stem / fuse_bneck need fuse_tail: without it the
+    executor takes the un-fused launches, which must be as right), and the stop_after='stem' tap."""
+    e, hip = env, env.hip
+    x, t = taps(e, res, n)
+    x8 = bf(torch.cat([x, torch.zeros((n, 5) + tuple(res), dtype=x.dtype, device=x.device)], 1))
+    chk = Checker('head %s n%d' % (res, n))
+    for combo in itertools.product((True, False), repeat=4):
+        kw = dict(zip(HEAD_FLAGS, combo))
+        with knobs(hip, **kw):
+            y = issue(hip, lambda: hip._head(x8))
+        chk('head', ','.join(k for k, v in kw.items() if v) or 'unfused', y, t['layer1'])
+    for fs in (True, False):
+        with knobs(hip, stop_after='stem', fuse_stem=fs):
+            y = issue(hip, lambda: hip._head(x8))
+        chk('stem', 'stop_after=stem fuse_stem=%s' % fs, y, t['stem'])
+    chk.done()
+
+
+# -- transitions -------------------------------------------------------------------------------------------------------------------
+def _transition_cases(e, t):
+    """(name, packed op, bf16 input, reference submodule) of the four transition convolutions."""
+    ref, hip = e.ref, e.hip
+    return [('t1[0]', hip.t1[0], bf(t['layer1']), ref.transition1[0]),
+            ('t1[1]', hip.t1[1], bf(t['layer1']), ref.transition1[1]),
+            ('t2', hip.t2, bf(t['stage3'][0][1]), ref.transition2[2]),
+            ('t3', hip.t3, bf(t['stage4'][0][2]), ref.transition3[3])]
+
+
+@pytest.mark.parametrize('res,n', SHAPES, ids=SHAPE_IDS)
+def test_transitions_vs_fp32(env, res, n):
+    """The transition convolutions as plain launches, on the streamed stride-2 kernels and on the generic ones (down_s)."""
+    e, hip = env, env.hip
+    chk = Checker('transitions %s n%d' % (res, n))
+    for name, op, xin, sub in _transition_cases(e, taps(e, res, n)[1]):
+        with torch.no_grad():
+            r = sub(xin.float())
+        for down_s in (True, False):
+            with knobs(hip, down_s=down_s):
+                y = issue(hip, lambda: hip.conv(op, xin, relu=True))
+            chk('transition', '%s down_s=%s' % (name, down_s), y, r)
+    chk.done()
+
+
+@pytest.mark.parametrize('multi_stream', [True, False], ids=['multi_stream', 'one_stream'])
+@pytest.mark.parametrize('res,n', SHAPES, ids=SHAPE_IDS)
+def test_lazy_transitions_inside_the_first_module_of_each_stage(env, res, n, multi_stream):
+    """The ('lazy', op, src) branch _hr_module resolves on the new branch's own stream: the first module of every stage with its new
+    branches handed over lazily, every output against transition + module in fp32."""
+    e, hip, ref = env, env.hip, env.ref
+    t = taps(e, res, n)[1]
+    chk = Checker('lazy %s n%d %s' % (res, n, multi_stream))
+    l1 = bf(t['layer1'])
+    s3, s4 = [bf(q) for q in t['stage3'][0][:2]], [bf(q) for q in t['stage4'][0][:3]]
+    cases = [('stage2', [('lazy', hip.t1[0], l1), ('lazy', hip.t1[1], l1)], lambda: [ref.transition1[0](l1.float()), ref.transition1[1](l1.float())]),
+             ('stage3', s3 + [('lazy', hip.t2, s3[1])], lambda: [q.float() for q in s3] + [ref.transition2[2](s3[1].float())]),
+             ('stage4', s4 + [('lazy', hip.t3, s4[2])], lambda: [q.float() for q in s4] + [ref.transition3[3](s4[2].float())])]
+    for stage, xs, ref_in in cases:
+        with torch.no_grad():
+            r = getattr(ref, stage)[0](ref_in())
+        with knobs(hip, multi_stream=multi_stream):
+            out = issue(hip, lambda: hip._hr_module(getattr(hip, stage)[0], xs))
+        assert len(out) == len(r)
+        for i, (y, q) in enumerate(zip(out, r)):
+            chk(stage, '%s[0] lazy out%d' % (stage, i), y, q)
+    chk.done()
+
+
+# -- HR modules ----------------------------------------------------------------------------------------------------------------------
+def _module_cases():
+    from pam.hrnet_hip import HipHRNet
+    base = dict(HipHRNet.CONFIGS['fused48_fused96'], merge_fuse=True, merge_up=True, multi_stream=True)
+    cases = {}
+    for name, cfg in HipHRNet.CONFIGS.items():
+        for ms in (True, False):
+            cases['%s-%s' % (name, 'ms' if ms else '1s')] = dict(base, **cfg, multi_stream=ms)
+    cases['no_merge_fuse'] = dict(base, merge_fuse=False)
+    cases['no_merge_up'] = dict(base, merge_up=False)
+    cases['fused_sums5'] = dict(base, fused_sums=5)                   # outputs 0 and 2 through k_fuse_sum, 1 and 3 through k_upsample_add
+    cases['fused_sums10'] = dict(base, fused_sums=10)
+    cases['fused_sums10-1s'] = dict(base, fused_sums=10, multi_stream=False)
+    for b in (0, 1, 2):
+        cases['block2=%d' % b] = dict(base, block2=b)
+    cases['block2=0-c96_slab=0'] = dict(base, block2=0, c96_slab=0)   # the 96-channel branch's convolutions on k_conv3x3
+    cases['block2=1-c96_slab=0'] = dict(base, block2=1, c96_slab=0)
+    cases['block2=0-c96_slab=48'] = dict(base, block2=0, c96_slab=48)
+    return cases
+
+
+MODULE_CASES = _module_cases()
+
+
+@pytest.mark.parametrize('case', sorted(MODULE_CASES))
+@pytest.mark.parametrize('res,n', SHAPES, ids=SHAPE_IDS)
+def test_every_output_of_every_hr_module_vs_fp32(env, res, n, case):
+    """All eight HR modules, every output, in one executor configuration: the CONFIGS entries on one stream and on the branch streams,
+    the un-merged fuse convolutions, mixed fused-sum masks, the fused-block switches and the 96-channel slab width."""
+    e, hip = env, env.hip
+    chk = Checker('modules %s n%d %s' % (res, n, case))
+    with knobs(hip, **MODULE_CASES[case]):
+        for stage, m in STAGES:
+            xs, r = module_ref(e, res, n, stage, m)
+            out = issue(hip, lambda: hip._hr_module(getattr(hip, stage)[m], xs))
+            assert len(out) == len(r), (stage, m)
+            for i, (y, q) in enumerate(zip(out, r)):
+                chk(stage, '%s[%d] out%d' % (stage, m, i), y, q)
+    chk.done()
+
+
+# -- whole network -------------------------------------------------------------------------------------------------------------------
+# Heat-maps vs the fp32 network.  The per-module error (~0.5 %) compounds over stem, layer1 and eight modules, and this network amplifies
+# it: with bf16 weights alone the heat-maps move by 2.6 %, with bf16 weights AND a bf16 store after every conv, block and module (fp32
+# arithmetic otherwise: hrnet_calibrated.bf16_storage) by 4.3 % -- a floor for a bf16 executor, so no fixed bound under it can hold.
+# The HIP stack measured 4.17 % in every configuration (0.97 x that floor); it must stay within NET_FLOOR_RATIO of the floor computed
+# for the same crops.  (On the product's random-weight network the same floor is 0.67 %.)
+NET_FLOOR_RATIO = 1.1
+
+
+@pytest.fixture(scope='module')
+def calibrated_checkpoint(tmp_path_factory):
+    path = os.path.join(str(tmp_path_factory.mktemp('calibrated')), 'pose_hrnet_w48_384x288.pth')
+    torch.save(HC.calibrated()[0], path)
+    return path
+
+
+def test_whole_network_on_calibrated_weights_in_every_configuration(env, calibrated_checkpoint):
+    """HRNetPose built from a checkpoint of the calibrated network, ONE replaying object: in each executor configuration the replay
+    equals the same object's eager forward bitwise, the heat-maps' error vs the fp32 network stays within NET_FLOOR_RATIO of what bf16
+    storage alone costs, and every joint drift_statistics calls decided (k = 4, 8) decodes to the same cell."""
+    from pam import hrnet, hrnet_hip
+    n = 3
+    net = hrnet.HRNetPose(48, 17, calibrated_checkpoint, resolution=(384, 288), use_graph=True, max_crops=n)
+    assert net.weights == calibrated_checkpoint
+    ref = HC.folded_copy().to(net.device).eval()
+    x = torch.randn((n, 3, 384, 288), generator=torch.Generator().manual_seed(77)).to(torch.bfloat16).to(net.device)
+    x8 = net.input_buffer(n)
+    x8.zero_()
+    x8[:, :3] = x
+    with torch.no_grad():
+        h32 = ref(x.float())
+        floor = float((HC.bf16_storage(ref)(x.float()) - h32).norm() / h32.norm())
+    assert 0.02 < floor < 0.06, floor
+    bad = []
+    for name in hrnet_hip.HipHRNet.CONFIGS:
+        net.config_for = lambda k, name=name: name
+        net._dead_graphs.extend(v for v in net._graphs.values()); net._dead_graphs.extend(v for v in net._alt.values() if v is not None)
+        net._graphs.clear(); net._alt.clear(); net.flag_synced.clear(); net.flag_timing.clear()
+        hr = net.heatmaps(x8).clone()                                 # capture, then replay
+        hr2 = net.heatmaps(x8).clone()
+        assert net.hip.config_name == name
+        with torch.no_grad():
+            he = net._forward(x8, 'heatmaps').clone()                 # the same object's executor, eager
+        torch.cuda.synchronize()
+        assert torch.equal(hr, hr2) and torch.equal(hr, he), name
+        d = hrnet.drift_statistics(h32, he.float())
+        print('NETWORK ' + json.dumps(dict(config=name, rel=d['rel_l2_err'], floor=floor, rms=d['rms_err'], decided=d['decided'],
+                                           planted=d['planted_peak_max_cells'], moved=d['argmax_moved_frac'])))
+        if not d['rel_l2_err'] <= NET_FLOOR_RATIO * floor:
+            bad.append('%s: heat-map rel err %.4g > %.2f x the bf16 floor %.4g' % (name, d['rel_l2_err'], NET_FLOOR_RATIO, floor))
+        for k in ('4', '8'):
+            if d['decided'][k]['max_cells'] != 0:
+                bad.append('%s: a decided joint (k=%s) moved %d cells' % (name, k, d['decided'][k]['max_cells']))
+        if d['planted_peak_max_cells']['8'] != 0:
+            bad.append('%s: a planted peak of 8 sigmas moved' % name)
+    assert not bad, bad
