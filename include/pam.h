@@ -267,6 +267,14 @@ int pam_conv3x3_layout_small(int H, int W, int Cin, int Cout);
 #define PAM_CONV_KERNEL_GS    3   /* k_conv_gs   */
 #define PAM_CONV_KERNEL_STEM  4   /* k_conv_stem */
 int pam_conv_last_kernel(void);
+/* which instantiation of that kernel it launched, a decimal code whose fields are the kernel's template parameters:
+ *   PAM_CONV_KERNEL_IGEMM  G*1000000 + BM*1000 + BN       G = 1: general-activation epilogue (codes > 1); BM x BN = pixel x channel tile
+ *   PAM_CONV_KERNEL_3X3    Cin*10 + NTW                   output-channel slab 16*NTW
+ *   PAM_CONV_KERNEL_3X3S   G*100000 + Cin*100 + NTW*10 + MT   G = 1: general-activation form (tile_cfg -7); slab 16*NTW; MT M tiles per wave
+ *   PAM_CONV_KERNEL_GS     NBUF*1000000 + BM*1000 + 16*NTW    chunk ring depth, pixel tile, output-channel slab
+ *   PAM_CONV_KERNEL_STEM   S*100 + Cout                   stride 1 / 2, 32 or 64 output channels
+ * Kernel and form are recorded together, by the launcher, from the launched kernel's own template parameters. */
+int pam_conv_last_form(void);
 /* diagnostic builds only: device buffer (64 x uint64 per workgroup) for k_conv3x3's s_memtime stamps, used when tile_cfg = 100 + 64 */
 int pam_conv_debug_stamps(void* dev_buf);
 int pam_upsample_add_nhwc_bf16(void* stream, const void* base, int n_terms, const void* const* terms,

@@ -27,6 +27,13 @@ __device__ __forceinline__ float epi_act(float v, float r, int act) {
     return (act & 4) ? epi_act1(v, act & 3) + r : epi_act1(v + r, act & 3);
 }
 
+// which kernel (PAM_CONV_KERNEL_*) and which instantiation of it (the form: include/pam.h) the calling thread's last
+// pam_conv2d_nhwc_bf16[_ex] call launched.  Both are recorded by ONE statement inside each launcher, from the template parameters of
+// the kernel it launches, so the two cannot disagree with each other or with the launch (profiling labels, tests of the tile choice).
+static thread_local int g_last_conv_kernel = 0;
+static thread_local int g_last_conv_form = 0;
+#define CONV_KIND(k, form) (g_last_conv_kernel = (k), g_last_conv_form = (form))
+
 struct ConvArgs {
     const uint16_t* in; const uint16_t* w; const float* bias; const uint16_t* res; uint16_t* out;
     int N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, relu, Ktot, Kpad, M;
@@ -288,12 +295,14 @@ template <int NTW, int WM, int WN>
 static int launch_conv(hipStream_t s, const ConvArgs& a) {
     constexpr int BM_ = 64 * WM, BN_ = 16 * NTW * WN;
     if (a.relu > 1) {                                   // Darknet activation codes: the general-epilogue instantiation
+        CONV_KIND(PAM_CONV_KERNEL_IGEMM, 1000000 + BM_ * 1000 + BN_);
         dim3 grid((a.M + BM_ - 1) / BM_, a.Cout / BN_);
         const size_t lds = (a.Kpad > KC ? 2 : 1) * (size_t)(BM_ + BN_) * ROWB;
         pam_launch(k_conv_igemm<NTW, WM, WN, true>, grid, dim3(64 * WM * WN), lds, s, a);
         return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
     }
     constexpr int BM = 64 * WM, BN = 16 * NTW * WN;
+    CONV_KIND(PAM_CONV_KERNEL_IGEMM, BM * 1000 + BN);
     dim3 grid((a.M + BM - 1) / BM, a.Cout / BN);
     const size_t lds = (a.Kpad > KC ? 2 : 1) * (size_t)(BM + BN) * ROWB;
     pam_launch(k_conv_igemm<NTW, WM, WN, false>, grid, dim3(64 * WM * WN), lds, s, a);
@@ -630,6 +639,7 @@ static int launch_c3_one(hipStream_t s, const C3Args& a) {
     dim3 grid(a.tiles_y * a.N, a.Cout / (16 * NTW));
     const size_t lds = c3_lds_bytes(CIN, NTW, npatch);
     if (lds > 150 * 1024) return PAM_E_ARG;
+    CONV_KIND(PAM_CONV_KERNEL_3X3, CIN * 10 + NTW);
     if (CIN / c3_ck(CIN) == 1 && !C3_DBG(128)) {        // single-chunk layers: persistent workgroups (see the kernel)
         int per_cu = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_conv3x3<CIN, NTW, MT, NWAVES, PMAX>, 64 * NWAVES, lds) != hipSuccess || per_cu < 1) per_cu = 1;
@@ -987,6 +997,7 @@ template <int CIN, int NTW, int MT, int PMAX>
 static int launch_c3s_gen_one(hipStream_t s, const C3Args& a) {
     constexpr size_t lds = (size_t)2 * (PMAX * 64 + 9 * 16 * NTW * 64);
     if (!pam_max_dynamic_lds((const void*)k_conv3x3s<CIN, NTW, MT, PMAX, 2, true>, (int)lds)) return PAM_E_HIP;
+    CONV_KIND(PAM_CONV_KERNEL_3X3S, 100000 + CIN * 100 + NTW * 10 + MT);
     pam_launch(k_conv3x3s<CIN, NTW, MT, PMAX, 2, true>, dim3(a.tiles_y * a.N, a.Cout / (16 * NTW)), dim3(512), lds, s, a);
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
 }
@@ -1016,6 +1027,7 @@ static int launch_c3s_one(hipStream_t s, const C3Args& a) {
     constexpr size_t lds = (size_t)NBUF * (PMAX * 64 + 9 * 16 * NTW * 64);
     static_assert(lds <= 160 * 1024, "LDS");
     if (!pam_max_dynamic_lds((const void*)k_conv3x3s<CIN, NTW, MT, PMAX, NBUF>, (int)lds)) return PAM_E_HIP;
+    CONV_KIND(PAM_CONV_KERNEL_3X3S, CIN * 100 + NTW * 10 + MT);
     pam_launch(k_conv3x3s<CIN, NTW, MT, PMAX, NBUF>, dim3(a.tiles_y * a.N, a.Cout / (16 * NTW)), dim3(512), lds, s, a);
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
 }
@@ -1283,6 +1295,7 @@ static int launch_conv_gs_r(hipStream_t s, const ConvArgs& a) {
     constexpr size_t lds = (size_t)NBUF * (BM + 16 * NTW) * 128;
     static_assert(lds <= 160 * 1024, "LDS");
     if (!pam_max_dynamic_lds((const void*)k_conv_gs<NTW, NBUF, RES, BM>, (int)lds)) return PAM_E_HIP;
+    CONV_KIND(PAM_CONV_KERNEL_GS, NBUF * 1000000 + BM * 1000 + 16 * NTW);
     const int ntile = ((a.M + BM - 1) / BM) * (a.Cout / (16 * NTW));
     pam_launch(k_conv_gs<NTW, NBUF, RES, BM>, dim3(ntile < 256 ? ntile : 256), dim3(512), lds, s, a);
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
@@ -1372,10 +1385,9 @@ extern "C" int pam_conv2d_nhwc_bf16(void* stream, const void* in, const void* w_
     return pam_conv2d_nhwc_bf16_ex(stream, in, w_packed, w_img, bias, residual, out, N, H, W, Cin, Cout, KH, KW, stride, pad, relu,
                                    tile_cfg, Cin, 0);
 }
-// which kernel the last pam_conv2d_nhwc_bf16[_ex] call of this thread launched (profiling labels: bench.py's per-family roofline)
-static thread_local int g_last_conv_kernel = 0;
+// profiling labels (bench.py's per-family roofline) and the tests' record of the tile choice: see g_last_conv_kernel
 extern "C" int pam_conv_last_kernel(void) { return g_last_conv_kernel; }
-#define CONV_KIND(k) (g_last_conv_kernel = (k))
+extern "C" int pam_conv_last_form(void) { return g_last_conv_form; }
 extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void* w_packed, const void* w_img, const float* bias,
                                        const void* residual, void* out, int N, int H, int W, int Cin, int Cout,
                                        int KH, int KW, int stride, int pad, int relu, int tile_cfg, int in_cstride, int relu_from) {
@@ -1397,7 +1409,6 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
 #ifdef PAM_DIAG
         c.dbg = 0; c.stamps = nullptr;
 #endif
-        CONV_KIND(PAM_CONV_KERNEL_3X3S);
         return launch_c3s_gen((hipStream_t)stream, c, Cin, mt);
     }
     // -8: a 192- / 384-channel ReLU / linear layer on the streamed kernel with 32-channel slabs (pam_conv3x3_layout_small; same arithmetic;
@@ -1414,7 +1425,6 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
 #ifdef PAM_DIAG
         c.dbg = 0; c.stamps = nullptr;
 #endif
-        CONV_KIND(PAM_CONV_KERNEL_3X3S);
         return launch_c3s((hipStream_t)stream, c, Cin, 2, mt, pmax);
     }
     const int c96_slab = tile_cfg == -5 ? 48 : 0;
@@ -1440,7 +1450,7 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
         t.N = N; t.H = H; t.W = W; t.Ho = a.Ho; t.Wo = a.Wo; t.relu = relu;
         const dim3 grid((N * a.Ho + 3) / 4), blk(256);
         hipStream_t s = (hipStream_t)stream;
-        CONV_KIND(PAM_CONV_KERNEL_STEM);
+        CONV_KIND(PAM_CONV_KERNEL_STEM, stride * 100 + Cout);
         if (stride == 2 && Cout == 64) pam_launch(k_conv_stem<2, 4>, grid, blk, 0, s, t);
         else if (stride == 2) pam_launch(k_conv_stem<2, 2>, grid, blk, 0, s, t);
         else if (Cout == 64) pam_launch(k_conv_stem<1, 4>, grid, blk, 0, s, t);
@@ -1463,7 +1473,6 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
 #ifdef PAM_DIAG
             c.dbg = g_c3_stamps ? 64 : 0; c.stamps = g_c3_stamps;
 #endif
-            CONV_KIND(PAM_CONV_KERNEL_3X3S);
             return launch_c3s((hipStream_t)stream, c, Cin, ntw, mt, pmax);
         }
     }
@@ -1486,15 +1495,17 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
             else c.dbg = tile_cfg - 100;
 #endif
         }
-        if (c.TH * (W + 2) > 16 * (cfg / 10) * (cfg % 10)) return PAM_E_ARG;
+        // a row wider than the block's output slots (W + 2 > 256: the detector's 64-channel layers from 512 x 512 inputs, e.g. 304 x 304
+        // at 608) does not fit at all: the generic kernel below takes it, like any other tile that does not fit (only the tuning hooks refuse)
+        const bool rows_fit = c.TH * (W + 2) <= 16 * (cfg / 10) * (cfg % 10);
+        if (!rows_fit && tile_cfg >= 100) return PAM_E_ARG;
         c.tiles_y = (H + c.TH - 1) / c.TH;
         hipStream_t s = (hipStream_t)stream;
         // rows too wide for the patch-in-LDS kernel (e.g. the detector's 208-wide layers): the generic kernel takes them
         const int npatch = (c.TH + 2) * (W + 2), pmax = (cfg == 44 || cfg == 54) ? 416 : (cfg == 43 ? 352 : 288);
-        const bool fits = npatch <= pmax && c3_lds_bytes(Cin, ntw, npatch) <= 150 * 1024 && Cout % (16 * ntw) == 0 &&
+        const bool fits = rows_fit && npatch <= pmax && c3_lds_bytes(Cin, ntw, npatch) <= 150 * 1024 && Cout % (16 * ntw) == 0 &&
                           (relu <= 1 || c3_general_act(Cin));
         if (!fits && tile_cfg >= 100) return PAM_E_ARG;
-        if (fits) CONV_KIND(PAM_CONV_KERNEL_3X3);
         if (fits) switch (Cin * 10 + ntw) {
             case 483: return launch_c3<48, 3>(s, c, cfg);
             case 643: return launch_c3<64, 3>(s, c, cfg);
@@ -1525,7 +1536,6 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
     const bool leaky_gs = relu == 2 && !a.res && classic && relu_from == 0;
     const bool gs_ok = (relu <= 1 || leaky_gs) && KH * KW <= 9 && Cin % 8 == 0 && (size_t)N * H * W * in_cstride * 2 < (1u << 31);
     if (leaky_gs && gs_ok && tile_cfg == -1 && conv_gs_auto(a)) {
-        CONV_KIND(PAM_CONV_KERNEL_GS);
         if (Cout % 48 == 0) return launch_conv_gs<3>((hipStream_t)stream, a);
         // Darknet's widths are multiples of 64: the smallest pixel tile that still is ONE round of workgroups, as for HRNet's small fuse convolutions
         const int nslab = Cout / 64;
@@ -1536,25 +1546,22 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
     if (tile_cfg >= 8 && tile_cfg <= 12 && !gs_ok) return PAM_E_ARG;
     if (tile_cfg == 12) {                               // 64-pixel tiles: the smallest images (12 x 9) as a few hundred short workgroups
         if (a.res || Cout % 48 != 0) return PAM_E_ARG;
-        CONV_KIND(PAM_CONV_KERNEL_GS);
         return launch_conv_gs_r<3, false, 64, 3>((hipStream_t)stream, a);
     }
     if (tile_cfg == 10 || tile_cfg == 11) {             // 128-pixel tiles, ring of 5 (10) / 3 (11) chunks: twice the workgroups, deeper prefetch
         if (a.res || Cout % 48 != 0) return PAM_E_ARG;
-        CONV_KIND(PAM_CONV_KERNEL_GS);
         return tile_cfg == 10 ? launch_conv_gs_r<3, false, 128, 5>((hipStream_t)stream, a) : launch_conv_gs_r<3, false, 128, 3>((hipStream_t)stream, a);
     }
     if (tile_cfg == 9)                                  // streamed implicit GEMM with 96-channel slabs: the gathered pixel tile feeds twice the MFMAs
-        return Cout % 96 == 0 ? (CONV_KIND(PAM_CONV_KERNEL_GS), launch_conv_gs<6>((hipStream_t)stream, a)) : PAM_E_ARG;
+        return Cout % 96 == 0 ? launch_conv_gs<6>((hipStream_t)stream, a) : PAM_E_ARG;
     // large-M strided layers with whole 96-channel slabs and no residual (merged fuse heads 48 -> 96 / 192 at 96 x 72, transition1's
     // 256 -> 96): the 96-channel-slab form gathers every pixel tile half as often (26.3 -> 23.3, 16.2 -> 13.2, 46.2 -> 31.4 us at 20 crops;
     // slower below ~100 pixel tiles, where the layer is a latency chain whatever its tile)
 #ifndef PAM_GS_OLDTILES                                  /* A/B hook (tools/ab_build.sh): round-2 tile choice */
     if (gs_ok && tile_cfg == -1 && !classic && !a.res && Cout % 96 == 0 && KH == 3 && stride == 2 && a.M >= 100 * 256)
-        return CONV_KIND(PAM_CONV_KERNEL_GS), launch_conv_gs<6>((hipStream_t)stream, a);
+        return launch_conv_gs<6>((hipStream_t)stream, a);
 #endif
     if (gs_ok && (tile_cfg == 8 || (tile_cfg == -1 && !classic && conv_gs_auto(a)))) {
-        CONV_KIND(PAM_CONV_KERNEL_GS);
 #ifndef PAM_GS_OLDTILES
         if (tile_cfg == -1 && !a.res && Cout % 48 == 0) {
             // the small fuse-layer convolutions are latency chains of a few workgroups: the smallest pixel tile that still is ONE round of
@@ -1567,7 +1574,6 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
 #endif
         return (Cout % 48 == 0) ? launch_conv_gs<3>((hipStream_t)stream, a) : launch_conv_gs<4>((hipStream_t)stream, a);
     }
-    CONV_KIND(PAM_CONV_KERNEL_IGEMM);
     return (Cout % 48 == 0) ? dispatch_conv<3>((hipStream_t)stream, a, tile_cfg) : dispatch_conv<4>((hipStream_t)stream, a, tile_cfg);
 }
 

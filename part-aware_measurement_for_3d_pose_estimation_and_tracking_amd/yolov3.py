@@ -302,30 +302,33 @@ class HipDarknet(ConvEngine):
 
     def forward(self, x8):
         """x8: (N, 8, H, W) channels-last bf16 (RGB in [0,1] + 5 zero channels) -> head tensors, channels-last bf16."""
-        outs, heads = {-1: x8}, []
+        outs = {-1: x8}
         for step in self.plan:
-            kind, dst = step[0], step[1]
-            if kind == 'conv':
-                _, _, op, src, act, skip = step
-                if skip is not None and self.unfuse_wide and op.kh == 3 and op.stride == 1 and outs[src].shape[3] + 2 > 138:
-                    # rows too wide for the rows-in-LDS 3x3 kernels (the 208-wide block of the 416 x 416 network): with the shortcut
-                    # folded in, the layer fell to the classic implicit GEMM (90 us for 5 views); as a residual-free convolution it runs on
-                    # the streamed implicit GEMM and the shortcut is one k_upsample_add (round 5: 90 -> 25 + 17 us)
-                    y = self.conv(op, outs[src], relu=act)
-                    outs[dst] = self.upsample_add(y, [outs[skip]], [0], relu=False)
-                    continue
-                outs[dst] = self.conv(op, outs[src], res=outs[skip] if skip is not None else None, relu=act,
-                                      res_after_act=skip is not None)
-            elif kind == 'add':
-                outs[dst] = self.upsample_add(outs[step[2]], [outs[step[3]]], [0], relu=False)
-            elif kind == 'alias':
-                outs[dst] = outs[step[2]]
-            elif kind == 'upcat':
-                outs[dst] = self.upsample_concat(outs[step[2]], outs[step[3]])
-            else:
-                outs[dst] = outs[step[2]]
-                heads.append(outs[dst])
-        return heads
+            outs[step[1]] = self.run_step(step, outs)
+        return [outs[step[1]] for step in self.plan if step[0] == 'head']
+
+    def run_step(self, step, outs):
+        """One entry of ``plan`` on the layer outputs it reads (outs: layer index -> tensor, -1 = the input) -> its output."""
+        kind = step[0]
+        if kind == 'conv':
+            _, _, op, src, act, skip = step
+            if self.unfused(step, outs[src]):
+                # rows too wide for the rows-in-LDS 3x3 kernels (the 208-wide block of the 416 x 416 network): with the shortcut
+                # folded in, the layer fell to the classic implicit GEMM (90 us for 5 views); as a residual-free convolution it runs on
+                # the streamed implicit GEMM and the shortcut is one k_upsample_add (round 5: 90 -> 25 + 17 us)
+                y = self.conv(op, outs[src], relu=act)
+                return self.upsample_add(y, [outs[skip]], [0], relu=False)
+            return self.conv(op, outs[src], res=outs[skip] if skip is not None else None, relu=act, res_after_act=skip is not None)
+        if kind == 'add':
+            return self.upsample_add(outs[step[2]], [outs[step[3]]], [0], relu=False)
+        if kind == 'upcat':
+            return self.upsample_concat(outs[step[2]], outs[step[3]])
+        return outs[step[2]]                                # alias, head
+
+    def unfused(self, step, x):
+        """Whether conv step `step` on input x runs its shortcut as a separate k_upsample_add (see run_step)."""
+        op, skip = step[2], step[5]
+        return skip is not None and self.unfuse_wide and op.kh == 3 and op.stride == 1 and x.shape[3] + 2 > 138
 
 
 class YOLOv3(object):

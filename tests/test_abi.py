@@ -47,6 +47,25 @@ def test_frame_plan_query_is_bound_and_rejects_a_null_handle():
     assert [x.value for x in v] == [-7, -7, -7]
 
 
+def test_conv_form_query_is_bound_and_documented():
+    """pam_conv_last_form (which instantiation the thread's last pam_conv2d_nhwc_bf16[_ex] call launched) is declared next to
+    pam_conv_last_kernel, bound without arguments, documented per kernel family in pam.h, and answers 0 on a thread that launched
+    no convolution -- like the kernel query, without touching a device."""
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    assert _lib._SIGS['pam_conv_last_form'] == (ctypes.c_int, [])
+    hdr = open(os.path.join(ROOT, 'include', 'pam.h')).read()
+    doc = hdr[hdr.index('int pam_conv_last_kernel(void);'):hdr.index('int pam_conv_last_form(void);')]
+    for fam in ('IGEMM', '3X3 ', '3X3S', 'GS', 'STEM'):
+        assert 'PAM_CONV_KERNEL_' + fam in doc, fam
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in ('pam_conv_last_form', 'pam_conv_last_kernel'):
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = ctypes.c_int, []
+        assert fn() == 0, name
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(_lib, '_lib', None)
     monkeypatch.setattr(_lib, 'LIB_PATH', '/nonexistent/libpam_hip.so')
