@@ -28,9 +28,8 @@
 // Same K order per output element as k_bblock / k_conv3x3<48>: results are bit-identical to theirs.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <utility>
 #include "../../include/pam.h"
-#include "pam_launch.hpp"
+#include "pam_kernel.hpp"
 
 // Diagnostic build only (tools/stamp_block2.py compiles this file with -DPAM_DIAG): per-wave s_memtime stamps into a buffer of their
 // own that no kernel reads; the shipped library contains no stamp code.
@@ -43,15 +42,6 @@ extern "C" int pam_block2_debug_stamps(void* dev_buf) { g_bb2_stamps = (unsigned
 #endif
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(2))) short s16x2;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
 
 constexpr int PA = 96;                     // bytes per activation slot (48 bf16)
 constexpr int NST = 14;                    // k-steps per convolution (432 = 13.5 x 32, zero weights in the tail)
@@ -72,23 +62,6 @@ struct BB2Args {
 };
 
 __device__ __attribute__((aligned(64))) const uint32_t g_bb2_zero[16] = {0};
-
-__device__ __forceinline__ int fdiv_small(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }   // exact for x < 2^16
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {     // one v_cvt_pk_bf16_f32 (RNE).  The element-wise cast form compiles to two
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;           // converts + a permute; an asm statement is one instruction too but the compiler
-    typedef __attribute__((ext_vector_type(2))) float f32x2;               // does not pad it against the MFMA that wrote lo / hi (csrc/pam_stem.hip met that)
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){lo, hi}, bf16x2_t));
-}
-__device__ __forceinline__ uint32_t relu_bf16x2(uint32_t v) {           // bf16 is sign-magnitude: max(int16, 0) clears the negatives
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), (s16x2){0, 0}));
-}
-
-// issue order of one k-step: the next step's NR fragment reads alternate with the first NR of this step's NM MFMAs
-template <int NM, int NR, int... R>
-__device__ __forceinline__ void spread(std::integer_sequence<int, R...>) {
-    (((void)R, __builtin_amdgcn_sched_group_barrier(0x008, 1, 0), __builtin_amdgcn_sched_group_barrier(0x100, 1, 0)), ...);
-    __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
-}
 
 // One convolution of a wave: MT M tiles x 3 N tiles, K walked once, fragments of k-step st + 1 read under the MFMAs of k-step st.
 // wl: this lane's row of k-step 0 in the weight image; xl: this lane's slot of the wave's first M tile; koff[st]: byte offset of the
@@ -117,7 +90,7 @@ __device__ __forceinline__ void conv_pass(f32x4 (&acc)[MW1][3], const char* wl, 
 #pragma unroll
             for (int j = 0; j < 3; ++j)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[cur][j]), __builtin_bit_cast(bf16x8_t, bf[cur][i]), acc[i][j], 0, 0, 0);
-        spread<3 * MT, MT + 3>(std::make_integer_sequence<int, MT + 3>{});
+        spread<3 * MT, MT + 3>();
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -128,8 +101,7 @@ __global__ __launch_bounds__(512) void k_bblock2_48(BB2Args a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // XCD-aware item order: workgroups b, b + 8, ... share an XCD and its L2 -> give each XCD a contiguous run of tiles (neighbouring
     // tiles re-read each other's halo)
-    int bx;
-    { const int v = blockIdx.x, q = a.nitems >> 3, r = a.nitems & 7, xcd = v & 7, loc = v >> 3; bx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc; }
+    const int bx = xcd_order(blockIdx.x, a.nitems);
     const int per_img = a.tiles_y * a.tiles_x;
     const int n = bx / per_img, trem = bx - n * per_img, tyi = trem / a.tiles_x, txi = trem - tyi * a.tiles_x;
     const int ty0 = tyi * a.TR, tx0 = txi * a.TC;
@@ -301,8 +273,8 @@ __global__ __launch_bounds__(512) void k_bblock2_48(BB2Args a) {
         uint32_t ov[6];
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-            const float r0 = __builtin_bit_cast(float, rr[2 * j] << 16), r1 = __builtin_bit_cast(float, rr[2 * j] & 0xffff0000u);
-            const float r2f = __builtin_bit_cast(float, rr[2 * j + 1] << 16), r3 = __builtin_bit_cast(float, rr[2 * j + 1] & 0xffff0000u);
+            const float r0 = bf16_lo(rr[2 * j]), r1 = bf16_hi(rr[2 * j]);
+            const float r2f = bf16_lo(rr[2 * j + 1]), r3 = bf16_hi(rr[2 * j + 1]);
             ov[2 * j] = relu_bf16x2(pack_bf16x2(acc[i][j][0] + r0, acc[i][j][1] + r1));
             ov[2 * j + 1] = relu_bf16x2(pack_bf16x2(acc[i][j][2] + r2f, acc[i][j][3] + r3));
         }
@@ -361,8 +333,7 @@ __global__ __launch_bounds__(64 * B96_NW) void k_bblock2_96(BB96Args a) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, l15 = lane & 15;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bx;
-    { const int v = blockIdx.x, q = a.nitems >> 3, r = a.nitems & 7, xcd = v & 7, loc = v >> 3; bx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc; }
+    const int bx = xcd_order(blockIdx.x, a.nitems);
     const int per_img = a.tiles_y * a.tiles_x;
     const int n = bx / per_img, trem = bx - n * per_img, tyi = trem / a.tiles_x, txi = trem - tyi * a.tiles_x;
     const int ty0 = tyi * a.TR, tx0 = txi * a.TC;
@@ -533,10 +504,10 @@ __global__ __launch_bounds__(64 * B96_NW) void k_bblock2_96(BB96Args a) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const f32x4 b4 = *(const f32x4*)(bias + 96 + ch + 4 * h);
-                acc[i][2 * m + h][0] = b4[0] + __builtin_bit_cast(float, v[2 * h] << 16);
-                acc[i][2 * m + h][1] = b4[1] + __builtin_bit_cast(float, v[2 * h] & 0xffff0000u);
-                acc[i][2 * m + h][2] = b4[2] + __builtin_bit_cast(float, v[2 * h + 1] << 16);
-                acc[i][2 * m + h][3] = b4[3] + __builtin_bit_cast(float, v[2 * h + 1] & 0xffff0000u);
+                acc[i][2 * m + h][0] = b4[0] + bf16_lo(v[2 * h]);
+                acc[i][2 * m + h][1] = b4[1] + bf16_hi(v[2 * h]);
+                acc[i][2 * m + h][2] = b4[2] + bf16_lo(v[2 * h + 1]);
+                acc[i][2 * m + h][3] = b4[3] + bf16_hi(v[2 * h + 1]);
             }
         }
     }

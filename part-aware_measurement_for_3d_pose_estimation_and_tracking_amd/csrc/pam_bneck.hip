@@ -21,18 +21,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pam.h"
-#include "pam_launch.hpp"
+#include "pam_kernel.hpp"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) short s16x2;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
-#define OOB_OFFSET 0x80000000u
 
 constexpr int TR = 16, TC = 8;                         // tile
 constexpr int RP = TC + 2, NPOS = (TR + 2) * RP;       // y1 positions under it: 18 x 10
@@ -47,17 +38,6 @@ struct BnArgs {
     const char* w1img; const float* b1; uint16_t* outx; uint16_t* outy;
     int N, H, W, tiles_y, tiles_x, ntiles;
 };
-
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {      // one v_cvt_pk_bf16_f32 (RNE), visible to the compiler's hazard padding
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){lo, hi}, bf16x2_t));
-}
-__device__ __forceinline__ uint32_t relu_bf16x2(uint32_t v) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), (s16x2){0, 0}));
-}
-__device__ __forceinline__ float lo_f(uint32_t d) { return __builtin_bit_cast(float, d << 16); }
-__device__ __forceinline__ float hi_f(uint32_t d) { return __builtin_bit_cast(float, d & 0xffff0000u); }
 
 // HAS2: the next block's conv1 is computed; DOWN: the FIRST block -- no residual, instead the 1x1 downsample convolution over the block input x0 as a
 // second K range of the first product (w3img's second chunk; its 32 fragments live in registers: 32 KB
@@ -231,8 +211,8 @@ __global__ __launch_bounds__(512, 1) void k_bneck(BnArgs a) {
                     o[2 * j + 1] = relu_bf16x2(pack_bf16x2(acc3[j][2], acc3[j][3]));
                 } else {
                     const uint32_t d0 = rc[j >> 1][(2 * j) & 3], d1 = rc[j >> 1][(2 * j + 1) & 3];
-                    o[2 * j] = relu_bf16x2(pack_bf16x2(acc3[j][0] + lo_f(d0), acc3[j][1] + hi_f(d0)));
-                    o[2 * j + 1] = relu_bf16x2(pack_bf16x2(acc3[j][2] + lo_f(d1), acc3[j][3] + hi_f(d1)));
+                    o[2 * j] = relu_bf16x2(pack_bf16x2(acc3[j][0] + bf16_lo(d0), acc3[j][1] + bf16_hi(d0)));
+                    o[2 * j + 1] = relu_bf16x2(pack_bf16x2(acc3[j][2] + bf16_lo(d1), acc3[j][3] + bf16_hi(d1)));
                 }
             }
             const u32x4 xf[2] = {(u32x4){o[0], o[1], o[2], o[3]}, (u32x4){o[4], o[5], o[6], o[7]}};

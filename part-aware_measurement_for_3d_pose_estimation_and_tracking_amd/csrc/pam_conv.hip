@@ -12,11 +12,7 @@
 #include <type_traits>
 #include <utility>
 #include "../../include/pam.h"
-#include "pam_launch.hpp"
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;     // 8 bf16 = one MFMA A/B fragment (4 VGPRs)
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+#include "pam_kernel.hpp"
 
 // fused epilogue activation.  act & 3: 0 linear, 1 ReLU, 2 leaky ReLU (slope 0.1); act & 4: the residual is added AFTER the
 // activation (Darknet shortcut layers) instead of before it (ResNet / HRNet blocks)
@@ -41,11 +37,8 @@ struct ConvArgs {
     int relu_from;    // the activation applies to output channels >= relu_from (0 = all); multiple of 16
 };
 
-__device__ __forceinline__ float bf16_to_f32(uint16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
-__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {     // plain cast: hipcc emits v_cvt_pk_bf16_f32 (RNE) on gfx950
-    return __builtin_bit_cast(uint16_t, (__bf16)f);
-}
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {     // two floats -> one dword of two bf16 (one instruction)
+// the element-wise pack (two converts + a permute); the shared pack_bf16x2 changes these kernels' code and is left to a measured change
+__device__ __forceinline__ uint32_t pack_bf16x2_ew(float lo, float hi) {
     typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
     bf16x2_t v = {(__bf16)lo, (__bf16)hi};
     return __builtin_bit_cast(uint32_t, v);
@@ -53,10 +46,6 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {     // two
 
 constexpr int KC = 64;               // K elements staged per LDS chunk (two 32-deep MFMA steps)
 constexpr int ROWB = KC * 2 + 16;    // LDS row pitch in bytes: 128 B of data + 16 B pad (spreads ds_read_b128 over banks)
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-#define OOB_OFFSET 0x80000000u          // beyond any buffer's num_records: the hardware bounds check returns zeros
 
 // One lane's row piece of 4*NTW contiguous bf16 channels (8*NTW bytes at byte offset o, 8-byte aligned; 16-byte aligned
 // when NTW is even or the lane group g is even) as 16-byte accesses where possible.  NTW = 3 (24 bytes) splits 16 + 8 for
@@ -83,23 +72,6 @@ __device__ __forceinline__ void c3_row_load(__amdgpu_buffer_rsrc_t rs, unsigned 
         const u32x2 h = __builtin_amdgcn_raw_buffer_load_b64(rs, o + (odd ? 0u : 16u), 0, 0);
         d[0] = odd ? h[0] : q[0]; d[1] = odd ? h[1] : q[1]; d[2] = odd ? q[0] : q[2];
         d[3] = odd ? q[1] : q[3]; d[4] = odd ? q[2] : h[0]; d[5] = odd ? q[3] : h[1];
-    }
-}
-template <int NTW>
-__device__ __forceinline__ void c3_row_store(uint16_t* p, int g, const uint32_t* d) {
-    if constexpr (NTW == 1) {
-        *(u32x2*)p = (u32x2){d[0], d[1]};
-    } else if constexpr (NTW == 2) {
-        *(u32x4*)p = (u32x4){d[0], d[1], d[2], d[3]};
-    } else if constexpr (NTW == 4) {
-        *(u32x4*)p = (u32x4){d[0], d[1], d[2], d[3]}; *(u32x4*)(p + 8) = (u32x4){d[4], d[5], d[6], d[7]};
-    } else if constexpr (NTW == 6) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) *(u32x4*)(p + 8 * k) = (u32x4){d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]};
-    } else {
-        const bool odd = g & 1;
-        *(u32x4*)(p + (odd ? 4 : 0)) = odd ? (u32x4){d[2], d[3], d[4], d[5]} : (u32x4){d[0], d[1], d[2], d[3]};
-        *(u32x2*)(p + (odd ? 0 : 8)) = odd ? (u32x2){d[0], d[1]} : (u32x2){d[4], d[5]};
     }
 }
 
@@ -251,7 +223,6 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
     // epilogue straight from the accumulators: with the weights as the A operand the D tile has channels on its rows, so this
     // lane holds channels cw0 + 4*NTW*g + 4*j + r of pixel mw0 + i*16 + (lane & 15): 4*NTW contiguous channels, 16-byte accesses
     const int mw0 = m0 + wm * 64;
-    typedef __attribute__((ext_vector_type(2))) short s16x2;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int m = mw0 + i * 16 + (lane & 15);
@@ -270,18 +241,18 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
                 if constexpr (GEN) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = epi_act(v[r], rr[r], act_on ? a.relu : (a.relu & 4));
-                    ov[2 * j] = pack_bf16x2(v[0], v[1]); ov[2 * j + 1] = pack_bf16x2(v[2], v[3]);
+                    ov[2 * j] = pack_bf16x2_ew(v[0], v[1]); ov[2 * j + 1] = pack_bf16x2_ew(v[2], v[3]);
                 } else {                                // HRNet's codes 0 / 1; ReLU as a packed int16 max on the bf16 pairs
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] += rr[r];
-                    ov[2 * j] = pack_bf16x2(v[0], v[1]); ov[2 * j + 1] = pack_bf16x2(v[2], v[3]);
+                    ov[2 * j] = pack_bf16x2_ew(v[0], v[1]); ov[2 * j + 1] = pack_bf16x2_ew(v[2], v[3]);
                     if (a.relu && act_on) {
                         ov[2 * j] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, ov[2 * j]), (s16x2){0, 0}));
                         ov[2 * j + 1] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, ov[2 * j + 1]), (s16x2){0, 0}));
                     }
                 }
             }
-            c3_row_store<NTW>(a.out + o, g, ov);
+            row_store<NTW>(a.out + o, g, ov);
         }
     }
 }
@@ -375,8 +346,6 @@ __host__ __device__ constexpr int c3_ck(int cin) { return cin == 48 ? 48 : (cin 
 __host__ __device__ constexpr int c3_pitch_a(int cin) { return c3_ck(cin) == 64 ? 160 : 96; }
 __host__ __device__ constexpr int c3_pitch_w(int cin) { return cin == 48 ? 864 : (c3_ck(cin) == 64 ? 1184 : 608); }
 
-__device__ __forceinline__ int fdiv_small(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }   // exact for x < 2^16
-
 // the deep small-image layers run one workgroup per CU (one wave per SIMD): give those instantiations the whole register
 // file, otherwise the scheduler, starved by the chunk-prefetch registers, reads each MFMA fragment right before its use
 template <int CIN, int NTW, int MT, int NWAVES, int PMAX>
@@ -396,10 +365,7 @@ __global__ __launch_bounds__(64 * NWAVES, (c3_ck(CIN) == 64 ? 1 : 2)) void k_con
     // v = blockIdx.x, + gridDim.x, ... with the slab's weights staged once and the next tile's patch in flight (registers)
     // under the current tile's epilogue.  gridDim.x is a multiple of 8 then, so a workgroup stays on its XCD's run.
     const int ntiles = a.tiles_y * a.N;
-    auto tile_of = [&](int v) {
-        const int q = ntiles >> 3, r = ntiles & 7, xcd = v & 7, loc = v >> 3;
-        return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    };
+    auto tile_of = [&](int v) { return xcd_order(v, ntiles); };
     int vtile = blockIdx.x;
     int bx = tile_of(vtile);
     int n = bx / a.tiles_y, ty0 = (bx - n * a.tiles_y) * a.TH;
@@ -580,7 +546,6 @@ __global__ __launch_bounds__(64 * NWAVES, (c3_ck(CIN) == 64 ? 1 : 2)) void k_con
     // (bf16 is sign-magnitude: max(int16, 0) clears exactly the negative values) -- the tail is VALU-issue bound.
     auto epilogue = [&](auto RESC, auto RELUC, auto GENC) {
         constexpr bool RES = decltype(RESC)::value, RELU = decltype(RELUC)::value, GEN = decltype(GENC)::value;
-        typedef __attribute__((ext_vector_type(2))) short s16x2;
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const int p = wave * 16 * MT + i * 16 + (lane & 15);
@@ -598,20 +563,20 @@ __global__ __launch_bounds__(64 * NWAVES, (c3_ck(CIN) == 64 ? 1 : 2)) void k_con
                     if constexpr (GEN) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = epi_act(v[r], rr[r], a.relu);
-                        ov[2 * j] = pack_bf16x2(v[0], v[1]); ov[2 * j + 1] = pack_bf16x2(v[2], v[3]);
+                        ov[2 * j] = pack_bf16x2_ew(v[0], v[1]); ov[2 * j + 1] = pack_bf16x2_ew(v[2], v[3]);
                     } else {
                         if constexpr (RES) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r) v[r] += rr[r];
                         }
-                        ov[2 * j] = pack_bf16x2(v[0], v[1]); ov[2 * j + 1] = pack_bf16x2(v[2], v[3]);
+                        ov[2 * j] = pack_bf16x2_ew(v[0], v[1]); ov[2 * j + 1] = pack_bf16x2_ew(v[2], v[3]);
                         if constexpr (RELU) {
                             ov[2 * j] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, ov[2 * j]), (s16x2){0, 0}));
                             ov[2 * j + 1] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, ov[2 * j + 1]), (s16x2){0, 0}));
                         }
                     }
                 }
-                c3_row_store<NTW>(a.out + (((size_t)n * a.H + ty0 + py) * a.W + px) * a.Cout + n0 + g * 4 * NTW, g, ov);
+                row_store<NTW>(a.out + (((size_t)n * a.H + ty0 + py) * a.W + px) * a.Cout + n0 + g * 4 * NTW, g, ov);
             }
         }
     };
@@ -721,17 +686,7 @@ extern "C" int pam_conv3x3_slab(int H, int W, int Cin, int Cout) {
 //   this layout (pam_conv3x3_layout() == 1).  The residual is added to the bias before the K loop (its loads run beside the first
 //   chunk's DMA), so the epilogue is convert + ReLU + store.
 // ====================================================================================================================
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
 __device__ __attribute__((aligned(64))) const uint32_t g_c3_zero[16 + 16 * 16] = {0};   // 64 B + the largest chunk offset (Cin = 512)
-
-// scheduling pattern of one k-step: the next step's NR LDS reads alternate with the first NR of this step's NM MFMAs, the other MFMAs
-// follow (slack for the last read's latency); the builtin takes literal counts
-template <int NM, int NR, int... R>
-__device__ __forceinline__ void c3s_spread(std::integer_sequence<int, R...>) {
-    (((void)R, __builtin_amdgcn_sched_group_barrier(0x008, 1, 0), __builtin_amdgcn_sched_group_barrier(0x100, 1, 0)), ...);
-    __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
-}
 
 template <int CIN, int NTW, int MT, int PMAX, int NBUF, bool GEN = false>
 __global__ __launch_bounds__(512, 1) void k_conv3x3s(C3Args a) {
@@ -743,10 +698,7 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3s(C3Args a) {
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ntiles = a.tiles_y * a.N;
-    const int bx = [&] {                                // XCD-aware tile order (see k_conv3x3)
-        const int v = blockIdx.x, q = ntiles >> 3, r = ntiles & 7, xcd = v & 7, loc = v >> 3;
-        return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }();
+    const int bx = xcd_order(blockIdx.x, ntiles);       // XCD-aware tile order (see k_conv3x3)
     const int n = bx / a.tiles_y, ty0 = (bx - n * a.tiles_y) * a.TH;
     const int PW = a.W + 2, npatch = (a.TH + 2) * PW;
     const int nslots = min(a.TH, a.H - ty0) * PW;
@@ -783,9 +735,7 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3s(C3Args a) {
             if (c < NCHUNK) issue(c);
         for (int k = 0; k < NCHUNK; ++k) {
             const int fly = min(NCHUNK - 1 - k, NBUF - 2);                               // younger chunks that may stay in flight
-            if (fly <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (fly == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPER) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NPER) : "memory");
+            dma_ring_wait<NPER, NBUF>(fly);
             asm volatile("s_barrier" ::: "memory");
             if (k + NBUF - 1 < NCHUNK) issue(k + NBUF - 1);
         }
@@ -884,7 +834,7 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3s(C3Args a) {
                                                                        __builtin_bit_cast(bf16x8_t, af[cur][i]), acc[i][j], 0, 0, 0);
             // issue order inside the step: the next step's MT + NTW fragment reads spread between this step's MFMAs (a burst of reads
             // ahead of the MFMAs holds the wave's issue slot ~100 cycles per step with the matrix pipe idle)
-            if constexpr (MT * NTW >= MT + NTW) c3s_spread<MT * NTW, MT + NTW>(std::make_integer_sequence<int, MT + NTW>{});   // (16-channel slabs: more reads than MFMAs, the compiler's order)
+            if constexpr (MT * NTW >= MT + NTW) spread<MT * NTW, MT + NTW>();   // (16-channel slabs: more reads than MFMAs, the compiler's order)
             __builtin_amdgcn_sched_barrier(0);
         }
         C3_STAMP(4 + 3 * (k & 15));
@@ -898,7 +848,6 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3s(C3Args a) {
     C3_STAMP(60);
 
     // ---- epilogue straight from the accumulators (row permutation of the slab as in k_conv3x3: 4*NTW contiguous channels per lane)
-    typedef __attribute__((ext_vector_type(2))) short s16x2;
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
         const int p = wave * 16 * MT + i * 16 + (lane & 15);
@@ -914,13 +863,13 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3s(C3Args a) {
                     acc[i][j][2] = epi_act(acc[i][j][2], __builtin_bit_cast(float, r23 << 16), a.relu);
                     acc[i][j][3] = epi_act(acc[i][j][3], __builtin_bit_cast(float, r23 & 0xffff0000u), a.relu);
                 }
-                ov[2 * j] = pack_bf16x2(acc[i][j][0], acc[i][j][1]); ov[2 * j + 1] = pack_bf16x2(acc[i][j][2], acc[i][j][3]);
+                ov[2 * j] = pack_bf16x2_ew(acc[i][j][0], acc[i][j][1]); ov[2 * j + 1] = pack_bf16x2_ew(acc[i][j][2], acc[i][j][3]);
                 if (!GEN && a.relu) {
                     ov[2 * j] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, ov[2 * j]), (s16x2){0, 0}));
                     ov[2 * j + 1] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, ov[2 * j + 1]), (s16x2){0, 0}));
                 }
             }
-            c3_row_store<NTW>(a.out + (((size_t)n * a.H + ty0 + py) * a.W + px) * a.Cout + n0 + g * 4 * NTW, g, ov);
+            row_store<NTW>(a.out + (((size_t)n * a.H + ty0 + py) * a.W + px) * a.Cout + n0 + g * 4 * NTW, g, ov);
         }
     }
     C3_STAMP(61);
@@ -1100,10 +1049,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_gs(ConvArgs a) {
     // XCD-aware order: workgroups b, b + 8, ... share an XCD and its L2 (gridDim.x is a multiple of 8 whenever a workgroup walks more
     // than one tile), so every XCD gets a contiguous run of the (block, slab) list: the slabs of one pixel block then gather the same
     // input pixels through ONE L2 instead of pulling them over the fabric once per XCD
-    auto tile_of = [&](int t) {
-        const int v = (int)blockIdx.x + t * (int)gridDim.x, qn = ntile >> 3, rn = ntile & 7, xcd = v & 7, loc = v >> 3;
-        return (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + loc;
-    };
+    auto tile_of = [&](int t) { return xcd_order((int)blockIdx.x + t * (int)gridDim.x, ntile); };
 
     if (wave >= 4) {
         // ---- loader waves ---------------------------------------------------------------------------------------------------
@@ -1171,6 +1117,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_gs(ConvArgs a) {
         for (int c = 0; c < NBUF - 1; ++c)
             if (issued < total) issue_next();
         for (int k = 0; k < total; ++k) {
+            // (dma_ring_wait's ladder, written out: as a call it changes the register allocation of the BM = 256 instantiations)
             const int fly = min(total - 1 - k, NBUF - 2);                                // younger chunks that may stay in flight
             if (fly <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             else if (fly == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPER) : "memory");
@@ -1216,7 +1163,6 @@ __global__ __launch_bounds__(512, 1) void k_conv_gs(ConvArgs a) {
             for (int j = 0; j < NTW; ++j)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, bf_[j]), __builtin_bit_cast(bf16x8_t, af_[i]), acc[i][j], 0, 0, 0);
     };
-    typedef __attribute__((ext_vector_type(2))) short s16x2;
     asm volatile("s_barrier" ::: "memory");                                              // my first chunk has landed (and is visible)
     int G = 0;
     for (int t = 0; t < mine; ++t) {
@@ -1242,7 +1188,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_gs(ConvArgs a) {
         for (int c = 0; c < nchunks; ++c, ++G) {
             ldfrag(G, 1, af[1], bfr[1]);
             mfmas(af[0], bfr[0]);
-            c3s_spread<MTW * NTW, MTW + NTW>(std::make_integer_sequence<int, MTW + NTW>{});
+            spread<MTW * NTW, MTW + NTW>();
             __builtin_amdgcn_sched_barrier(0);
             if (G + 1 < total) {
                 __builtin_amdgcn_s_waitcnt(0xC07F);                                       // lgkmcnt(0): this wave is done reading chunk G
@@ -1265,13 +1211,13 @@ __global__ __launch_bounds__(512, 1) void k_conv_gs(ConvArgs a) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) acc[i][j][r] = acc[i][j][r] > 0.0f ? acc[i][j][r] : 0.1f * acc[i][j][r];
                     }
-                    ov[2 * j] = pack_bf16x2(acc[i][j][0], acc[i][j][1]); ov[2 * j + 1] = pack_bf16x2(acc[i][j][2], acc[i][j][3]);
+                    ov[2 * j] = pack_bf16x2_ew(acc[i][j][0], acc[i][j][1]); ov[2 * j + 1] = pack_bf16x2_ew(acc[i][j][2], acc[i][j][3]);
                     if (a.relu == 1 && n0 + g * 4 * NTW + j * 4 >= a.relu_from) {
                         ov[2 * j] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, ov[2 * j]), (s16x2){0, 0}));
                         ov[2 * j + 1] = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, ov[2 * j + 1]), (s16x2){0, 0}));
                     }
                 }
-                c3_row_store<NTW>(a.out + (size_t)m * a.Cout + n0 + g * 4 * NTW, g, ov);
+                row_store<NTW>(a.out + (size_t)m * a.Cout + n0 + g * 4 * NTW, g, ov);
             }
         }
     }
@@ -1367,9 +1313,9 @@ __global__ __launch_bounds__(256) void k_conv_stem(StemArgs a) {
                 float v[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = epi_act1(acc[j][r], a.relu & 3);
-                d[2 * j] = pack_bf16x2(v[0], v[1]); d[2 * j + 1] = pack_bf16x2(v[2], v[3]);
+                d[2 * j] = pack_bf16x2_ew(v[0], v[1]); d[2 * j + 1] = pack_bf16x2_ew(v[2], v[3]);
             }
-            c3_row_store<NT>(orow + (size_t)ox * (16 * NT), g, d);
+            row_store<NT>(orow + (size_t)ox * (16 * NT), g, d);
         }
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) cur[ky] = nxt[ky];
@@ -1388,6 +1334,17 @@ extern "C" int pam_conv2d_nhwc_bf16(void* stream, const void* in, const void* w_
 // profiling labels (bench.py's per-family roofline) and the tests' record of the tile choice: see g_last_conv_kernel
 extern "C" int pam_conv_last_kernel(void) { return g_last_conv_kernel; }
 extern "C" int pam_conv_last_form(void) { return g_last_conv_form; }
+// the arguments of a k_conv3x3 / k_conv3x3s launch with TH output rows per tile (the diagnostic fields off)
+static C3Args c3_args(const void* in, const void* w_img, const float* bias, const void* res, void* out, int N, int H, int W, int Cout,
+                      int relu, int TH) {
+    C3Args c;
+    c.in = (const uint16_t*)in; c.wimg = (const uint16_t*)w_img; c.bias = bias; c.res = (const uint16_t*)res; c.out = (uint16_t*)out;
+    c.N = N; c.H = H; c.W = W; c.Cout = Cout; c.TH = TH; c.tiles_y = (H + TH - 1) / TH; c.relu = relu; c.inv_pw = 1.0f / (float)(W + 2);
+#ifdef PAM_DIAG
+    c.dbg = 0; c.stamps = nullptr;
+#endif
+    return c;
+}
 extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void* w_packed, const void* w_img, const float* bias,
                                        const void* residual, void* out, int N, int H, int W, int Cin, int Cout,
                                        int KH, int KW, int stride, int pad, int relu, int tile_cfg, int in_cstride, int relu_from) {
@@ -1399,33 +1356,19 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
     // -5: streamed, and a 96 -> 96 layer's image is packed for slabs of 48 output channels
     // -7: a Darknet layer (activation code > 1 allowed) on the streamed kernel, image packed for 64-channel slabs (pam_conv3x3_layout_gen)
     if (tile_cfg == -7) {
-        C3Args c;
-        int mt = 0, pmax = 0;
+        int th = 0, mt = 0, pmax = 0;
         if (!in || !w_packed || !w_img || !out || N <= 0 || KH != 3 || KW != 3 || stride != 1 || pad != 1 || in_cstride != Cin || relu_from != 0 ||
-            !c3s_pick_gen(H, W, Cin, Cout, c.TH, mt, pmax) || (size_t)N * H * W * Cout * 2 >= (1ull << 31)) return PAM_E_ARG;
-        c.in = (const uint16_t*)in; c.wimg = (const uint16_t*)w_img; c.bias = bias; c.res = (const uint16_t*)residual; c.out = (uint16_t*)out;
-        c.N = N; c.H = H; c.W = W; c.Cout = Cout; c.relu = relu; c.inv_pw = 1.0f / (float)(W + 2);
-        c.tiles_y = (H + c.TH - 1) / c.TH;
-#ifdef PAM_DIAG
-        c.dbg = 0; c.stamps = nullptr;
-#endif
-        return launch_c3s_gen((hipStream_t)stream, c, Cin, mt);
+            !c3s_pick_gen(H, W, Cin, Cout, th, mt, pmax) || (size_t)N * H * W * Cout * 2 >= (1ull << 31)) return PAM_E_ARG;
+        return launch_c3s_gen((hipStream_t)stream, c3_args(in, w_img, bias, residual, out, N, H, W, Cout, relu, th), Cin, mt);
     }
     // -8: a 192- / 384-channel ReLU / linear layer on the streamed kernel with 32-channel slabs (pam_conv3x3_layout_small; same arithmetic;
     // 16-channel slabs were measured too: no faster at 2-6 crops, slower from 9)
     if (tile_cfg == -8) {
-        C3Args c;
-        int mt = 0, pmax = 0, ntw = 0;
+        int th = 0, mt = 0, pmax = 0, ntw = 0;
         if (!in || !w_img || !out || N <= 0 || KH != 3 || KW != 3 || stride != 1 || pad != 1 || in_cstride != Cin || relu_from != 0 || relu > 1 ||
-            !pam_conv3x3_layout_small(H, W, Cin, Cout) || !c3s_pick(H, W, Cin, Cout, c.TH, mt, pmax, ntw, 0) || (size_t)N * H * W * Cout * 2 >= (1ull << 31))
+            !pam_conv3x3_layout_small(H, W, Cin, Cout) || !c3s_pick(H, W, Cin, Cout, th, mt, pmax, ntw, 0) || (size_t)N * H * W * Cout * 2 >= (1ull << 31))
             return PAM_E_ARG;
-        c.in = (const uint16_t*)in; c.wimg = (const uint16_t*)w_img; c.bias = bias; c.res = (const uint16_t*)residual; c.out = (uint16_t*)out;
-        c.N = N; c.H = H; c.W = W; c.Cout = Cout; c.relu = relu; c.inv_pw = 1.0f / (float)(W + 2);
-        c.tiles_y = (H + c.TH - 1) / c.TH;
-#ifdef PAM_DIAG
-        c.dbg = 0; c.stamps = nullptr;
-#endif
-        return launch_c3s((hipStream_t)stream, c, Cin, 2, mt, pmax);
+        return launch_c3s((hipStream_t)stream, c3_args(in, w_img, bias, residual, out, N, H, W, Cout, relu, th), Cin, 2, mt, pmax);
     }
     const int c96_slab = tile_cfg == -5 ? 48 : 0;
     const bool force_streamed = tile_cfg == -3 || c96_slab != 0, no_streamed = tile_cfg == -4;
@@ -1461,15 +1404,12 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
     if (w_img && KH == 3 && KW == 3 && stride == 1 && pad == 1 && tile_cfg == -1 && !no_streamed) {
         // streamed kernel (specialised loader / multiplier waves): w_img then has the layout pam_conv3x3_layout() > 0 announces.
         // Any other tile_cfg (-2 = classic kernel, >= 100 = tuning hooks) takes the classic kernel and the classic images.
-        C3Args c;
-        int mt = 0, pmax = 0, ntw = 0;
-        const bool picked = c3s_pick(H, W, Cin, Cout, c.TH, mt, pmax, ntw, c96_slab);
+        int th = 0, mt = 0, pmax = 0, ntw = 0;
+        const bool picked = c3s_pick(H, W, Cin, Cout, th, mt, pmax, ntw, c96_slab);
         if (force_streamed && !picked) return PAM_E_ARG;
         if (picked) {
             if (relu > 1) return PAM_E_ARG;
-            c.in = a.in; c.wimg = (const uint16_t*)w_img; c.bias = bias; c.res = a.res; c.out = a.out;
-            c.N = N; c.H = H; c.W = W; c.Cout = Cout; c.relu = relu; c.inv_pw = 1.0f / (float)(W + 2);
-            c.tiles_y = (H + c.TH - 1) / c.TH;
+            C3Args c = c3_args(in, w_img, bias, residual, out, N, H, W, Cout, relu, th);
 #ifdef PAM_DIAG
             c.dbg = g_c3_stamps ? 64 : 0; c.stamps = g_c3_stamps;
 #endif
@@ -1481,25 +1421,19 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
     if (w_img && KH == 3 && KW == 3 && stride == 1 && pad == 1 && (tile_cfg < 0 || tile_cfg >= 100) &&
         (Cin == 48 || Cin == 64 || Cin == 96 || Cin == 192 || Cin == 384 || Cin == 128 || Cin == 256 || Cin == 512)) {
         const int ntw = pam_conv3x3_slab(H, W, Cin, Cout) / 16;
-        C3Args c;
-        c.in = a.in; c.wimg = (const uint16_t*)w_img; c.bias = bias; c.res = a.res; c.out = a.out;
-        c.N = N; c.H = H; c.W = W; c.Cout = Cout; c.relu = relu; c.inv_pw = 1.0f / (float)(W + 2);
-        int cfg = 0;
-        pick_rows(N, H, W, Cout, ntw, c.TH, cfg);
+        int th = 0, cfg = 0;
+        pick_rows(N, H, W, Cout, ntw, th, cfg);
+        // tuning hook: 1000 + TH*100 + cfg (diagnostic build also: 100 + dbg bits)
+        if (tile_cfg >= 1000) { th = (tile_cfg - 1000) / 100; cfg = (tile_cfg - 1000) % 100; }
+        C3Args c = c3_args(in, w_img, bias, residual, out, N, H, W, Cout, relu, th);
 #ifdef PAM_DIAG
-        c.dbg = 0; c.stamps = g_c3_stamps;
+        c.stamps = g_c3_stamps;
+        if (tile_cfg >= 100 && tile_cfg < 1000) c.dbg = tile_cfg - 100;
 #endif
-        if (tile_cfg >= 100) {                           // tuning hook: 1000 + TH*100 + cfg (diagnostic build also: 100 + dbg bits)
-            if (tile_cfg >= 1000) { c.TH = (tile_cfg - 1000) / 100; cfg = (tile_cfg - 1000) % 100; }
-#ifdef PAM_DIAG
-            else c.dbg = tile_cfg - 100;
-#endif
-        }
         // a row wider than the block's output slots (W + 2 > 256: the detector's 64-channel layers from 512 x 512 inputs, e.g. 304 x 304
         // at 608) does not fit at all: the generic kernel below takes it, like any other tile that does not fit (only the tuning hooks refuse)
         const bool rows_fit = c.TH * (W + 2) <= 16 * (cfg / 10) * (cfg % 10);
         if (!rows_fit && tile_cfg >= 100) return PAM_E_ARG;
-        c.tiles_y = (H + c.TH - 1) / c.TH;
         hipStream_t s = (hipStream_t)stream;
         // rows too wide for the patch-in-LDS kernel (e.g. the detector's 208-wide layers): the generic kernel takes them
         const int npatch = (c.TH + 2) * (W + 2), pmax = (cfg == 44 || cfg == 54) ? 416 : (cfg == 43 ? 352 : 288);
@@ -1606,7 +1540,7 @@ __global__ __launch_bounds__(256) void k_upsample_add(UpArgs a) {
             }
         bf16x8 o;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (short)f32_to_bf16_rne(a.relu ? fmaxf(v[k], 0.0f) : v[k]);
+        for (int k = 0; k < 8; ++k) o[k] = (short)f32_to_bf16(a.relu ? fmaxf(v[k], 0.0f) : v[k]);
         *(bf16x8*)(a.out + (size_t)pix * a.C + c8 * 8) = o;
     }
 }

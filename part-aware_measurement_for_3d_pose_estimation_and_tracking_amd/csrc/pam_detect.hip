@@ -6,9 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pam.h"
-
-__device__ __forceinline__ uint16_t f32_to_bf16(float f) { return __builtin_bit_cast(uint16_t, (__bf16)f); }
-__device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
+#include "pam_kernel.hpp"
 
 // ---- whole-frame resize -------------------------------------------------------------------------------------------
 // One thread per output pixel: bilinear (half-pixel centres, border replicate = cv2.resize INTER_LINEAR) from the BGR

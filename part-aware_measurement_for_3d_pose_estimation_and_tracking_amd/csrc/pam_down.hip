@@ -23,20 +23,10 @@
 //   results are bit-identical to pam_conv2d_nhwc_bf16's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <utility>
 #include "../../include/pam.h"
-#include "pam_launch.hpp"
+#include "pam_kernel.hpp"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((ext_vector_type(2))) short s16x2;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
 
 constexpr int PA = 96;                     // bytes per input slot (48 bf16)
 constexpr int NST = 14;                    // k-steps of 32 (432 = 13.5 x 32, zero weights in the tail)
@@ -55,23 +45,6 @@ struct D48Args {
 };
 
 __device__ __attribute__((aligned(64))) const uint32_t g_d48_zero[16] = {0};
-
-__device__ __forceinline__ int fdiv_small(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }   // exact for x < 2^16
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {     // one v_cvt_pk_bf16_f32 (RNE) the compiler can see (hazard padding)
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){lo, hi}, bf16x2_t));
-}
-__device__ __forceinline__ uint32_t relu_bf16x2(uint32_t v) {           // bf16 is sign-magnitude: max(int16, 0) clears the negatives
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), (s16x2){0, 0}));
-}
-
-// issue order of one k-step: the next step's NR fragment reads alternate with the first NR of this step's NM MFMAs
-template <int NM, int NR, int... R>
-__device__ __forceinline__ void spread(std::integer_sequence<int, R...>) {
-    (((void)R, __builtin_amdgcn_sched_group_barrier(0x008, 1, 0), __builtin_amdgcn_sched_group_barrier(0x100, 1, 0)), ...);
-    if constexpr (NM > NR) __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
-}
 
 // One slab of a wave: MT M tiles x 3 N tiles, K walked once, fragments of k-step st + 1 read under the MFMAs of k-step st.
 // wl: this lane's row of k-step 0 in the slab's weight image; xl[i]: this lane's window corner of M tile i; koff[st]: byte offset of the
@@ -95,7 +68,7 @@ __device__ __forceinline__ void slab_pass(f32x4 (&acc)[MTMAX][3], const char* wl
 #pragma unroll
             for (int j = 0; j < 3; ++j)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[cur][j]), __builtin_bit_cast(bf16x8_t, bf[cur][i]), acc[i][j], 0, 0, 0);
-        if constexpr (MT >= 2) spread<3 * MT, MT + 3>(std::make_integer_sequence<int, MT + 3>{});
+        if constexpr (MT >= 2) spread<3 * MT, MT + 3>();
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -106,8 +79,7 @@ __global__ __launch_bounds__(512) void k_down48(D48Args a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // XCD-aware item order: workgroups b, b + 8, ... share an XCD and its L2 -> every XCD gets a contiguous run of tiles (neighbouring
     // tiles re-read each other's halo row / column)
-    int bx;
-    { const int v = blockIdx.x, q = a.nitems >> 3, r = a.nitems & 7, xcd = v & 7, loc = v >> 3; bx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc; }
+    const int bx = xcd_order(blockIdx.x, a.nitems);
     const int per_img = a.tiles_y * a.tiles_x;
     const int n = bx / per_img, trem = bx - n * per_img, tyi = trem / a.tiles_x, txi = trem - tyi * a.tiles_x;
     const int ty0 = tyi * a.TR, tx0 = txi * a.TC;                    // output tile origin
@@ -228,8 +200,8 @@ __global__ __launch_bounds__(512) void k_down48(D48Args a) {
                 float v0 = acc[i][j][0], v1 = acc[i][j][1], v2 = acc[i][j][2], v3 = acc[i][j][3];
                 if (a.res) {
                     const uint32_t r01 = j < 2 ? rq[i][2 * j] : rh[i][0], r23 = j < 2 ? rq[i][2 * j + 1] : rh[i][1];
-                    v0 += __builtin_bit_cast(float, r01 << 16); v1 += __builtin_bit_cast(float, r01 & 0xffff0000u);
-                    v2 += __builtin_bit_cast(float, r23 << 16); v3 += __builtin_bit_cast(float, r23 & 0xffff0000u);
+                    v0 += bf16_lo(r01); v1 += bf16_hi(r01);
+                    v2 += bf16_lo(r23); v3 += bf16_hi(r23);
                 }
                 ov[2 * j] = pack_bf16x2(v0, v1); ov[2 * j + 1] = pack_bf16x2(v2, v3);
                 if (j < 2 ? relu_lo : relu_hi) { ov[2 * j] = relu_bf16x2(ov[2 * j]); ov[2 * j + 1] = relu_bf16x2(ov[2 * j + 1]); }
@@ -301,18 +273,6 @@ struct DSArgs {
     float inv_pwp, inv_wo;
 };
 
-template <int NTW>
-__device__ __forceinline__ void ds_row_store(uint16_t* p, int g, const uint32_t* d) {
-    if constexpr (NTW == 4) {
-        *(u32x4*)p = (u32x4){d[0], d[1], d[2], d[3]}; *(u32x4*)(p + 8) = (u32x4){d[4], d[5], d[6], d[7]};
-    } else {
-        static_assert(NTW == 3, "slab width");            // 24 bytes: 16 + 8 for even g, 8 + 16 for odd g (the 16-byte half stays aligned)
-        const bool odd = g & 1;
-        *(u32x4*)(p + (odd ? 4 : 0)) = odd ? (u32x4){d[2], d[3], d[4], d[5]} : (u32x4){d[0], d[1], d[2], d[3]};
-        *(u32x2*)(p + (odd ? 0 : 8)) = odd ? (u32x2){d[0], d[1]} : (u32x2){d[4], d[5]};
-    }
-}
-
 template <int CIN, int NTW, int MT, int PMAX, int NBUF>
 __global__ __launch_bounds__(512, 1) void k_down_s(DSArgs a) {
     constexpr int BN = 16 * NTW, NCHUNK = CIN / 32;
@@ -323,10 +283,7 @@ __global__ __launch_bounds__(512, 1) void k_down_s(DSArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ntiles = a.tiles_y * a.N;
-    const int bx = [&] {                                // XCD-aware tile order: every XCD gets a contiguous run of tiles
-        const int v = blockIdx.x, q = ntiles >> 3, r = ntiles & 7, xcd = v & 7, loc = v >> 3;
-        return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    }();
+    const int bx = xcd_order(blockIdx.x, ntiles);
     const int n = bx / a.tiles_y, ty0 = (bx - n * a.tiles_y) * a.TH;                     // first OUTPUT row of the tile
     const int NEp = a.Wo + 1, PWp = 2 * a.Wo + 2, npatch = (2 * a.TH + 1) * PWp;
     const int npos = min(a.TH, a.Ho - ty0) * a.Wo;                                       // output positions of this tile
@@ -366,8 +323,7 @@ __global__ __launch_bounds__(512, 1) void k_down_s(DSArgs a) {
             if (c < NCHUNK) issue(c);
         for (int k = 0; k < NCHUNK; ++k) {
             const int fly = min(NCHUNK - 1 - k, NBUF - 2);                               // younger chunks that may stay in flight
-            if (fly <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPER) : "memory");
+            dma_ring_wait<NPER, NBUF>(fly);
             asm volatile("s_barrier" ::: "memory");
             if (k + NBUF - 1 < NCHUNK) issue(k + NBUF - 1);
         }
@@ -428,7 +384,7 @@ __global__ __launch_bounds__(512, 1) void k_down_s(DSArgs a) {
                 for (int j = 0; j < NTW; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, bfr[cur][j]),
                                                                        __builtin_bit_cast(bf16x8_t, af[cur][i]), acc[i][j], 0, 0, 0);
-            spread<MT * NTW, MT + NTW>(std::make_integer_sequence<int, MT + NTW>{});
+            spread<MT * NTW, MT + NTW>();
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -448,7 +404,7 @@ __global__ __launch_bounds__(512, 1) void k_down_s(DSArgs a) {
             ov[2 * j] = pack_bf16x2(acc[i][j][0], acc[i][j][1]); ov[2 * j + 1] = pack_bf16x2(acc[i][j][2], acc[i][j][3]);
             if (a.relu && n0 + g * 4 * NTW + j * 4 >= a.relu_from) { ov[2 * j] = relu_bf16x2(ov[2 * j]); ov[2 * j + 1] = relu_bf16x2(ov[2 * j + 1]); }
         }
-        ds_row_store<NTW>(a.out + (size_t)opix[i] * a.Cout + n0 + g * 4 * NTW, g, ov);
+        row_store<NTW>(a.out + (size_t)opix[i] * a.Cout + n0 + g * 4 * NTW, g, ov);
     }
 }
 

@@ -17,16 +17,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pam.h"
-#include "pam_launch.hpp"
+#include "pam_kernel.hpp"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
 
 constexpr int FS_MAXI = 5;                 // 16-byte items of the output tile per thread at most
 
@@ -41,15 +34,6 @@ struct FSArgs {
     int src_base, term_off[3];              // term tiles [source][pixel][C]
     float inv_otw;
 };
-
-__device__ __forceinline__ float bf2f(uint16_t v) { return __builtin_bit_cast(float, ((uint32_t)v) << 16); }
-__device__ __forceinline__ uint16_t f2bf(float f) { return __builtin_bit_cast(uint16_t, (__bf16)f); }
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){lo, hi}, bf16x2_t));
-}
-__device__ __forceinline__ int fdiv_small(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }   // exact for x < 2^16
 
 template <int C>
 __global__ __launch_bounds__(576) void k_fuse_sum(FSArgs a) {
@@ -182,12 +166,12 @@ __global__ __launch_bounds__(576) void k_fuse_sum(FSArgs a) {
             const int r = trc[k] >> 16, c = (trc[k] >> 8) & 255, c8 = trc[k] & 255;
             float v[8];
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = bf2f((uint16_t)vb[k][e]);
+            for (int e = 0; e < 8; ++e) v[e] = bf16_to_f32((uint16_t)vb[k][e]);
 #pragma unroll
             for (int t = 0; t < 2; ++t)
                 if (t < a.nplain) {
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] += bf2f((uint16_t)vp[t][k][e]);
+                    for (int e = 0; e < 8; ++e) v[e] += bf16_to_f32((uint16_t)vp[t][k][e]);
                 }
 #pragma unroll
             for (int s = 0; s < 3; ++s)
@@ -195,11 +179,11 @@ __global__ __launch_bounds__(576) void k_fuse_sum(FSArgs a) {
                     const int sh = a.shift[s], tw = a.TB << (a.smax - sh);
                     const bf16x8 q = *(const bf16x8*)(smem + a.term_off[s] + (((r >> sh) * tw + (c >> sh)) * C + c8 * 8) * 2);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] += bf2f((uint16_t)q[e]);
+                    for (int e = 0; e < 8; ++e) v[e] += bf16_to_f32((uint16_t)q[e]);
                 }
             bf16x8 o;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (short)f2bf(a.relu ? fmaxf(v[e], 0.0f) : v[e]);
+            for (int e = 0; e < 8; ++e) o[e] = (short)f32_to_bf16(a.relu ? fmaxf(v[e], 0.0f) : v[e]);
             *(bf16x8*)(a.out + (long)eo[k] * C + c8 * 8) = o;
         }
     }

@@ -4,12 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pam.h"
+#include "pam_kernel.hpp"
 
 #define J PAM_J
-
-__device__ __forceinline__ uint16_t f32_to_bf16(float f) {   // round-to-nearest-even (v_cvt_pk_bf16_f32 on gfx950)
-    return __builtin_bit_cast(uint16_t, (__bf16)f);
-}
 
 // One thread per output pixel: bilinear sample (half-pixel centres, border replicate) of the person box from the BGR
 // uint8 frame, BGR->RGB, /255, ImageNet mean/std, bf16 NHWC store (6 B per thread, contiguous across the wave).
@@ -236,7 +233,7 @@ __global__ __launch_bounds__(HEAD_T) void k_head(int npix, const uint16_t* __res
             const uint32_t d[4] = {v.x, v.y, v.z, v.w};
             float x[8];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { x[2 * k] = __uint_as_float(d[k] << 16); x[2 * k + 1] = __uint_as_float(d[k] & 0xffff0000u); }
+            for (int k = 0; k < 4; ++k) { x[2 * k] = bf16_lo(d[k]); x[2 * k + 1] = bf16_hi(d[k]); }
 #pragma unroll
             for (int j = 0; j < JN; ++j)
 #pragma unroll
@@ -291,7 +288,7 @@ __global__ __launch_bounds__(HEAD_T) void k_head_argmax(int HW, int tiles, const
             const uint32_t d[4] = {v.x, v.y, v.z, v.w};
             float x[8];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { x[2 * k] = __uint_as_float(d[k] << 16); x[2 * k + 1] = __uint_as_float(d[k] & 0xffff0000u); }
+            for (int k = 0; k < 4; ++k) { x[2 * k] = bf16_lo(d[k]); x[2 * k + 1] = bf16_hi(d[k]); }
 #pragma unroll
             for (int j = 0; j < JN; ++j)
 #pragma unroll

@@ -21,23 +21,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pam.h"
-#include "pam_launch.hpp"
+#include "pam_kernel.hpp"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) short s16x2;
-#define OOB_OFFSET 0x80000000u
-
-__device__ __forceinline__ uint32_t pw_pack(float lo, float hi) {
+// the element-wise pack (two converts + a permute); the shared pack_bf16x2 changes these kernels' code and is left to a measured change
+__device__ __forceinline__ uint32_t pack_bf16x2_ew(float lo, float hi) {
     typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
     bf16x2_t v = {(__bf16)lo, (__bf16)hi};
     return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ float pw_lo(uint32_t d) { return __builtin_bit_cast(float, d << 16); }
-__device__ __forceinline__ float pw_hi(uint32_t d) { return __builtin_bit_cast(float, d & 0xffff0000u); }
-__device__ __forceinline__ uint32_t pw_relu2(uint32_t d) {          // ReLU on a bf16 pair: one packed int16 max (bf16 is sign-magnitude)
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, d), (s16x2){0, 0}));
 }
 
 struct PwArgs {
@@ -170,9 +160,9 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_pw2(PwArgs a) {
                     float v0 = acc3[mt][j][0], v1 = acc3[mt][j][1], v2 = acc3[mt][j][2], v3 = acc3[mt][j][3];
                     if constexpr (RES) {
                         const uint32_t d0 = rc[mt][j >> 1][(2 * j) & 3], d1 = rc[mt][j >> 1][(2 * j + 1) & 3];
-                        v0 += pw_lo(d0); v1 += pw_hi(d0); v2 += pw_lo(d1); v3 += pw_hi(d1);
+                        v0 += bf16_lo(d0); v1 += bf16_hi(d0); v2 += bf16_lo(d1); v3 += bf16_hi(d1);
                     }
-                    o[2 * j] = pw_relu2(pw_pack(v0, v1)); o[2 * j + 1] = pw_relu2(pw_pack(v2, v3));
+                    o[2 * j] = relu_bf16x2(pack_bf16x2_ew(v0, v1)); o[2 * j + 1] = relu_bf16x2(pack_bf16x2_ew(v2, v3));
                 }
                 xf[mt][0] = (u32x4){o[0], o[1], o[2], o[3]}; xf[mt][1] = (u32x4){o[4], o[5], o[6], o[7]};
                 const unsigned po = pix_off(wt, mt, 512);
@@ -203,8 +193,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void k_pw2(PwArgs a) {
                 uint32_t o[8];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    o[2 * j] = pw_relu2(pw_pack(acc1[mt][j][0], acc1[mt][j][1]));
-                    o[2 * j + 1] = pw_relu2(pw_pack(acc1[mt][j][2], acc1[mt][j][3]));
+                    o[2 * j] = relu_bf16x2(pack_bf16x2_ew(acc1[mt][j][0], acc1[mt][j][1]));
+                    o[2 * j + 1] = relu_bf16x2(pack_bf16x2_ew(acc1[mt][j][2], acc1[mt][j][3]));
                 }
                 const unsigned po = pix_off(wt, mt, 128);
                 const unsigned oo = po == OOB_OFFSET ? po : po + g * 32;
@@ -281,11 +271,11 @@ __global__ __launch_bounds__(256) void k_pw1(Pw1Args a) {
                 for (int j = 0; j < 4; ++j) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) acc[j][r] = acc[j][r] > 0.0f ? acc[j][r] : 0.1f * acc[j][r];
-                    o[2 * j] = pw_pack(acc[j][0], acc[j][1]); o[2 * j + 1] = pw_pack(acc[j][2], acc[j][3]);
+                    o[2 * j] = pack_bf16x2_ew(acc[j][0], acc[j][1]); o[2 * j + 1] = pack_bf16x2_ew(acc[j][2], acc[j][3]);
                 }
             } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { o[2 * j] = pw_relu2(pw_pack(acc[j][0], acc[j][1])); o[2 * j + 1] = pw_relu2(pw_pack(acc[j][2], acc[j][3])); }
+                for (int j = 0; j < 4; ++j) { o[2 * j] = relu_bf16x2(pack_bf16x2_ew(acc[j][0], acc[j][1])); o[2 * j + 1] = relu_bf16x2(pack_bf16x2_ew(acc[j][2], acc[j][3])); }
             }
             const int m = (t0 + u) * 16 + px;
             const unsigned oo = (t0 + u < ntile && m < a.M) ? (unsigned)m * 128u + g * 32 : OOB_OFFSET;

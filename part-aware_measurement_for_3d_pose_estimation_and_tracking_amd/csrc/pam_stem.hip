@@ -28,18 +28,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pam.h"
-#include "pam_launch.hpp"
+#include "pam_kernel.hpp"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-typedef __attribute__((ext_vector_type(2))) short s16x2;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
-#define OOB_OFFSET 0x80000000u
 
 #ifndef STEM_LOOK
 #define STEM_LOOK 1
@@ -61,15 +52,6 @@ struct StemFArgs {
     uint16_t* x0; uint16_t* y1;
     int N, H, W, H1, W1, H2, W2, tiles_y, tiles_x, ntiles;
 };
-
-__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {      // one v_cvt_pk_bf16_f32 (RNE) the compiler can see: as an asm
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;            // statement it is not padded against the MFMA that wrote lo / hi
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2){lo, hi}, bf16x2_t));
-}
-__device__ __forceinline__ uint32_t relu_bf16x2(uint32_t v) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), (s16x2){0, 0}));
-}
 
 __global__ __launch_bounds__(512, 1) void k_stem_fused(StemFArgs a) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
