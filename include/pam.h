@@ -212,15 +212,15 @@ int pam_decode_heatmaps(void* stream, int n, const float* dev_heatmaps, int nchw
 int pam_clock_probe(void* stream, unsigned long long* dev_out2, int microseconds);
 
 /* ---- HRNet conv stack (a1) as hand-written MFMA kernels -------------------------------------------------------
- * pam_conv2d_nhwc_bf16: NHWC bf16 convolution (KH,KW in {1,3}; stride 1/2; Cin % 8 == 0; Cout % 48 == 0 or % 64 == 0) as an
+ * pam_conv2d_nhwc_bf16: NHWC bf16 convolution (KH,KW in {1,3}; stride 1/2; Cin % 8 == 0; Cout % 48 == 0, % 64 == 0 or % 32 == 0) as an
  * implicit GEMM on v_mfma_f32_16x16x32_bf16 with fused epilogue out = act(conv + bias [+ residual]); `relu` is the activation
  * code: 0 linear, 1 ReLU, 2 leaky ReLU (slope 0.1, Darknet); + 4 = add the residual AFTER the activation (Darknet shortcut).  w_packed is
  * [Cout][Kpad] bf16, k = (ky, kx, cin) flattened, zero-padded to Kpad = roundup(KH*KW*Cin, 64); bias float32 or NULL;
  * residual NHWC bf16 of the output shape or NULL.  tile_cfg: -1 = choose automatically (w_img in the layout pam_conv3x3_layout() announces
  * at call time), -3 / -4 = the same with the layout of w_img STATED by the caller (-3 streamed: k_conv3x3s or PAM_E_ARG; -4 classic),
  * -2 = the classic kernels (k_conv3x3 /
- * k_conv_igemm) with automatic tiles, 0..7 = one k_conv_igemm tile shape, 8 = the streamed implicit GEMM k_conv_gs (activation codes 0 / 1).  w_img (optional, 3x3 stride-1 layers
- * with Cin in {48,64,96,128,192,256,384,512}): the same weights pre-packed as per-chunk LDS images [Cout/BN][Cin/CK][BN][9*CK + pad] (BN =
+ * k_conv_igemm) with automatic tiles, 0..7 = one k_conv_igemm tile shape (Cout a multiple of 32 only: 0 / 2), 8 = the streamed implicit GEMM k_conv_gs (activation codes 0 / 1).  w_img (optional, 3x3 stride-1 layers
+ * with Cin in {48,64,96,128,192,256,384,512}, or 32 -> 32): the same weights pre-packed as per-chunk LDS images [Cout/BN][Cin/CK][BN][9*CK + pad] (BN =
  * pam_conv3x3_slab(H, W, Cin, Cout); CK = 48 if Cin == 48, 64 if Cin >= 192, else 32; row pitch 864 / 1184 / 608 bytes;
  * row j*16 + q of a slab, q < 16, j < BN/16, holds output channel 4*(BN/16)*(q >> 2) + 4*j + (q & 3) of that slab) for the
  * rows-in-LDS kernel k_conv3x3; for a stem layer (Cin 8, Cout 32 or 64, 3x3, stride 1 or 2, pad 1; Cout 32 is accepted only
@@ -286,7 +286,7 @@ int pam_upsample_add_nhwc_bf16_ex(void* stream, const void* base, int n_terms, c
 /* ---- fused HRNet BasicBlock (row a1; stands inside the absent HRNet backend behind /root/reference/src/ivclabpose.py:210).
  * out = ReLU(conv3x3(ReLU(conv3x3(in) + b1)) + b2 + in), NHWC bf16, C -> C -> C, stride 1, pad 1, BatchNorm folded; the intermediate
  * never leaves LDS.  ONE launch per tensor with 2-D items of tile_rows x tile_cols output positions (csrc/pam_block2.hip), all
- * operands fetched by LDS-DMA.  pam_basic_block2_tile writes the {rows, cols} the library would pick for N x H x W (whole rounds of 256
+ * operands fetched by LDS-DMA; C = 32, 48 or 96.  pam_basic_block2_tile writes the {rows, cols} the library would pick for N x H x W (whole rounds of 256
  * workgroups first, then the least work per item); tile_rows / tile_cols <= 0 in the launch = that choice.  in != out.
  * C = 48 (k_bblock2_48): BOTH weight sets resident in LDS beside a 75 KB input tile, no barrier inside the K loops.  Limits:
  *   (rows + 4)(cols + 4) <= 800, (rows + 2)(cols + 4) <= 768, rows (cols + 2) <= 640.
@@ -301,7 +301,14 @@ int pam_upsample_add_nhwc_bf16_ex(void* stream, const void* base, int n_terms, c
  *   wpack (1 024 + 331 776 bytes): [float32 bias 96 + 96, padded to 1 KiB][54 k-step images of [96 rows][64 bytes]] in the order (conv,
  *   chunk of 32 input channels, tap); row j*16 + q = output channel 24*(q >> 2) + 4*j + (q & 3); physical 16-byte piece p of row r
  *   holds the chunk's input channels 8*(p ^ ((r >> 1) & 2)) .. + 7.  The residual enters the sum before the products (as in the
- *   streamed convolution kernel): equal to the two-launch path to within the last bf16 bit. */
+ *   streamed convolution kernel): equal to the two-launch path to within the last bf16 bit.
+ * C = 32 (k_bblock2_32, csrc/pam_block32.hip; HRNet-W32): both weight sets resident in LDS (2 x 18 KB), no barrier inside the K loops.
+ *   Limits: (rows + 2)(cols + 4) <= 768, rows (cols + 2) <= 640, (rows + 4)(cols + 4) <= 1968.  Activation slots of 64 bytes in LDS with
+ *   physical piece p of slot s holding channels 8*(p ^ ((s >> 2) & 3)) .. + 7 (conflict-free ds_read_b128 at every tap offset).
+ *   wpack (1 024 + 36 864 bytes): [float32 bias: conv1's 32, conv2's 32, zero padding to 1 KiB][conv1's 9 k-step images][conv2's 9]; k-step
+ *   t = tap t (ky * 3 + kx), its 32 K elements = the 32 input channels; a k-step image = [32 rows][64 bytes = 4 pieces of 8 bf16]: row
+ *   j*16 + q = output channel 8*(q >> 2) + 4*j + (q & 3), physical piece p of row R holds input channels 8*(p ^ ((R >> 2) & 3)) .. + 7.
+ *   Results are bit-identical to two pam_conv2d_nhwc_bf16 calls on k_conv3x3<32> (same K order per output element). */
 int pam_basic_block2_tile(int C, int N, int H, int W, int32_t* out2);
 int pam_basic_block2_nhwc_bf16(void* stream, const void* in, const void* wpack, void* out, int N, int H, int W, int C,
                                int tile_rows, int tile_cols);

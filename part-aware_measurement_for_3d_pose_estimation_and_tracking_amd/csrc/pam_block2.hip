@@ -619,10 +619,14 @@ bool pick_tile(int N, int H, int W, int& TR, int& TC) {
 
 }  // namespace
 
+// C = 32 (HRNet-W32): k_bblock2_32, csrc/pam_block32.hip
+bool pam_bb32_pick_tile(int N, int H, int W, int& TR, int& TC);
+int pam_bb32_launch(void* stream, const void* in, const void* wpack, void* out, int N, int H, int W, int tile_rows, int tile_cols);
+
 extern "C" int pam_basic_block2_tile(int C, int N, int H, int W, int32_t* out2) {
-    if ((C != 48 && C != 96) || N < 1 || H < 1 || W < 1 || !out2) return PAM_E_ARG;
+    if ((C != 32 && C != 48 && C != 96) || N < 1 || H < 1 || W < 1 || !out2) return PAM_E_ARG;
     int tr = 0, tc = 0;
-    if (!(C == 48 ? pick_tile(N, H, W, tr, tc) : pick_tile96(N, H, W, tr, tc))) return PAM_E_ARG;
+    if (!(C == 32 ? pam_bb32_pick_tile(N, H, W, tr, tc) : C == 48 ? pick_tile(N, H, W, tr, tc) : pick_tile96(N, H, W, tr, tc))) return PAM_E_ARG;
     out2[0] = tr; out2[1] = tc;
     return PAM_OK;
 }
@@ -657,8 +661,9 @@ static int launch_bb96(void* stream, const void* in, const void* wpack, void* ou
 }
 
 extern "C" int pam_basic_block2_nhwc_bf16(void* stream, const void* in, const void* wpack, void* out, int N, int H, int W, int C, int tile_rows, int tile_cols) {
-    if ((C != 48 && C != 96) || !in || !wpack || !out || in == out || N < 1 || H < 1 || W < 1) return PAM_E_ARG;
+    if ((C != 32 && C != 48 && C != 96) || !in || !wpack || !out || in == out || N < 1 || H < 1 || W < 1) return PAM_E_ARG;
     if ((size_t)N * H * W * C * 2 >= (1ull << 31)) return PAM_E_ARG;
+    if (C == 32) return pam_bb32_launch(stream, in, wpack, out, N, H, W, tile_rows, tile_cols);
     if (C == 96) return launch_bb96(stream, in, wpack, out, N, H, W, tile_rows, tile_cols);
     BB2Args a;
     a.in = (const uint16_t*)in; a.wpack = (const char*)wpack; a.out = (uint16_t*)out;

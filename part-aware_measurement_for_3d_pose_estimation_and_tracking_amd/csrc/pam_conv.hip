@@ -308,6 +308,18 @@ static int dispatch_conv(hipStream_t s, const ConvArgs& a, int force) {
     return PAM_E_ARG;
 }
 
+// layers whose width is a multiple of 32 but of neither 48 nor 64 (HRNet-W32): one 32-channel N tile per wave (BN = 32); their N-tile
+// count is odd, so a workgroup is one wave wide -- 128-pixel blocks while they give the chip >= 2 workgroups per CU, else 64
+static int dispatch_conv32(hipStream_t s, const ConvArgs& a, int force) {
+    const long blocks128 = (long)((a.M + 127) / 128) * (a.Cout / 32);
+    const int cfg = force < 0 ? (blocks128 >= 512 ? 2 : 0) : force;
+    switch (cfg) {
+        case 0: return launch_conv<2, 1, 1>(s, a);
+        case 2: return launch_conv<2, 2, 1>(s, a);
+    }
+    return PAM_E_ARG;
+}
+
 // ====================================================================================================================
 // k_conv3x3: 3x3 / stride 1 / pad 1 convolutions (85 % of HRNet-W48's FLOPs) with the input rows resident in LDS.
 //
@@ -661,6 +673,7 @@ static void pick_rows(int N, int H, int W, int Cout, int ntw, int& TH, int& cfg)
 // output channels per workgroup slab of k_conv3x3 (the host packs the weight images with the same number).  The deep, small
 // images (24x18, 12x9) have too few pixel tiles to fill 256 CUs, so their slabs are narrower: more, shorter workgroups.
 extern "C" int pam_conv3x3_slab(int H, int W, int Cin, int Cout) {
+    if (Cout == 32) return 32;                                                     // HRNet-W32's 32-channel branch and transition1
     const int wide = (Cout % 48 == 0) ? 48 : 64;
     if (Cin < 192) return wide;
     if (Cout % 48 != 0) return H * W <= 1024 ? 32 : 64;                            // Darknet's 256- / 512-channel 3x3 layers
@@ -1375,7 +1388,10 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
     if (force_streamed || no_streamed) tile_cfg = -1;
     if (in_cstride != Cin || relu_from != 0) { if (force_streamed) return PAM_E_ARG; w_img = nullptr; }   // sliced input / partial activation: generic kernel only
     const bool stem32 = w_img && Cin == 8 && Cout == 32 && KH == 3 && KW == 3 && pad == 1 && !residual && tile_cfg < 0 && stride <= 2;
-    if (!in || !w_packed || !out || N <= 0 || H <= 0 || W <= 0 || Cin % 8 != 0 || (Cout % 48 != 0 && Cout % 64 != 0 && !stem32) ||
+    // Cout % 32 == 0 only (HRNet-W32's 32-channel outputs and the 224-channel merged up-convolution): k_conv3x3<32 | 256, 2> or the
+    // implicit GEMM with 32-channel slabs, below
+    const bool out32 = Cout % 48 != 0 && Cout % 64 != 0 && !stem32;
+    if (!in || !w_packed || !out || N <= 0 || H <= 0 || W <= 0 || Cin % 8 != 0 || (out32 && Cout % 32 != 0) ||
         KH < 1 || KW < 1 || KH > 3 || KW > 3 || stride < 1)
         return PAM_E_ARG;
     ConvArgs a;
@@ -1419,7 +1435,7 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
     const bool classic = tile_cfg == -2;                 // -2: the classic kernels (k_conv3x3 / k_conv_igemm), automatic tiles
     if (classic) tile_cfg = -1;
     if (w_img && KH == 3 && KW == 3 && stride == 1 && pad == 1 && (tile_cfg < 0 || tile_cfg >= 100) &&
-        (Cin == 48 || Cin == 64 || Cin == 96 || Cin == 192 || Cin == 384 || Cin == 128 || Cin == 256 || Cin == 512)) {
+        (Cin == 48 || Cin == 64 || Cin == 96 || Cin == 192 || Cin == 384 || Cin == 128 || Cin == 256 || Cin == 512 || (Cin == 32 && Cout == 32))) {
         const int ntw = pam_conv3x3_slab(H, W, Cin, Cout) / 16;
         int th = 0, cfg = 0;
         pick_rows(N, H, W, Cout, ntw, th, cfg);
@@ -1461,10 +1477,12 @@ extern "C" int pam_conv2d_nhwc_bf16_ex(void* stream, const void* in, const void*
             case 2562: return launch_c3<256, 2>(s, c, cfg);
             case 5124: return launch_c3<512, 4>(s, c, cfg);
             case 5122: return launch_c3<512, 2>(s, c, cfg);
+            case 322: return launch_c3<32, 2>(s, c, cfg);       // HRNet-W32's 32-channel branch (unfused BasicBlocks)
             default: if (tile_cfg >= 100) return PAM_E_ARG;     // no instantiation for this (Cin, slab): generic kernel below
         }
     }
     if (tile_cfg >= 100) tile_cfg = -1;
+    if (out32) return dispatch_conv32((hipStream_t)stream, a, tile_cfg);
     // streamed implicit GEMM (k_conv_gs): codes 0 / 1, taps in a 32-bit mask, whole 16-byte pieces per tap (Cin % 8 == 0)
     // (round 5: code 2 -- leaky, no residual -- too: the detector's 1x1 and strided layers, which the classic implicit GEMM ran at 20 us each)
     const bool leaky_gs = relu == 2 && !a.res && classic && relu_from == 0;

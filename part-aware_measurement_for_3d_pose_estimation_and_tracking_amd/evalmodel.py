@@ -35,7 +35,8 @@ def eval_ivclabpose_PersonTrack_Project3DPose(cfg, inputs):
 if __name__ == "__main__":
     parser = argparse.ArgumentParser()
     parser.add_argument('--dataset', help='Three options: CampusSeq1, Shelf, Panoptic', type=str, default='CampusSeq1')
+    parser.add_argument('--config', help='model configuration file (default: configs/<dataset>/model_configs.yaml)', type=str, default=None)
     opt = parser.parse_args()
-    cfg = GetConfig(os.path.join(_HERE, 'configs', opt.dataset, 'model_configs.yaml'))
+    cfg = GetConfig(opt.config or os.path.join(_HERE, 'configs', opt.dataset, 'model_configs.yaml'))
     datas = LoadFilenames(cfg.DATASET)
     {'PersonTrack_Project3DPose': eval_ivclabpose_PersonTrack_Project3DPose}[cfg.TEST_FUNCTION](cfg, datas)

@@ -1,8 +1,8 @@
-"""HRNet-W48 top-down 2D pose (a1): the ``HRNetPose(...).predict(...)`` seam of the reference
+"""HRNet-W48 / -W32 top-down 2D pose (a1): the ``HRNetPose(...).predict(...)`` seam of the reference
 (/root/reference/src/ivclabpose.py:125-134,210; the backend itself is git-ignored there).
 
 The conv stack is a plain PyTorch-ROCm module (public HRNet architecture, official state-dict key layout so
-``pose_hrnet_w48_384x288.pth`` loads), run in bf16 channels-last with BatchNorm folded and replayed from a hipGraph.
+``pose_hrnet_w48_384x288.pth`` and ``pose_hrnet_w32_256x192.pth`` load), run in bf16 channels-last with BatchNorm folded and replayed from a hipGraph.
 Crop / resize / normalise and the heat-map arg-max decode are HIP kernels of libpam_hip.so (csrc/pam_image.hip).
 Parity with the authors' modified backend is UNPINNED (no source, weights or tests in the reference): decode follows
 upstream simple-HRNet (hard arg-max, linear map through the box)."""
@@ -285,12 +285,18 @@ def load_folded_checkpoint(path, c, nof_joints):
 
 class HRNetPose(object):
     """Mirror of ``backend.HRPose.SimpleHRNet.HRNetPose``: ctor (c, nof_joints, checkpoint, model_name, resolution, ...),
-    ``predict(person_bbox_list, batch_size, conf_threshold) -> dump_results`` (ivclabpose.py:131-132,210)."""
+    ``predict(person_bbox_list, batch_size, conf_threshold) -> dump_results`` (ivclabpose.py:131-132,210).
+    c: the network width, 48 (HRNet-W48, the reference's configs) or 32 (HRNet-W32, usually at resolution (256, 192))."""
+    WIDTHS = (32, 48)
+    width = 48                  # the class default: config_for reads it (tests build objects with __new__)
 
     def __init__(self, c, nof_joints, checkpoint_path, model_name='HRNet', resolution=(384, 288), hrpose_args=None,
                  device=0, dtype=torch.bfloat16, use_graph=True, seed=0, max_dets=16, backend='hip', graph_bucket=4,
                  shard_crops=False, group=None, autotune=False, max_crops=32, antialias=False):
         assert model_name == 'HRNet' and int(nof_joints) == 17
+        if int(c) != c or int(c) not in self.WIDTHS:
+            raise ValueError('HRNetPose: width c=%r is not supported (HRNet-W%s only)' % (c, ' / -W'.join(str(w) for w in self.WIDTHS)))
+        self.width = int(c)
         if not torch.cuda.is_available():
             raise RuntimeError('HRNetPose needs a GPU (the preprocessing / decode kernels are HIP only; no CPU fallback)')
         self.lib = _lib.load()
@@ -321,7 +327,7 @@ class HRNetPose(object):
             model = _folded_random_model(c, nof_joints, seed)
             self.weights = 'random(seed=%d)' % seed
         self.head = model.final_layer.to(self.device).float()           # 1x1 head + decode stay float32
-        self.head_w = self.head.weight.detach().reshape(int(nof_joints), -1).contiguous()     # [17][48] for k_head
+        self.head_w = self.head.weight.detach().reshape(int(nof_joints), -1).contiguous()     # [17][c] for k_head
         self.head_b = self.head.bias.detach().contiguous()
         model.final_layer = nn.Identity()
         # the conv stack = the hand-written MFMA kernels of csrc/ (hrnet_hip.HipHRNet); there is no other backend in the product: the
@@ -329,8 +335,8 @@ class HRNetPose(object):
         if backend != 'hip':
             raise ValueError("HRNetPose has one conv backend, 'hip' (got %r)" % (backend,))
         self.backend = backend
-        from .hrnet_hip import HipHRNet
-        self.hip = HipHRNet(model, self.device)
+        from .hrnet_hip import HipHRNet, HipHRNetW32
+        self.hip = (HipHRNetW32 if self.width == 32 else HipHRNet)(model, self.device)
         self.in_channels = 8
         self.model = None
         self.use_graph = use_graph
@@ -384,7 +390,7 @@ class HRNetPose(object):
 
     # -- conv stack (PyTorch-ROCm; hipGraph replay per batch size) -------------------------------------------------
     def _forward(self, x, kind='heatmaps'):
-        f = self.hip.features(x)                                        # (N, 48, h, w) channels-last bf16
+        f = self.hip.features(x)                                        # (N, c, h, w) channels-last bf16
         if kind == 'features':
             return f
         n, c, h, w = f.shape
@@ -401,7 +407,7 @@ class HRNetPose(object):
         return self._run(x, 'heatmaps', slot)
 
     def features(self, x, slot=0):
-        """x as above -> (N,48,H/4,W/4) channels-last bf16: the input of ``head_decode`` (the product path: the heat-maps are
+        """x as above -> (N,c,H/4,W/4) channels-last bf16: the input of ``head_decode`` (the product path: the heat-maps are
         never written).  slot: which replay instance (own static input / activations / output) -- two frames whose forwards are in
         flight at the same time (FramePipeline(pose_streams=2)) use different slots of the same weights."""
         return self._run(x, 'features', slot)
@@ -638,9 +644,10 @@ class HRNetPose(object):
         as ONE workgroup; 2 crops -8 %, 4 -10 %, 6 -8 %, 9 -3 ... -6 %, 12 -2 %, 14 0 %, 16 +2 %).
         The 96-channel branch as streamed convolutions (round 4's choice for 8-12 crops under stream events) loses at every count now
         (+0.1 ... +5.6 %).  (Round 3 timed every configuration at the first replay of a crop count: 1.5 s per count, a choice decided by
-        noise, and three dead captures per count that could never be destroyed, see _lib.new_graph.)"""
+        noise, and three dead captures per count that could never be destroyed, see _lib.new_graph.)
+        HRNet-W32 has one configuration per executor setting (HipHRNetW32.CONFIGS): its class default at every crop count."""
         name = type(self.hip).config_name
-        if self.autotune:
+        if self.autotune and self.width == 48:
             name = 'fused48_fused96_fsum_s32' if n <= self.s32_max_crops else ('fused48_fused96_fsum' if n <= self.fsum_max_crops else name)
         self.tuned[n] = {'choice': name}
         return name
@@ -688,7 +695,7 @@ class HRNetPose(object):
 
     def head_decode(self, f, view_of, slot_of, boxes, det, kp=None, heat=None, n=None):
         """Final 1x1 convolution + arg-max decode (soft-arg-max when ``self.soft_beta`` is set) in one pass over the features f
-        (N,48,h,w channels-last bf16): det rows as ``decode``; the heat-maps are written only when ``heat`` (N,17,h,w float32
+        (N,c,h,w channels-last bf16): det rows as ``decode``; the heat-maps are written only when ``heat`` (N,17,h,w float32
         channels-last) is given.  n: decode only the first n crops of f."""
         nf, c, h, w = f.shape
         n = nf if n is None else n

@@ -1,4 +1,4 @@
-"""HRNet-W48 conv stack on the hand-written MFMA kernels of csrc/pam_conv.hip (no MIOpen in the loop).
+"""HRNet-W48 / -W32 conv stack on the hand-written MFMA kernels of csrc/pam_conv.hip (no MIOpen in the loop).
 
 The folded (conv + bias) PyTorch module of hrnet.py is walked once into packed weights; ``forward`` then issues one
 ``pam_conv2d_nhwc_bf16`` per convolution -- bias, residual add and ReLU fused into its epilogue -- plus one
@@ -28,7 +28,8 @@ class PackedConv(object):
             b = torch.cat([b, torch.zeros(pad_cout_to - cout)])
             cout = pad_cout_to
         stem = cin == 8 and cout in (32, 64) and kh == 3 and kw == 3 and conv.stride[0] in (1, 2) and conv.padding[0] == 1
-        assert cin % 8 == 0 and (cout % 48 == 0 or cout % 64 == 0 or stem), (cin, cout)
+        # widths that are multiples of 32 only (HRNet-W32: 32, 224): the implicit GEMM with 32-channel slabs, k_conv3x3<32 | 256, 2>
+        assert cin % 8 == 0 and (cout % 48 == 0 or cout % 64 == 0 or cout % 32 == 0 or stem), (cin, cout)
         ktot = kh * kw * cin
         kpad = (ktot + 63) // 64 * 64
         wp = torch.zeros((cout, kpad), dtype=torch.float32)
@@ -39,7 +40,8 @@ class PackedConv(object):
         self.stride, self.pad = conv.stride[0], conv.padding[0]
         # per-chunk LDS images for k_conv3x3, built lazily per slab width (the kernel picks the slab from the layer's H x W)
         self._w_ohwi = w.permute(0, 2, 3, 1).contiguous() if (kh == 3 and kw == 3 and self.stride == 1 and self.pad == 1 and
-                                                              cin in (48, 64, 96, 128, 192, 256, 384, 512)) else None
+                                                              (cin in (48, 64, 96, 128, 192, 256, 384, 512) or
+                                                               (cin == 32 and cout == 32))) else None
         self._images = {}
         self._device = device
         # stem convolution (8 -> 32 / 64 channels, 3x3, stride 1 / 2): the MFMA A fragments of k_conv_stem, [n-tile j][ky][lane][8]:
@@ -171,18 +173,29 @@ class PackedUp(object):
 
 
 class PackedBlock(object):
-    """One BasicBlock (conv3x3 -> ReLU -> conv3x3 -> + x -> ReLU) of the 48- or 96-channel branch packed for
+    """One BasicBlock (conv3x3 -> ReLU -> conv3x3 -> + x -> ReLU) of the 32-, 48- or 96-channel branch packed for
     ``pam_basic_block2_nhwc_bf16`` (csrc/pam_block2.hip; layouts: include/pam.h): ONE buffer ``wpack`` =
     [float32 bias of conv1, conv2, padded to 1 KiB][k-step weight images of conv1][... of conv2]."""
 
     def __init__(self, conv1, conv2, device):
         c = conv1.weight.shape[0]
-        assert c in (48, 96) and conv1.weight.shape == (c, c, 3, 3) and conv2.weight.shape == (c, c, 3, 3)
+        assert c in (32, 48, 96) and conv1.weight.shape == (c, c, 3, 3) and conv2.weight.shape == (c, c, 3, 3)
         rows = torch.arange(c)
         zb = lambda cv: cv.bias.detach().float() if cv.bias is not None else torch.zeros(c)
         head = torch.zeros(256, dtype=torch.float32)
         head[:2 * c] = torch.cat([zb(conv1), zb(conv2)])
-        if c == 48:
+        if c == 32:
+            # k_bblock2_32: K = (tap, cin), 9 k-steps of 32 (one per tap); a k-step image = [32 rows][4 pieces][8].  Row j * 16 + q =
+            # channel 8 (q >> 2) + 4 j + (q & 3) (a lane ends with channels 8 g .. 8 g + 7: one 16-byte piece of a pixel); physical piece
+            # p of row R holds logical piece p ^ ((R >> 2) & 3) (LDS bank swizzle)
+            chan = 8 * ((rows % 16) >> 2) + 4 * (rows // 16) + (rows & 3)
+            src = torch.arange(4)[None, :] ^ ((rows >> 2) & 3)[:, None]
+            imgs = []
+            for conv in (conv1, conv2):
+                w = conv.weight.detach().float().permute(0, 2, 3, 1)[chan].reshape(c, 9, 4, 8)      # [row][tap][piece][8]
+                imgs.append(torch.gather(w, 2, src[:, None, :, None].expand(c, 9, 4, 8)).permute(1, 0, 2, 3))
+            nbytes = 1024 + 2 * 9 * c * 64
+        elif c == 48:
             # k_bblock2_48: K = (tap, cin) flattened, 14 k-steps of 32 (zero tail); a k-step image = [48 rows][4 pieces][8].  Row
             # j * 16 + 4 q' + r = channel 8 q' + 4 j + r for N tiles j = 0, 1 and 32 + 4 q' + r for j = 2 (a lane ends with channels
             # 8 g .. 8 g + 7 and 32 + 4 g .. + 3: aligned 16 + 8 bytes of a pixel); physical piece p of row R holds logical piece
@@ -457,7 +470,7 @@ class ConvEngine(object):
         return y
 
     def basic_block2(self, op, x, tile=None):
-        """One BasicBlock (PackedBlock with ``wpack``: C = 48) on x through the resident-weights kernel; tile = (rows, cols) or None."""
+        """One BasicBlock (PackedBlock with ``wpack``: C = 32, 48 or 96) on x through the resident-weights kernel; tile = (rows, cols) or None."""
         n, c, h, w = x.shape
         assert c == op.c, (x.shape, op.c)
         y = self._new(n, c, h, w, x.device)
@@ -759,8 +772,9 @@ class HipHRNet(ConvEngine):
     def _module(self, hm):
         P = lambda c: PackedConv(c, self.device)
         branches = [[(P(b.conv1), P(b.conv2)) for b in br] for br in hm.branches]
-        # the same blocks packed for the fused kernels (48- and 96-channel branches: one launch per block)
-        fused = [[PackedBlock(b.conv1, b.conv2, self.device) for b in br] if br[0].conv1.out_channels in (48, 96) else None for br in hm.branches]
+        # the same blocks packed for the fused kernels (32-, 48- and 96-channel branches: one launch per block)
+        fused = [[PackedBlock(b.conv1, b.conv2, self.device) for b in br] if br[0].conv1.out_channels in (32, 48, 96) else None
+                 for br in hm.branches]
         fuse = []
         for i, row in enumerate(hm.fuse_layers):
             r = []
@@ -849,7 +863,8 @@ class HipHRNet(ConvEngine):
         self.config_name = name
 
     config_name = 'fused48_fused96'
-    block2 = 3                  # bit 0: 48-channel branch as one resident-weights fused BasicBlock launch per block (k_bblock2_48), bit 1: the
+    block2 = 3                  # bit 0: the finest branch (48 channels; 32 in HipHRNetW32) as one resident-weights fused BasicBlock launch per
+                                # block (k_bblock2_48 / k_bblock2_32), bit 1: the
                                 # 96-channel branch on the streamed-weights fused block (k_bblock2_96) -- csrc/pam_block2.hip
     c96_slab = 48               # 96 -> 96 layers that are NOT fused: k_conv3x3s with 48-channel slabs (0 = k_conv3x3)
     stamp = None                # diagnostics (tools/fwd_stamps.py): callable(tag) issued on the current stream at points of the schedule
@@ -936,7 +951,7 @@ class HipHRNet(ConvEngine):
         fused = mod['fused'][b]
         if self.knock_out & (1 << b):
             return x
-        if blocks and fused is not None and (self.block2 & (1 if fused[0].c == 48 else 2)):
+        if blocks and fused is not None and (self.block2 & (2 if fused[0].c == 96 else 1)):
             for op in fused:
                 x = self.basic_block2(op, x)
             return x
@@ -1127,3 +1142,17 @@ class HipHRNet(ConvEngine):
         for m in self.stage4:
             xs = self._hr_module(m, xs)
         return self._end(xs)
+
+
+class HipHRNetW32(HipHRNet):
+    """HRNet-W32 (branches of 32 / 64 / 128 / 256 channels) on the same executor.  The 32-channel branch has a fused block
+    (k_bblock2_32, block2 bit 0); the 64-channel branch runs as two launches per block (its two weight sets, 144 KB, do not fit LDS
+    beside a tile).  k_fuse_sum (fused_sums) and the 32-channel slabs of the 192- / 384-channel layers (slab32) have no W32 form, the
+    stride-2 k_down48 / k_down_s never see a W32 input (48 / 96 / 192 channels)."""
+    CONFIGS = {
+        'w32_fused': dict(block2=1, c96_slab=0, fused_sums=False, slab32=False),       # one k_bblock2_32 launch per 32-channel block
+        'w32_unfused': dict(block2=0, c96_slab=0, fused_sums=False, slab32=False),     # two k_conv3x3<32> launches per block (bit-identical)
+    }
+    config_name = 'w32_fused'
+    block2 = 1
+    c96_slab = 0

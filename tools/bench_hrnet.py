@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU micro-benchmark of the HRNet-W48 conv stack variants (development tool)."""
+"""GPU micro-benchmark of the HRNet-W48 / -W32 conv stack variants (development tool)."""
 import os, sys, time, argparse
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -14,9 +14,12 @@ ap.add_argument('--backends', default='hip')
 ap.add_argument('--no-branch-streams', action='store_true')
 ap.add_argument('--order', default='0,1,2,3')
 ap.add_argument('--config', default='', help='executor configuration (HipHRNet.CONFIGS); empty = the flags below'); ap.add_argument('--merge', type=int, default=2, help='0: no merged fuse convs, 1: strided chains only, 2: + up-convs')
+ap.add_argument('--width', type=int, default=48, help='network width: 48 (HRNet-W48) or 32 (HRNet-W32)')
+ap.add_argument('--resolution', default='384,288', help='network input H,W (W32: 256,192)')
 args = ap.parse_args()
 dev = torch.device('cuda:0')
-flops = hrnet.count_flops() * args.n
+res = tuple(int(q) for q in args.resolution.split(','))
+flops = hrnet.count_flops(args.width, 17, *res) * args.n
 
 
 def timeit(fn, iters):
@@ -35,7 +38,7 @@ for backend in args.backends.split(','):
     for mode in args.modes.split(','):
         torch.backends.cudnn.benchmark = (mode == 'bench')
         t0 = time.time()
-        net = hrnet.HRNetPose(48, 17, None, use_graph=(mode == 'graph'), backend=backend)
+        net = hrnet.HRNetPose(args.width, 17, None, resolution=res, use_graph=(mode == 'graph'), backend=backend)
         if backend == 'hip':
             net.hip.multi_stream = not args.no_branch_streams
             net.hip.order = tuple(int(q) for q in args.order.split(','))
@@ -47,4 +50,4 @@ for backend in args.backends.split(','):
         net.heatmaps(x); torch.cuda.synchronize()
         t1 = time.time()
         ms = timeit(lambda: net.heatmaps(x), args.iters)
-        print(backend, '%-6s N=%d  first-call %.1fs  %.3f ms/forward  %.1f TFLOP/s' % (mode, args.n, t1 - t0, ms, flops / ms / 1e9), flush=True)
+        print(backend, 'W%d %dx%d %-6s N=%d  first-call %.1fs  %.3f ms/forward  %.1f TFLOP/s' % (args.width, res[0], res[1], mode, args.n, t1 - t0, ms, flops / ms / 1e9), flush=True)

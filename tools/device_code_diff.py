@@ -3,7 +3,7 @@
 
 Each directory holds the `.s` files of `hipcc $(CXXFLAGS) --cuda-device-only -S pam_X.hip -o DIR/pam_X.s` (Makefile flags; once more
 with -DPAM_DIAG for the diagnostic build).  Per kernel the body (symbol to .Lfunc_end), the .amdhsa_kernel descriptor and the
-kernel's .amdgpu_metadata entry must be equal after two normalisations: the random __hip_cuid_* symbol, and local labels
+kernel's .amdgpu_metadata entry must be equal after three normalisations: assembler comments dropped, the random __hip_cuid_* symbol, and local labels
 (.LBB / .Lfunc_end / .Ltmp), renumbered in order of appearance because their function index moves with definition order.
 usage: device_code_diff.py OLD_DIR NEW_DIR      exit status 1 when a kernel differs or exists on one side only
 """
@@ -13,11 +13,14 @@ import sys
 
 CUID = re.compile(r"__hip_cuid_\w+")
 LABEL = re.compile(r"\.L(?:BB|func_end|tmp)[0-9_]+")
+COMMENT = re.compile(r"[ \t]*;.*$", re.M)
 
 
 def norm(lines):
     seen = {}
-    text = CUID.sub("__hip_cuid_X", "".join(lines))
+    # assembler comments go first: they name basic blocks by their function-wide number (";   in Loop: Header=BB166_5"), which moves
+    # whenever an instantiation is added in front of the kernel, like the labels
+    text = CUID.sub("__hip_cuid_X", "".join(COMMENT.sub("", l) for l in lines))
     return LABEL.sub(lambda m: seen.setdefault(m.group(0), ".L%d" % len(seen)), text)
 
 
