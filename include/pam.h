@@ -347,6 +347,23 @@ int pam_stem_fused_nhwc_bf16(void* stream, const void* in, const void* w1frag, c
 int pam_bottleneck_fused_nhwc_bf16(void* stream, const void* y1, const void* x0, const void* residual, const void* w2img,
                                    const float* bias2, const void* w3_img, const float* bias3, const void* w1_img, const float* bias1,
                                    void* out_x, void* out_y1, int N, int H, int W);
+/* ---- PoseResNet (Simple Baselines) layers of its own (csrc/pam_resnet.hip; executor: hrnet_hip.HipPoseResNet) ----------------
+ * pam_resnet_stem_nhwc_bf16: conv 7x7 stride 2 pad 3 (8 -> 64 channels) + bias + ReLU, then max-pool 3x3 stride 2 pad 1, in ONE launch (the
+ * H/2 map stays in LDS).  in (N, H, W, 8) bf16 NHWC (RGB + 5 zero channels: pam_preprocess_crops(out_c = 8)); out (N, Hp, Wp, 64) bf16 NHWC
+ * with Hc = (H - 1) / 2 + 1, Hp = (Hc - 1) / 2 + 1 (W alike).  wfrag [4 n-tiles j][7 ky][2 k-steps s][64 lanes][8] bf16: lane l holds, for
+ * output channel 16 ((l & 15) >> 2) + 4 j + (l & 3), input channels 0 .. 7 of tap (ky, kx = 4 s + (l >> 4)); kx = 7 is zero.  bias [64] float32.
+ * Constraints: N >= 1, H, W >= 2, Wc <= 192, N H W 16 < 2^31 and N Hp Wp 128 < 2^31 (32-bit offsets).  PAM_E_ARG otherwise (null pointer
+ * included), PAM_E_HIP on a launch error. */
+int pam_resnet_stem_nhwc_bf16(void* stream, const void* in, const void* wfrag, const float* bias, void* out, int N, int H, int W);
+/* pam_deconv4x4s2_nhwc_bf16: ConvTranspose2d(Cin, Cout, 4, stride 2, padding 1, output_padding 0) + bias [+ ReLU when relu = 1] in one launch
+ * for all four output parities.  in (N, H, W, Cin) bf16 NHWC -> out (N, 2H, 2W, Cout) bf16 NHWC; bias [Cout] float32 (BN folded).
+ * wimg: Cin Cout 16 bf16, [parity p = 2 py + px][slab s = Cout / 64][k-step c = Cin / 32][tap t = 2 ty + tx][n-tile j = 4][lane 64][8]: lane l
+ * holds output channel 64 s + 16 ((l & 15) >> 2) + 4 j + (l & 3) and input channels 32 c + 8 (l >> 4) .. + 7 of kernel tap (ky, kx) with
+ * ky = (1, 3)[ty] for py = 0 and (2, 0)[ty] for py = 1 (kx alike from px, tx): output (2 m + py, 2 k + px) reads input (m + dy, k + dx) with
+ * dy = (0, -1)[ty] / (0, +1)[ty].  Constraints: Cin % 32 == 0, Cout % 64 == 0, W <= 128, relu in {0, 1}, N H W Cin 2 < 2^31 and
+ * N 4 H W Cout 2 < 2^31 (32-bit offsets).  PAM_E_ARG otherwise (null pointer included), PAM_E_HIP on a launch error. */
+int pam_deconv4x4s2_nhwc_bf16(void* stream, const void* in, const void* wimg, const float* bias, void* out, int N, int H, int W,
+                              int Cin, int Cout, int relu);
 /* y = ReLU(W . x + bias), 64 -> 64 channels, pointwise (the first Bottleneck's conv1 on the stem output): w_img [64 rows][64 K] bf16, row
  * 16 jt + qq = output channel 16 (qq >> 2) + 4 jt + (qq & 3), natural K order, the row's 16-byte piece at position p holds K values
  * 8 q .. 8 q + 7 with q = p ^ ((row >> 1) & 7). */

@@ -84,6 +84,8 @@ _SIGS = {
     'pam_pointwise64_act_nhwc_bf16': (_I, [_P, _P, _P, _P, _P, C.c_longlong, _I]),
     'pam_stem_fused_nhwc_bf16': (_I, [_P] * 10 + [_I, _I, _I]),
     'pam_bottleneck_fused_nhwc_bf16': (_I, [_P] * 12 + [_I, _I, _I]),
+    'pam_resnet_stem_nhwc_bf16': (_I, [_P] * 5 + [_I, _I, _I]),
+    'pam_deconv4x4s2_nhwc_bf16': (_I, [_P] * 5 + [_I] * 6),
     'pam_bottleneck_tail_nhwc_bf16': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_longlong, _I]),
     'pam_conv3x3s2_c48_tile': (_I, [_I, _I, _I, _I, _P]),
     'pam_conv3x3s2_c48_nhwc_bf16': (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I] + [_I] * 9),

@@ -286,17 +286,30 @@ def load_folded_checkpoint(path, c, nof_joints):
 class HRNetPose(object):
     """Mirror of ``backend.HRPose.SimpleHRNet.HRNetPose``: ctor (c, nof_joints, checkpoint, model_name, resolution, ...),
     ``predict(person_bbox_list, batch_size, conf_threshold) -> dump_results`` (ivclabpose.py:131-132,210).
-    c: the network width, 48 (HRNet-W48, the reference's configs) or 32 (HRNet-W32, usually at resolution (256, 192))."""
+    c: the network width, 48 (HRNet-W48, the reference's configs) or 32 (HRNet-W32, usually at resolution (256, 192)); with
+    model_name='PoseResNet' the ResNet depth, 50 / 101 / 152 (Simple Baselines: poseresnet.py, executor hrnet_hip.HipPoseResNet)."""
     WIDTHS = (32, 48)
     width = 48                  # the class default: config_for reads it (tests build objects with __new__)
+    model_name = 'HRNet'        # or 'PoseResNet' (model_name 'PoseResNet' / 'poseresnet' / 'ResNet' / 'resnet'; c = depth 50 / 101 / 152)
+    depth = None
 
     def __init__(self, c, nof_joints, checkpoint_path, model_name='HRNet', resolution=(384, 288), hrpose_args=None,
                  device=0, dtype=torch.bfloat16, use_graph=True, seed=0, max_dets=16, backend='hip', graph_bucket=4,
                  shard_crops=False, group=None, autotune=False, max_crops=32, antialias=False):
-        assert model_name == 'HRNet' and int(nof_joints) == 17
-        if int(c) != c or int(c) not in self.WIDTHS:
-            raise ValueError('HRNetPose: width c=%r is not supported (HRNet-W%s only)' % (c, ' / -W'.join(str(w) for w in self.WIDTHS)))
-        self.width = int(c)
+        from . import poseresnet
+        if model_name in poseresnet.MODEL_NAMES:
+            # simple-HRNet's second family: c is the ResNet depth (Bottleneck ResNets only; 18 / 34 are BasicBlock networks)
+            if int(c) != c or int(c) not in poseresnet.DEPTHS:
+                raise ValueError('HRNetPose: PoseResNet depth c=%r is not supported (PoseResNet-%s only)' % (
+                    c, ' / -'.join(str(d) for d in sorted(poseresnet.DEPTHS))))
+            self.model_name, self.depth, self.width = 'PoseResNet', int(c), None
+        elif model_name != 'HRNet':
+            raise ValueError('HRNetPose: unknown model_name %r (HRNet, or PoseResNet as %s)' % (model_name, ' / '.join(poseresnet.MODEL_NAMES)))
+        assert int(nof_joints) == 17
+        if model_name == 'HRNet':
+            if int(c) != c or int(c) not in self.WIDTHS:
+                raise ValueError('HRNetPose: width c=%r is not supported (HRNet-W%s only)' % (c, ' / -W'.join(str(w) for w in self.WIDTHS)))
+            self.width = int(c)
         if not torch.cuda.is_available():
             raise RuntimeError('HRNetPose needs a GPU (the preprocessing / decode kernels are HIP only; no CPU fallback)')
         self.lib = _lib.load()
@@ -320,11 +333,12 @@ class HRNetPose(object):
         self.resolution = tuple(resolution)
         self.dtype = dtype
         self.max_dets = max_dets
+        resnet = self.model_name == 'PoseResNet'
         if checkpoint_path and os.path.exists(checkpoint_path):
-            model = load_folded_checkpoint(checkpoint_path, c, nof_joints)
+            model = (poseresnet.load_folded_checkpoint if resnet else load_folded_checkpoint)(checkpoint_path, c, nof_joints)
             self.weights = checkpoint_path
         else:
-            model = _folded_random_model(c, nof_joints, seed)
+            model = (poseresnet.folded_random_model if resnet else _folded_random_model)(c, nof_joints, seed)
             self.weights = 'random(seed=%d)' % seed
         self.head = model.final_layer.to(self.device).float()           # 1x1 head + decode stay float32
         self.head_w = self.head.weight.detach().reshape(int(nof_joints), -1).contiguous()     # [17][c] for k_head
@@ -335,8 +349,8 @@ class HRNetPose(object):
         if backend != 'hip':
             raise ValueError("HRNetPose has one conv backend, 'hip' (got %r)" % (backend,))
         self.backend = backend
-        from .hrnet_hip import HipHRNet, HipHRNetW32
-        self.hip = (HipHRNetW32 if self.width == 32 else HipHRNet)(model, self.device)
+        from .hrnet_hip import HipHRNet, HipHRNetW32, HipPoseResNet
+        self.hip = HipPoseResNet(model, self.device) if resnet else (HipHRNetW32 if self.width == 32 else HipHRNet)(model, self.device)
         self.in_channels = 8
         self.model = None
         self.use_graph = use_graph
@@ -645,7 +659,8 @@ class HRNetPose(object):
         The 96-channel branch as streamed convolutions (round 4's choice for 8-12 crops under stream events) loses at every count now
         (+0.1 ... +5.6 %).  (Round 3 timed every configuration at the first replay of a crop count: 1.5 s per count, a choice decided by
         noise, and three dead captures per count that could never be destroyed, see _lib.new_graph.)
-        HRNet-W32 has one configuration per executor setting (HipHRNetW32.CONFIGS): its class default at every crop count."""
+        HRNet-W32 has one configuration per executor setting (HipHRNetW32.CONFIGS): its class default at every crop count; so has PoseResNet
+        (HipPoseResNet.CONFIGS)."""
         name = type(self.hip).config_name
         if self.autotune and self.width == 48:
             name = 'fused48_fused96_fsum_s32' if n <= self.s32_max_crops else ('fused48_fused96_fsum' if n <= self.fsum_max_crops else name)

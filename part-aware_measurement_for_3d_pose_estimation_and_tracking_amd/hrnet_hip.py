@@ -1156,3 +1156,192 @@ class HipHRNetW32(HipHRNet):
     config_name = 'w32_fused'
     block2 = 1
     c96_slab = 0
+
+
+class PackedResNetStem(object):
+    """PoseResNet's conv1 (3 -> 64, 7x7 stride 2, BN folded) packed for ``pam_resnet_stem_nhwc_bf16`` (csrc/pam_resnet.hip; layout:
+    include/pam.h, poseresnet.stem_fragments); the max-pool after it has no weights."""
+
+    def __init__(self, conv, device):
+        from .poseresnet import stem_fragments
+        self.frag = stem_fragments(conv).to(torch.bfloat16).to(device).contiguous()
+        self.bias = (conv.bias.detach().float() if conv.bias is not None else torch.zeros(64)).to(device).contiguous()
+
+
+class PackedDeconv(object):
+    """A 4x4 stride-2 transposed convolution (BN folded) packed for ``pam_deconv4x4s2_nhwc_bf16``: the per-parity weight image of
+    poseresnet.deconv_image (layout: include/pam.h)."""
+
+    def __init__(self, deconv, device):
+        from .poseresnet import deconv_image
+        w = deconv.weight.detach().float()
+        assert tuple(w.shape[2:]) == (4, 4) and deconv.stride == (2, 2) and deconv.padding == (1, 1) and deconv.output_padding == (0, 0)
+        self.cin, self.cout = int(w.shape[0]), int(w.shape[1])
+        self.w = deconv_image(w).to(torch.bfloat16).to(device).contiguous()
+        self.bias = (deconv.bias.detach().float() if deconv.bias is not None else torch.zeros(self.cout)).to(device).contiguous()
+
+
+class HipPoseResNet(ConvEngine):
+    """PoseResNet-{50,101,152} (poseresnet.PoseResNet, BN folded) on the conv stack: ONE dependent chain on the caller's stream.
+    k_resnet_stem (7x7 conv + ReLU + max-pool), layer1 on HRNet's fused Bottleneck kernels (k_pw1 + k_bneck; or the un-fused
+    ConvEngine.conv launches), layer2-4 on ConvEngine.conv, then the three k_deconv4x4s2.  ``features`` returns the (N, 256, H/4, W/4)
+    channels-last bf16 map that HRNetPose's head + decode read.  No branch streams: the device-side flags are never used."""
+    CONFIGS = {
+        'resnet_fused': dict(fuse_layer1=True),       # layer1: k_pw1, then one k_bneck launch per block (3x3 + pointwise tail)
+        'resnet_unfused': dict(fuse_layer1=False),    # layer1 as ConvEngine.conv launches (1x1, 3x3, 1x1 + residual, downsample)
+    }
+    config_name = 'resnet_fused'
+    fuse_layer1 = True
+    multi_stream = False
+    flag_sync = False           # one chain: HRNetPose captures the stream-event form only
+    flags_on = False
+    flag_host_err = None
+    flag_dev_void = None
+    flag_max_us = 2000000
+    _flag_limit = None
+    _flags = None
+    stop_after = None           # tests / tools: 'stem' | 'layer1' .. 'layer4' | 'deconv0' | 'deconv1' -> the forward ends there
+    STAGES = ('stem', 'layer1', 'layer2', 'layer3', 'layer4', 'deconv0', 'deconv1', 'deconv2')
+
+    def __init__(self, folded_model, device):
+        self.lib = _lib.load()
+        self.device = device
+        self._pack(folded_model, device)
+        self.count = None
+
+    def _pack(self, m, device):
+        P = lambda c: PackedConv(c, device)
+        self.stem = PackedResNetStem(m.conv1, device)
+        l1 = list(m.layer1)
+        assert l1[0].conv1.weight.shape == (64, 64, 1, 1) and l1[0].downsample is not None
+        self.layer1 = [dict(c1=P(b.conv1), c2=P(b.conv2), c3=P(b.conv3), down=P(b.downsample[0]) if b.downsample is not None else None) for b in l1]
+        self.pw0 = PackedPointwise64(l1[0].conv1, device)
+        self.tails = [PackedTail(b.conv3, b.downsample[0] if b.downsample is not None else None, l1[i + 1].conv1 if i + 1 < len(l1) else None, device)
+                      for i, b in enumerate(l1)]
+        self.bnecks = [PackedBneck(b.conv2, self.tails[i], device) for i, b in enumerate(l1)]
+        self.layers = [[dict(c1=P(b.conv1), c2=P(b.conv2), c3=P(b.conv3), down=P(b.downsample[0]) if b.downsample is not None else None)
+                        for b in layer] for layer in (m.layer2, m.layer3, m.layer4)]
+        dl = m.deconv_layers
+        self.deconvs = [PackedDeconv(dl[i], device) for i in (0, 3, 6)]
+
+    def apply_config(self, name):
+        for k, v in self.CONFIGS[name].items():
+            setattr(self, k, v)
+        self.config_name = name
+
+    def flag_limit(self):
+        if self._flag_limit is None:
+            self._flag_limit = torch.tensor([int(self.flag_max_us)], dtype=torch.int32, device=self.device)
+        return self._flag_limit
+
+    def _epoch(self):
+        if self.arena is not None:
+            self.arena.epoch()
+
+    # -- launches of csrc/pam_resnet.hip ------------------------------------------------------------------------------------------------
+    def resnet_stem(self, op, x8):
+        """ReLU(conv7x7 s2 (x8) + b), then max-pool 3x3 s2 p1: (N, 8, H, W) -> (N, 64, Hp, Wp) in one launch (k_resnet_stem)."""
+        n, c, h, w = x8.shape
+        assert c == 8
+        hc, wc = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        hp, wp = (hc - 1) // 2 + 1, (wc - 1) // 2 + 1
+        y = self._new(n, 64, hp, wp, x8.device)
+        nbytes = 2 * (x8.numel() + y.numel() + 64 * 7 * 7 * 8) + 4 * 64
+        flops = 2 * n * hc * wc * 64 * 3 * 49                           # counted at the 3 real input channels
+        if self.count is not None:
+            self.count['bytes'] += nbytes; self.count['flops'] += flops; self.count['launches'] += 1
+        if x8.device.type == 'meta':
+            return y
+        assert x8.is_contiguous(memory_format=torch.channels_last)
+        launch = lambda: self.lib.pam_resnet_stem_nhwc_bf16(C.c_void_p(torch.cuda.current_stream(x8.device).cuda_stream), C.c_void_p(x8.data_ptr()),
+                                                             C.c_void_p(op.frag.data_ptr()), C.c_void_p(op.bias.data_ptr()), C.c_void_p(y.data_ptr()), n, h, w)
+        rc = launch()
+        if rc != 0:
+            raise _lib.PamError('pam_resnet_stem_nhwc_bf16 failed (%d) for %s' % (rc, tuple(x8.shape)))
+        self._prof_add(x8, 'k_resnet_stem 7x7 s2 + max-pool', (n, h, w), nbytes, flops, launch)
+        return y
+
+    def deconv(self, op, x, relu=True):
+        """ReLU(ConvTranspose2d 4x4 s2 p1 (x) + b): (N, Cin, H, W) -> (N, Cout, 2H, 2W) in one launch (k_deconv4x4s2, all four parities)."""
+        n, cin, h, w = x.shape
+        assert cin == op.cin, (x.shape, op.cin)
+        y = self._new(n, op.cout, 2 * h, 2 * w, x.device)
+        nbytes = 2 * (x.numel() + y.numel() + op.cin * op.cout * 16) + 4 * op.cout
+        flops = 2 * y.numel() * op.cin * 4                               # 4 live taps per output pixel
+        if self.count is not None:
+            self.count['bytes'] += nbytes; self.count['flops'] += flops; self.count['launches'] += 1
+        if x.device.type == 'meta':
+            return y
+        assert x.is_contiguous(memory_format=torch.channels_last)
+        launch = lambda: self.lib.pam_deconv4x4s2_nhwc_bf16(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), C.c_void_p(x.data_ptr()),
+                                                             C.c_void_p(op.w.data_ptr()), C.c_void_p(op.bias.data_ptr()), C.c_void_p(y.data_ptr()),
+                                                             n, h, w, op.cin, op.cout, 1 if relu else 0)
+        rc = launch()
+        if rc != 0:
+            raise _lib.PamError('pam_deconv4x4s2_nhwc_bf16 failed (%d) for %s' % (rc, tuple(x.shape)))
+        self._prof_add(x, 'k_deconv4x4s2 %d->%d' % (op.cin, op.cout), (n, h, w, op.cin, op.cout, bool(relu)), nbytes, flops, launch)
+        return y
+
+    # -- network ------------------------------------------------------------------------------------------------------------------------
+    def features(self, x8):
+        """x8: (N, 8, H, W) channels-last bf16 (RGB + 5 zero channels) -> (N, 256, H/4, W/4) channels-last bf16."""
+        self._keep = []
+        return self._features(x8)
+
+    def _layer1(self, x0):
+        n, _, h, w = x0.shape
+        small = n * h * w * 512 < 2 ** 31                                # the fused kernels index with 32 bits (as HipHRNet._head)
+        if self.fuse_layer1 and small:
+            y = self.pointwise64(self.pw0, x0)                          # the stem's epoch: block 0 reads x0 and y from the other half
+            res = None
+            for i in range(len(self.layer1)):
+                self._epoch()
+                x, y = self.bottleneck_fused(self.bnecks[i], y, res, x0 if i == 0 else None)
+                res = x
+            return x
+        x = x0
+        for b in self.layer1:
+            x = self._bottleneck(b, x)
+        return x
+
+    def _bottleneck(self, b, x):
+        self._epoch()                                                   # a block reads its input (previous epoch) and writes this one's
+        r = x if b['down'] is None else self.conv(b['down'], x)
+        y = self.conv(b['c1'], x, relu=True)
+        y = self.conv(b['c2'], y, relu=True)
+        return self.conv(b['c3'], y, res=r, relu=True)
+
+    def _features(self, x8):
+        if x8.device.type == 'meta' and self.arena is not None and self.arena.buf is None:
+            # a measuring arena (HRNetPose._arena_for sizes the activation arena ONCE, before the first capture): the largest epoch of every
+            # configuration -- the un-fused layer1 holds 640 channels at H/4 in one epoch, the fused one 320
+            saved = self.config_name
+            try:
+                for name in self.CONFIGS:
+                    self.apply_config(name)
+                    y = self._chain(x8)
+            finally:
+                self.apply_config(saved)
+            return y
+        return self._chain(x8)
+
+    def _chain(self, x8):
+        stop = self.stop_after
+        self._epoch()
+        x = self.resnet_stem(self.stem, x8)
+        if stop == 'stem':
+            return x
+        x = self._layer1(x)
+        if stop == 'layer1':
+            return x
+        for k, layer in enumerate(self.layers):
+            for b in layer:
+                x = self._bottleneck(b, x)
+            if stop == 'layer%d' % (k + 2):
+                return x
+        for k, op in enumerate(self.deconvs):
+            self._epoch()
+            x = self.deconv(op, x, relu=True)
+            if stop == 'deconv%d' % k:
+                return x
+        return x
