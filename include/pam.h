@@ -179,7 +179,8 @@ int pam_head_heatmaps(void* stream, int n_pix, const void* feat_bf16, int C, con
 /* head + decode in one pass (what the product path runs): the same 1x1 convolution (bit-identical values) with the per-joint
  * (max, first index) reduced on the fly -- the heat-maps are written only if dev_heatmaps_or_null is given.  feat: (n, hm_h, hm_w, C)
  * bf16 NHWC; det / kp / view_of / slot_of / boxes as pam_decode_heatmaps; dev_scratch: pam_head_decode_scratch_bytes(n, hm_h, hm_w)
- * bytes of device memory owned by the caller (per-tile candidates). */
+ * bytes of device memory owned by the caller (per-tile candidates).  Ties go to the lowest flat index; a map with no value above -inf
+ * (all -inf or NaN) decodes as cell 0 with score -inf, here and in pam_decode_heatmaps. */
 long long pam_head_decode_scratch_bytes(int n, int hm_h, int hm_w);
 int pam_head_decode(void* stream, int n, int hm_h, int hm_w, const void* feat_bf16, int C, const float* w, const float* bias, int J,
                     float* dev_heatmaps_or_null, const int32_t* dev_view_of, const int32_t* dev_slot_of, const float* dev_boxes,
@@ -199,7 +200,10 @@ int pam_preprocess_crops(void* stream, int n, const void* const* dev_frames /*de
  * n_total crops takes a call of n without a padded box table), and (b) antialias != 0: the resize of upstream simple-HRNet (a PIL image
  * through torchvision's Resize, i.e. PIL's ImagingResample with the bilinear filter): taps = the frame pixels whose centres lie within
  * max(scale, 1) of the output pixel's centre inside the box rounded outwards, triangle weights, normalised, in float32 (PIL's uint8
- * rounding between its two passes is not reproduced).  Equal to the plain bilinear form wherever the box is not larger than the output. */
+ * rounding between its two passes is not reproduced).  Equal to the plain bilinear form wherever the box is not larger than the output.
+ * At most 24 taps per axis (down-scaling by up to 11.5); a wider window keeps the 24 taps nearest the centre.  The outward-rounded box
+ * is clamped to the frame and always keeps one column / row of it (a box wholly outside: the nearest one); an output pixel none of whose
+ * taps has a positive weight is black (0 before the normalisation). */
 int pam_preprocess_crops_ex(void* stream, int n, int n_total, const void* const* dev_frames, int frame_h, int frame_w,
                             const int32_t* dev_view_of, const float* dev_boxes, int out_h, int out_w, int out_c, void* dev_out_bf16,
                             int antialias);

@@ -67,13 +67,16 @@ __global__ __launch_bounds__(256) void k_preprocess_crops(int n_src, const uint8
     } else {
         const float scx = bw / (float)ow, scy = bh / (float)oh, supx = fmaxf(scx, 1.0f), supy = fmaxf(scy, 1.0f);
         const float cx = bx + (ox + 0.5f) * scx, cy = by + (oy + 0.5f) * scy;
-        const int xlo = max(0, (int)floorf(bx)), xhi = max(xlo + 1, min(W, (int)ceilf(bx + bw)));
-        const int ylo = max(0, (int)floorf(by)), yhi = max(ylo + 1, min(H, (int)ceilf(by + bh)));
+        // (a box wholly right of / below the frame: the window is the last column / row, whose weight is 0 there -- a black pixel, never a read past the frame)
+        const int xlo = min(max(0, (int)floorf(bx)), W - 1), xhi = max(xlo + 1, min(W, (int)ceilf(bx + bw)));
+        const int ylo = min(max(0, (int)floorf(by)), H - 1), yhi = max(ylo + 1, min(H, (int)ceilf(by + bh)));
         int x0 = max(xlo, (int)(cx - supx + 0.5f)), x1 = min(xhi, (int)(cx + supx + 0.5f));
         int y0 = max(ylo, (int)(cy - supy + 0.5f)), y1 = min(yhi, (int)(cy + supy + 0.5f));
         if (x1 <= x0) { x0 = min(max((int)cx, xlo), xhi - 1); x1 = x0 + 1; }
         if (y1 <= y0) { y0 = min(max((int)cy, ylo), yhi - 1); y1 = y0 + 1; }
-        x1 = min(x1, x0 + AA_MAXT); y1 = min(y1, y0 + AA_MAXT);
+        // beyond the limit the window is cut to the AA_MAXT taps nearest the centre (symmetric: no shift of the sampled position)
+        if (x1 - x0 > AA_MAXT) { x0 = min(max((int)floorf(cx - 0.5f * AA_MAXT + 0.5f), x0), x1 - AA_MAXT); x1 = x0 + AA_MAXT; }
+        if (y1 - y0 > AA_MAXT) { y0 = min(max((int)floorf(cy - 0.5f * AA_MAXT + 0.5f), y0), y1 - AA_MAXT); y1 = y0 + AA_MAXT; }
         const float isx = 1.0f / supx, isy = 1.0f / supy;
         float acc[3] = {0.f, 0.f, 0.f}, wsum = 0.f;
         for (int y = y0; y < y1; ++y) {
@@ -123,6 +126,7 @@ __device__ __forceinline__ void write_keypoint_at(int j, double py, double pxx, 
     if (kp_row) { kp_row[j * 3 + 0] = x; kp_row[j * 3 + 1] = y; kp_row[j * 3 + 2] = score; }
 }
 __device__ __forceinline__ void write_keypoint(int j, Best b, int hm_h, int hm_w, const float* box, double* det_row, float* kp_row) {
+    if (b.i == 0x7fffffff) b.i = 0;        // no value was greater than -inf (a map of -inf or NaN): cell 0, as np.argmax
     write_keypoint_at(j, (double)(b.i / hm_w), (double)(b.i % hm_w), b.v, hm_h, hm_w, box, det_row, kp_row);
 }
 // soft-arg-max partial of one joint over a set of pixels: m = max, s = sum exp(beta (v - m)), sx / sy = the same sum weighted with the

@@ -1097,6 +1097,9 @@ def reference_decode(hm, boxes):
     first = (flat == val.unsqueeze(2)).float().argmax(dim=2)
     py = (first // w).double(); px = (first % w).double()
     b = boxes.double()
-    y = (py / h * b[:, 3:4] + b[:, 1:2]).float().double()
-    x = (px / w * b[:, 2:3] + b[:, 0:1]).float().double()
+    # divisors as tensors: on the GPU torch divides by a Python scalar as a multiplication with its reciprocal, which is one float32 ulp
+    # off the kernel's (and NumPy's) true division now and then (seen at h = 96)
+    hh = torch.tensor(float(h), dtype=torch.float64, device=hm.device); ww = torch.tensor(float(w), dtype=torch.float64, device=hm.device)
+    y = (py / hh * b[:, 3:4] + b[:, 1:2]).float().double()
+    x = (px / ww * b[:, 2:3] + b[:, 0:1]).float().double()
     return torch.stack([y, x, val.double()], dim=2)
