@@ -477,6 +477,24 @@ int pam_yolo_detect_ws(void* stream, int n_img, const void* const* heads, const 
                        float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det, float* dev_out, int32_t* dev_count,
                        void* dev_workspace, long long workspace_bytes);
 
+/* One to three `yolo` heads (YOLOv3-tiny has two): the three entry points above with the number of heads stated.  heads, grid_h, grid_w
+ * and chan_stride hold n_heads entries in cfg order (coarsest first); anchors: [head][anchor][w, h], 6 * n_heads floats.  Candidate order
+ * is unchanged: head, then cell row-major, then anchor.  n_heads outside 1 .. 3: PAM_E_ARG (-1 from the workspace query).  The three-head
+ * entry points are these with n_heads = 3. */
+long long pam_yolo_detect_heads_workspace_bytes(int n_img, int n_heads, const int32_t* grid_h, const int32_t* grid_w);
+int pam_yolo_detect_heads(void* stream, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
+                          const int32_t* chan_stride, const float* anchors, int net_w, int net_h, int num_classes, int class_id,
+                          float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det, float* dev_out, int32_t* dev_count);
+int pam_yolo_detect_heads_ws(void* stream, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
+                             const int32_t* chan_stride, const float* anchors, int net_w, int net_h, int num_classes, int class_id,
+                             float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det, float* dev_out, int32_t* dev_count,
+                             void* dev_workspace, long long workspace_bytes);
+/* Darknet `maxpool` on NHWC bf16 (YOLOv3-tiny): pad = size - 1, Ho = (H - 1) / stride + 1, Wo alike; the window of output (oy, ox) starts
+ * at (oy * stride - pad / 2, ox * stride - pad / 2) and taps outside the image do not take part.  out: N x Ho x Wo x C.  The result is
+ * one of the inputs (bit-exact against torch.max_pool2d on the -inf-padded tensor), so zero channels stay zero.
+ * C % 8 == 0, size 2 or 3, stride 1 or 2; PAM_E_ARG otherwise (null pointer included), PAM_E_HIP on a launch error. */
+int pam_maxpool_nhwc_bf16(void* stream, const void* in, void* out, int N, int H, int W, int C, int size, int stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,8 @@
 // libpam_hip.so, person-detector side: what `backend.YOLOv3` does around its conv stack for
 // ivclabpose.PersonDetect (/root/reference/src/ivclabpose.py:116-120,183-204; the backend itself is not in the reference
 // tree, so these follow the public Darknet YOLOv3 definition -- parity unpinned).  The Darknet-53 convolutions run on
-// pam_conv.hip; the kernels here are the HBM-bound streaming pieces: frame resize, route(upsample, skip) and the
-// three-scale box decode + greedy NMS.
+// pam_conv.hip; the kernels here are the HBM-bound streaming pieces: frame resize, route(upsample, skip), YOLOv3-tiny's
+// max-pool and the box decode + greedy NMS over one to three scales.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pam.h"
@@ -81,8 +81,67 @@ extern "C" int pam_upsample_concat_nhwc_bf16(void* stream, const void* a, const 
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
 }
 
+// ---- Darknet [maxpool] (src/maxpool_layer.c): pad = size - 1, Ho = (H + pad - size) / stride + 1 = (H - 1) / stride + 1, the window of
+// output (oy, ox) starts at (oy * stride - pad / 2, ox * stride - pad / 2), taps outside the image do not take part.  A pure stream: 8
+// channels (16 B) per lane and tap, no LDS.  The maximum is taken on floats in torch's scan order and with torch's rule (a later tap wins
+// when it is greater or NaN), so the result is one of the inputs, bit for bit what torch.max_pool2d gives on the -inf-padded tensor;
+// zero-padded channels stay zero.  Every window holds at least one tap of the image (its start is <= H - 1 - pad / 2 and >= -pad / 2).
+template <int SIZE>
+__global__ __launch_bounds__(256) void k_maxpool(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, int N, int H, int W, int C,
+                                                 int Ho, int Wo, int stride) {
+    const int C8 = C >> 3;
+    const size_t total = (size_t)N * Ho * Wo * C8;
+    constexpr int LO = (SIZE - 1) / 2;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c8 = (int)(i % C8);
+        const size_t p = i / C8;
+        const int ox = (int)(p % Wo);
+        const size_t q = p / Wo;
+        const int oy = (int)(q % Ho), n = (int)(q / Ho);
+        const int y0 = oy * stride - LO, x0 = ox * stride - LO;
+        uint4 v[SIZE * SIZE];
+        bool ok[SIZE * SIZE];
+#pragma unroll
+        for (int t = 0; t < SIZE * SIZE; ++t) {         // all taps' loads in flight together; a tap outside the image is not loaded
+            const int y = y0 + t / SIZE, x = x0 + t % SIZE;
+            ok[t] = y >= 0 && y < H && x >= 0 && x < W;
+            v[t] = make_uint4(0, 0, 0, 0);
+            if (ok[t]) v[t] = *(const uint4*)(in + (((size_t)n * H + y) * W + x) * C + c8 * 8);
+        }
+        uint32_t best[8];
+        float bf[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { best[k] = 0xff80u; bf[k] = -INFINITY; }
+#pragma unroll
+        for (int t = 0; t < SIZE * SIZE; ++t) {
+            if (!ok[t]) continue;
+            const uint32_t d[4] = {v[t].x, v[t].y, v[t].z, v[t].w};
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const uint32_t h = (k & 1) ? (d[k >> 1] >> 16) : (d[k >> 1] & 0xffffu);
+                const float f = bf16_to_f32((uint16_t)h);
+                if (f > bf[k] || f != f) { bf[k] = f; best[k] = h; }
+            }
+        }
+        uint4 o;
+        o.x = best[0] | (best[1] << 16); o.y = best[2] | (best[3] << 16); o.z = best[4] | (best[5] << 16); o.w = best[6] | (best[7] << 16);
+        *(uint4*)(out + p * C + c8 * 8) = o;
+    }
+}
+
+extern "C" int pam_maxpool_nhwc_bf16(void* stream, const void* in, void* out, int N, int H, int W, int C, int size, int stride) {
+    if (!in || !out || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || (size != 2 && size != 3) || (stride != 1 && stride != 2))
+        return PAM_E_ARG;
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    const size_t total = (size_t)N * Ho * Wo * (C / 8);
+    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    if (size == 2) hipLaunchKernelGGL(k_maxpool<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)in, (uint16_t*)out, N, H, W, C, Ho, Wo, stride);
+    else hipLaunchKernelGGL(k_maxpool<3>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)in, (uint16_t*)out, N, H, W, C, Ho, Wo, stride);
+    return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+}
+
 // ---- YOLO head decode + greedy NMS for one class --------------------------------------------------------------------
-// One workgroup per image.  Candidates are numbered head-major, then cell (row-major), then anchor.  Pass 1 keeps, in
+// One to three heads (YoloArgs.n_heads; an absent head has no candidates).  One workgroup per image.  Candidates are numbered head-major, then cell (row-major), then anchor.  Pass 1 keeps, in
 // that order, every candidate with sigmoid(objectness) * sigmoid(class logit) > score_thresh (at most PAM_YOLO_MAX_CAND of them enter
 // NMS): a thread takes DET_K consecutive candidates per round and has all their score loads in flight at once (round 5: one candidate
 // per thread and three barriers per 1 024 candidates was 11 serial memory round trips = 35 us of the 87 us launch), the kept ones are
@@ -96,6 +155,7 @@ struct YoloArgs {
     const uint16_t* head[3];
     int gh[3], gw[3], cs[3];
     float anchors[18];          // [head][anchor][w, h] in network-input pixels
+    int n_heads;                // 1 .. 3: heads h >= n_heads hold no candidates (their pointer is null and never read)
     int net_w, net_h, nc, cls;
     float score_thresh, nms_thresh;
     int frame_w, frame_h, max_det;
@@ -155,7 +215,7 @@ __device__ __forceinline__ int det_nms_wave(const YoloArgs& a, const DetLds& L, 
 __global__ __launch_bounds__(DET_T) void k_yolo_detect(YoloArgs a) {
     __shared__ DetLds L;
     const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per0 = a.gh[0] * a.gw[0] * 3, per1 = a.gh[1] * a.gw[1] * 3, per2 = a.gh[2] * a.gw[2] * 3;
+    const int per0 = a.gh[0] * a.gw[0] * 3, per1 = a.n_heads > 1 ? a.gh[1] * a.gw[1] * 3 : 0, per2 = a.n_heads > 2 ? a.gh[2] * a.gw[2] * 3 : 0;
     const int total = per0 + per1 + per2;
     const int stride_a = 5 + a.nc;
     if (tid == 0) L.running = 0;
@@ -245,7 +305,7 @@ __global__ __launch_bounds__(DET_TS) void k_yolo_detect_split(YoloArgs a, int* _
     __shared__ DetLds L;
     __shared__ int s_last;
     const int run = blockIdx.x, runs = gridDim.x, img = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per0 = a.gh[0] * a.gw[0] * 3, per1 = a.gh[1] * a.gw[1] * 3, per2 = a.gh[2] * a.gw[2] * 3;
+    const int per0 = a.gh[0] * a.gw[0] * 3, per1 = a.n_heads > 1 ? a.gh[1] * a.gw[1] * 3 : 0, per2 = a.n_heads > 2 ? a.gh[2] * a.gw[2] * 3 : 0;
     const int total = per0 + per1 + per2;
     const int stride_a = 5 + a.nc;
     const int base = run * DET_TS * DET_K;
@@ -338,43 +398,49 @@ __global__ __launch_bounds__(DET_TS) void k_yolo_detect_split(YoloArgs a, int* _
     if (lane == 0) { a.count[img] = kept; a.count[a.n_img + img] = nfound; }
 }
 
-static int det_fill_args(YoloArgs& a, int n_img, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w, const int32_t* chan_stride,
+static int det_fill_args(YoloArgs& a, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w, const int32_t* chan_stride,
                          const float* anchors, int net_w, int net_h, int num_classes, int class_id, float score_thresh, float nms_thresh,
                          int frame_w, int frame_h, int max_det, float* dev_out, int32_t* dev_count) {
     if (n_img < 0 || !heads || !grid_h || !grid_w || !chan_stride || !anchors || !dev_out || !dev_count || num_classes <= 0 ||
-        class_id < 0 || class_id >= num_classes || max_det <= 0 || net_w <= 0 || net_h <= 0)
+        class_id < 0 || class_id >= num_classes || max_det <= 0 || net_w <= 0 || net_h <= 0 || n_heads < 1 || n_heads > 3)
         return PAM_E_ARG;
+    long long total = 0;
     for (int h = 0; h < 3; ++h) {
+        a.head[h] = nullptr; a.gh[h] = 0; a.gw[h] = 0; a.cs[h] = 0;
+        if (h >= n_heads) continue;
         if (!heads[h] || grid_h[h] <= 0 || grid_w[h] <= 0 || chan_stride[h] < 3 * (5 + num_classes)) return PAM_E_ARG;
         a.head[h] = (const uint16_t*)heads[h]; a.gh[h] = grid_h[h]; a.gw[h] = grid_w[h]; a.cs[h] = chan_stride[h];
+        total += (long long)grid_h[h] * grid_w[h] * 3;
     }
-    for (int i = 0; i < 18; ++i) a.anchors[i] = anchors[i];
+    if (total >= (1ll << 30)) return PAM_E_ARG;         // candidate numbers are 32-bit
+    for (int i = 0; i < 18; ++i) a.anchors[i] = i < 6 * n_heads ? anchors[i] : 0.0f;
+    a.n_heads = n_heads;
     a.net_w = net_w; a.net_h = net_h; a.nc = num_classes; a.cls = class_id; a.score_thresh = score_thresh; a.nms_thresh = nms_thresh;
     a.frame_w = frame_w; a.frame_h = frame_h; a.max_det = max_det; a.out = dev_out; a.count = dev_count; a.n_img = n_img;
     return PAM_OK;
 }
-static int det_runs(const int32_t* grid_h, const int32_t* grid_w) {
+static int det_runs(int n_heads, const int32_t* grid_h, const int32_t* grid_w) {
     long long total = 0;
-    for (int h = 0; h < 3; ++h) total += (long long)grid_h[h] * grid_w[h] * 3;
+    for (int h = 0; h < n_heads; ++h) total += (long long)grid_h[h] * grid_w[h] * 3;
     return (int)((total + DET_TS * DET_K - 1) / (DET_TS * DET_K));
 }
-extern "C" long long pam_yolo_detect_workspace_bytes(int n_img, const int32_t* grid_h, const int32_t* grid_w) {
-    if (n_img < 0 || !grid_h || !grid_w) return -1;
-    for (int h = 0; h < 3; ++h) if (grid_h[h] <= 0 || grid_w[h] <= 0) return -1;
-    const int runs = det_runs(grid_h, grid_w);
+extern "C" long long pam_yolo_detect_heads_workspace_bytes(int n_img, int n_heads, const int32_t* grid_h, const int32_t* grid_w) {
+    if (n_img < 0 || n_heads < 1 || n_heads > 3 || !grid_h || !grid_w) return -1;
+    for (int h = 0; h < n_heads; ++h) if (grid_h[h] <= 0 || grid_w[h] <= 0) return -1;
+    const int runs = det_runs(n_heads, grid_h, grid_w);
     return (long long)(det_ws_head_bytes(n_img, runs) + (size_t)n_img * runs * sizeof(DetSeg));
 }
-extern "C" int pam_yolo_detect_ws(void* stream, int n_img, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
-                                  const int32_t* chan_stride, const float* anchors, int net_w, int net_h, int num_classes,
-                                  int class_id, float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det,
-                                  float* dev_out, int32_t* dev_count, void* dev_workspace, long long workspace_bytes) {
+extern "C" int pam_yolo_detect_heads_ws(void* stream, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
+                                        const int32_t* chan_stride, const float* anchors, int net_w, int net_h, int num_classes,
+                                        int class_id, float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det,
+                                        float* dev_out, int32_t* dev_count, void* dev_workspace, long long workspace_bytes) {
     YoloArgs a;
-    const int rc = det_fill_args(a, n_img, heads, grid_h, grid_w, chan_stride, anchors, net_w, net_h, num_classes, class_id, score_thresh,
+    const int rc = det_fill_args(a, n_img, n_heads, heads, grid_h, grid_w, chan_stride, anchors, net_w, net_h, num_classes, class_id, score_thresh,
                                  nms_thresh, frame_w, frame_h, max_det, dev_out, dev_count);
     if (rc != PAM_OK) return rc;
     if (n_img == 0) return PAM_OK;
-    if (!dev_workspace || workspace_bytes < pam_yolo_detect_workspace_bytes(n_img, grid_h, grid_w) || ((uintptr_t)dev_workspace & 15)) return PAM_E_ARG;
-    const int runs = det_runs(grid_h, grid_w);
+    if (!dev_workspace || workspace_bytes < pam_yolo_detect_heads_workspace_bytes(n_img, n_heads, grid_h, grid_w) || ((uintptr_t)dev_workspace & 15)) return PAM_E_ARG;
+    const int runs = det_runs(n_heads, grid_h, grid_w);
     int* tickets = (int*)dev_workspace;
     int* counts = tickets + n_img;
     DetSeg* segs = (DetSeg*)((char*)dev_workspace + det_ws_head_bytes(n_img, runs));
@@ -382,15 +448,34 @@ extern "C" int pam_yolo_detect_ws(void* stream, int n_img, const void* const* he
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
 }
 
-extern "C" int pam_yolo_detect(void* stream, int n_img, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
-                               const int32_t* chan_stride, const float* anchors, int net_w, int net_h, int num_classes,
-                               int class_id, float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det,
-                               float* dev_out, int32_t* dev_count) {
+extern "C" int pam_yolo_detect_heads(void* stream, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
+                                     const int32_t* chan_stride, const float* anchors, int net_w, int net_h, int num_classes,
+                                     int class_id, float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det,
+                                     float* dev_out, int32_t* dev_count) {
     YoloArgs a;
-    const int rc = det_fill_args(a, n_img, heads, grid_h, grid_w, chan_stride, anchors, net_w, net_h, num_classes, class_id, score_thresh,
+    const int rc = det_fill_args(a, n_img, n_heads, heads, grid_h, grid_w, chan_stride, anchors, net_w, net_h, num_classes, class_id, score_thresh,
                                  nms_thresh, frame_w, frame_h, max_det, dev_out, dev_count);
     if (rc != PAM_OK) return rc;
     if (n_img == 0) return PAM_OK;
     hipLaunchKernelGGL(k_yolo_detect, dim3(n_img), dim3(DET_T), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+}
+
+// the three-head forms: the entry points above with n_heads = 3
+extern "C" long long pam_yolo_detect_workspace_bytes(int n_img, const int32_t* grid_h, const int32_t* grid_w) {
+    return pam_yolo_detect_heads_workspace_bytes(n_img, 3, grid_h, grid_w);
+}
+extern "C" int pam_yolo_detect_ws(void* stream, int n_img, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
+                                  const int32_t* chan_stride, const float* anchors, int net_w, int net_h, int num_classes,
+                                  int class_id, float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det,
+                                  float* dev_out, int32_t* dev_count, void* dev_workspace, long long workspace_bytes) {
+    return pam_yolo_detect_heads_ws(stream, n_img, 3, heads, grid_h, grid_w, chan_stride, anchors, net_w, net_h, num_classes, class_id, score_thresh,
+                                    nms_thresh, frame_w, frame_h, max_det, dev_out, dev_count, dev_workspace, workspace_bytes);
+}
+extern "C" int pam_yolo_detect(void* stream, int n_img, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
+                               const int32_t* chan_stride, const float* anchors, int net_w, int net_h, int num_classes,
+                               int class_id, float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det,
+                               float* dev_out, int32_t* dev_count) {
+    return pam_yolo_detect_heads(stream, n_img, 3, heads, grid_h, grid_w, chan_stride, anchors, net_w, net_h, num_classes, class_id, score_thresh,
+                                 nms_thresh, frame_w, frame_h, max_det, dev_out, dev_count);
 }

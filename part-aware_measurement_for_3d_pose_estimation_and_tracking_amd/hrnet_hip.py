@@ -730,6 +730,24 @@ class ConvEngine(object):
             raise _lib.PamError('pam_upsample_concat_nhwc_bf16 failed (%d)' % rc)
         return y
 
+    def maxpool(self, x, size, stride):
+        """Darknet [maxpool]: pad = size - 1, out = (in + pad - size) / stride + 1, windows start at -pad / 2, taps outside the image
+        do not take part (size 2 or 3, stride 1 or 2)."""
+        n, c, h, w = x.shape
+        ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+        y = self._new(n, c, ho, wo, x.device)
+        if self.count is not None:
+            self.count['bytes'] += 2 * (x.numel() + y.numel())
+            self.count['launches'] += 1
+        if x.device.type == 'meta':
+            return y
+        assert x.is_contiguous(memory_format=torch.channels_last), (x.shape, x.stride())
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        rc = self.lib.pam_maxpool_nhwc_bf16(C.c_void_p(st), C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), n, h, w, c, int(size), int(stride))
+        if rc != 0:
+            raise _lib.PamError('pam_maxpool_nhwc_bf16 failed (%d) for %s size %d stride %d' % (rc, tuple(x.shape), size, stride))
+        return y
+
 
 class HipHRNet(ConvEngine):
     multi_stream = False

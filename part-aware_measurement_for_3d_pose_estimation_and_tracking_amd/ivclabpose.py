@@ -85,12 +85,15 @@ class ivclabpose(object):
             d = self.person_detector
             cfg, weight, names = _cfg(d, 'CFG'), _cfg(d, 'WEIGHT'), _cfg(d, 'CLASS_NAMES')
             # the reference's cfg / weight / names files are not distributed with it: a missing cfg or names file means
-            # the standard YOLOv3-416 COCO layout (person = class 0), missing weights mean a seeded random network
+            # the standard YOLOv3-416 COCO layout (person = class 0), missing weights mean a seeded random network.
+            # ARCH (optional key, not in the reference): 'yolov3' | 'yolov3-tiny', the standard network built when the cfg file is missing
+            arch = (d.get('ARCH') if isinstance(d, dict) else getattr(d, 'ARCH', None)) or 'yolov3'
             self.bbox_detector = YOLOv3(cfg if cfg and os.path.exists(cfg) else None,
                                         weight if weight and os.path.exists(weight) else None,
                                         names if names and os.path.exists(names) else None,
                                         score_thresh=_cfg(d, 'SCORE_THRESH'), nms_thresh=_cfg(d, 'NMS_THRESH'),
-                                        use_cuda=True, device=device, max_det=max_dets)   # best max_dets boxes per view: the tracker's capacity
+                                        use_cuda=True, device=device, max_det=max_dets,   # best max_dets boxes per view: the tracker's capacity
+                                        arch=arch)
             print("Person Detector : ", _cfg(d, 'NAME'), '(weights: %s)' % self.bbox_detector.weights)
         else:
             raise NotImplementedError('person detector %r' % _cfg(self.person_detector, 'NAME'))

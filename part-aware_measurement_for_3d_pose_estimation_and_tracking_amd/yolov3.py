@@ -4,8 +4,9 @@ entries are x1, y1, x2, y2, score in frame pixels).
 
 The backend itself, its cfg and its weights are not part of the reference tree, so this module follows the public Darknet
 YOLOv3 definition (Redmon & Farhadi 2018: Darknet-53 backbone, three ``yolo`` heads, 9 anchors) -- parity unpinned, like
-HRNet.  It understands Darknet ``.cfg`` text (convolutional / shortcut / route / upsample / yolo) and Darknet ``.weights``
-files; with no cfg it builds the standard 416 x 416, 80-class network, with no weights a seeded random one.
+HRNet.  It understands Darknet ``.cfg`` text (convolutional / shortcut / route / upsample / maxpool / yolo) and Darknet ``.weights``
+files; with no cfg it builds the standard 416 x 416, 80-class network (``arch='yolov3-tiny'``: the standard YOLOv3-tiny, 13
+convolutions, 6 max-pools, two heads), with no weights a seeded random one.
 
 Two executions of the same network: ``Darknet`` (plain PyTorch float32; the test reference) and ``HipDarknet`` (product
 path: every convolution on the MFMA kernels of csrc/pam_conv.hip with BN folded, leaky-ReLU and the shortcut add fused into
@@ -62,6 +63,39 @@ def default_cfg(width=416, height=416, classes=80):
     return '\n'.join(out)
 
 
+TINY_ANCHORS = [(10, 14), (23, 27), (37, 58), (81, 82), (135, 169), (344, 319)]
+
+
+def tiny_cfg(width=416, height=416, classes=80):
+    """The standard yolov3-tiny.cfg (24 layers: 13 convolutions, 6 max-pools, one upsample + route, two heads), generated like default_cfg."""
+    out = ['[net]', 'width=%d' % width, 'height=%d' % height, 'channels=3', '']
+
+    def conv(filters, size, bn=1, act='leaky'):
+        out.extend(['[convolutional]'] + (['batch_normalize=1'] if bn else []) +
+                   ['filters=%d' % filters, 'size=%d' % size, 'stride=1', 'pad=1', 'activation=%s' % act, ''])
+
+    def yolo(mask):
+        out.extend(['[yolo]', 'mask = %s' % ','.join(str(m) for m in mask),
+                    'anchors = %s' % ',  '.join('%d,%d' % a for a in TINY_ANCHORS), 'classes=%d' % classes, 'num=6', ''])
+
+    for k, f in enumerate((16, 32, 64, 128, 256, 512)):
+        conv(f, 3)
+        out.extend(['[maxpool]', 'size=2', 'stride=%d' % (2 if k < 5 else 1), ''])
+    conv(1024, 3); conv(256, 1); conv(512, 3)
+    conv(3 * (5 + classes), 1, bn=0, act='linear')
+    yolo((3, 4, 5))
+    out.extend(['[route]', 'layers = -4', ''])
+    conv(128, 1)
+    out.extend(['[upsample]', 'stride=2', '', '[route]', 'layers = -1, 8', ''])
+    conv(256, 3)
+    conv(3 * (5 + classes), 1, bn=0, act='linear')
+    yolo((0, 1, 2))
+    return '\n'.join(out)
+
+
+ARCHS = {'yolov3': default_cfg, 'yolov3-tiny': tiny_cfg}
+
+
 def parse_cfg(text):
     """Darknet cfg text -> (net options, [layer dicts]); values stay strings except the ones the network needs."""
     blocks = []
@@ -90,13 +124,19 @@ def parse_cfg(text):
             b['layers'] = [int(x) for x in b['layers'].split(',')]
         elif t == 'upsample':
             b['stride'] = int(b.get('stride', 2))
+        elif t == 'maxpool':
+            if b is layers[0]:                  # a pool needs a layer to pool: every network here starts with a convolution of the frame
+                raise NotImplementedError('[maxpool] as the first layer is not supported (a [convolutional] must come before it)')
+            b['size'], b['stride'] = int(b.get('size', 1)), int(b.get('stride', 1))
+            if int(b.get('padding', b['size'] - 1)) != b['size'] - 1:
+                raise NotImplementedError('[maxpool] padding=%s: only Darknet\'s default, size - 1, is supported' % b['padding'])
         elif t == 'yolo':
             b['mask'] = [int(x) for x in b['mask'].split(',')]
             a = [float(x) for x in b['anchors'].split(',')]
             b['anchors'] = [(a[i], a[i + 1]) for i in range(0, len(a), 2)]
             b['classes'] = int(b['classes'])
         else:
-            raise NotImplementedError('cfg layer [%s] is not supported (convolutional/shortcut/route/upsample/yolo only)' % t)
+            raise NotImplementedError('cfg layer [%s] is not supported (convolutional/shortcut/route/upsample/maxpool/yolo only)' % t)
     return net, layers
 
 
@@ -126,7 +166,7 @@ class Darknet(nn.Module):
                 c_out = chans[i - 1]
             elif t == 'route':
                 c_out = sum(chans[l if l >= 0 else i + l] for l in b['layers'])
-            else:                       # upsample, yolo
+            else:                       # upsample, maxpool, yolo
                 c_out = chans[i - 1]
             mods.append(m)
             chans.append(c_out)
@@ -153,6 +193,8 @@ class Darknet(nn.Module):
                 x = xs[0] if len(xs) == 1 else torch.cat(xs, 1)
             elif t == 'upsample':
                 x = F.interpolate(x, scale_factor=b['stride'], mode='nearest')
+            elif t == 'maxpool':
+                x = darknet_maxpool(x, b['size'], b['stride'])
             else:
                 heads.append(x)
             outs.append(x)
@@ -213,6 +255,14 @@ class Darknet(nn.Module):
         return self
 
 
+def darknet_maxpool(x, size, stride):
+    """Darknet's [maxpool] (src/maxpool_layer.c) on (N, C, H, W): pad = size - 1, out = (in + pad - size) / stride + 1, the window of
+    output o starts at o * stride - pad / 2, taps outside the image do not take part."""
+    pad = size - 1
+    lo, hi = pad // 2, pad - pad // 2
+    return F.max_pool2d(F.pad(x, (lo, hi, lo, hi), value=float('-inf')), size, stride)
+
+
 def fold_conv(m):
     """(conv [, bn]) -> one nn.Conv2d with bias (inference form)."""
     conv = m.conv
@@ -234,8 +284,9 @@ def _round_channels(c):
 
 class HipDarknet(ConvEngine):
     """The cfg's layer list compiled to kernel launches.  Channel counts the MFMA kernels cannot take (3 -> 8 on the input,
-    32 / 255 -> 64 / 256 on outputs) are zero-padded at the end of the channel axis; padded channels stay exactly zero
-    through leaky-ReLU and shortcut adds, and the head decode reads the real ones through its channel stride."""
+    32 / 255 -> 64 / 256 on outputs; YOLOv3-tiny's 16-filter first layer -> 32 on k_conv_stem) are zero-padded at the end of the
+    channel axis; padded channels stay exactly zero through leaky-ReLU, shortcut adds and max-pools, and the head decode reads the
+    real ones through its channel stride."""
 
     def __init__(self, model, device):
         self.lib = _lib.load()
@@ -259,9 +310,10 @@ class HipDarknet(ConvEngine):
             b, t = layers[i], layers[i]['type']
             if t == 'convolutional':
                 cin_pad = c_pad if i == 0 else padded[i - 1]
-                stem = i == 0 and cin_pad == 8 and b['size'] == 3 and b['pad'] and b['stride'] in (1, 2) and b['filters'] in (32, 64)
+                stem = i == 0 and cin_pad == 8 and b['size'] == 3 and b['pad'] and b['stride'] in (1, 2) and b['filters'] in (16, 32, 64)
+                # k_conv_stem writes 32 or 64 real channels; 16 filters (YOLOv3-tiny) run as its 32-channel form with 16 zero filters
                 op = PackedConv(fold_conv(model.mods[i]), device, pad_cin_to=cin_pad,
-                                pad_cout_to=None if stem else _round_channels(b['filters']))      # k_conv_stem writes 32 real channels
+                                pad_cout_to=(32 if b['filters'] == 16 else None) if stem else _round_channels(b['filters']))
                 nxt = layers[i + 1] if i + 1 < n else None
                 fuse = (nxt is not None and nxt['type'] == 'shortcut' and nxt['activation'] == 'linear' and used_by[i] == [] and
                         b['activation'] in ('leaky', 'linear'))
@@ -294,6 +346,12 @@ class HipDarknet(ConvEngine):
                 real += [real[i - 1], real[i - 1] + real[skip]]; padded += [padded[i - 1], padded[i - 1] + padded[skip]]
                 i += 2
                 continue
+            elif t == 'maxpool':
+                if b['size'] not in (2, 3) or b['stride'] not in (1, 2):
+                    raise NotImplementedError('[maxpool] size=%d stride=%d: the max-pool kernel takes size 2 or 3 and stride 1 or 2' %
+                                              (b['size'], b['stride']))
+                self.plan.append(('pool', i, i - 1, b['size'], b['stride']))
+                real.append(real[i - 1]); padded.append(padded[i - 1])
             else:                                           # yolo
                 self.plan.append(('head', i, i - 1))
                 real.append(real[i - 1]); padded.append(padded[i - 1])
@@ -323,6 +381,8 @@ class HipDarknet(ConvEngine):
             return self.upsample_add(outs[step[2]], [outs[step[3]]], [0], relu=False)
         if kind == 'upcat':
             return self.upsample_concat(outs[step[2]], outs[step[3]])
+        if kind == 'pool':
+            return self.maxpool(outs[step[2]], step[3], step[4])
         return outs[step[2]]                                # alias, head
 
     def unfused(self, step, x):
@@ -337,14 +397,17 @@ class YOLOv3(object):
     array per image, rows (x1, y1, x2, y2, score) of the ``person`` class in that image's pixels, best score first."""
 
     def __init__(self, cfgfile=None, weightfile=None, namesfile=None, score_thresh=0.7, nms_thresh=0.45, use_cuda=True,
-                 device=0, max_det=64, seed=0, use_graph=True):
+                 device=0, max_det=64, seed=0, use_graph=True, arch='yolov3'):
+        """arch: 'yolov3' | 'yolov3-tiny', the standard network built when cfgfile is None (a cfg file always decides the architecture)."""
         if not use_cuda or not torch.cuda.is_available():
             raise RuntimeError('YOLOv3 needs a GPU (HIP kernels only; no CPU fallback)')
         self.lib = _lib.load()
         self.device = torch.device('cuda:%d' % device)
         if cfgfile is not None and not os.path.exists(cfgfile):
             raise FileNotFoundError(cfgfile)
-        model = Darknet(open(cfgfile).read() if cfgfile is not None else None)
+        if cfgfile is None and arch not in ARCHS:
+            raise ValueError('arch %r: expected one of %s' % (arch, ', '.join(sorted(ARCHS))))
+        model = Darknet(open(cfgfile).read() if cfgfile is not None else ARCHS[arch]())
         if weightfile is not None:
             model.load_darknet_weights(weightfile)
             self.weights = weightfile
@@ -354,10 +417,11 @@ class YOLOv3(object):
         model.eval()
         self.size = (model.height, model.width)
         yl = model.yolo_layers()
-        if len(yl) != 3:
-            raise NotImplementedError('expected three [yolo] heads, cfg has %d' % len(yl))
+        if not 1 <= len(yl) <= 3 or any(len(y['mask']) != 3 for y in yl):
+            raise NotImplementedError('expected one to three [yolo] heads of three masked anchors each, cfg has %d (masks %s)' %
+                                      (len(yl), [y['mask'] for y in yl]))
         self.num_classes = yl[0]['classes']
-        self.anchors = np.array([[yl[h]['anchors'][m] for m in yl[h]['mask']] for h in range(3)], dtype=np.float32)   # (3,3,2)
+        self.anchors = np.array([[y['anchors'][m] for m in y['mask']] for y in yl], dtype=np.float32)   # (n_heads, 3, 2)
         self.class_id = 0
         if namesfile is not None:
             names = [l.strip() for l in open(namesfile) if l.strip()]
@@ -377,21 +441,22 @@ class YOLOv3(object):
         if rc != 0:
             raise _lib.PamError('pam_resize_frames failed: %d' % rc)
         heads = self.net.forward(x8)
-        hp = (C.c_void_p * 3)(*[C.c_void_p(h.data_ptr()) for h in heads])
-        gh = (C.c_int32 * 3)(*[h.shape[2] for h in heads]); gw = (C.c_int32 * 3)(*[h.shape[3] for h in heads])
-        cs = (C.c_int32 * 3)(*[h.shape[1] for h in heads])
+        nh = len(heads)
+        hp = (C.c_void_p * nh)(*[C.c_void_p(h.data_ptr()) for h in heads])
+        gh = (C.c_int32 * nh)(*[h.shape[2] for h in heads]); gw = (C.c_int32 * nh)(*[h.shape[3] for h in heads])
+        cs = (C.c_int32 * nh)(*[h.shape[1] for h in heads])
         an = np.ascontiguousarray(self.anchors.reshape(-1))
         # decode + NMS with the scoring pass over several workgroups per image; the workspace belongs to (this detector, n): replays of one
         # detector run one after the other on its stream
-        need = int(self.lib.pam_yolo_detect_workspace_bytes(n, gh, gw))
+        need = int(self.lib.pam_yolo_detect_heads_workspace_bytes(n, nh, gh, gw))
         ws = self._det_ws.get(n)
         if ws is None or ws.numel() < need:
             ws = self._det_ws[n] = torch.zeros(need, dtype=torch.uint8, device=self.device)
-        rc = self.lib.pam_yolo_detect_ws(C.c_void_p(st), n, hp, gh, gw, cs, an.ctypes.data_as(C.c_void_p), W, H, self.num_classes,
-                                         self.class_id, self.score_thresh, self.nms_thresh, fw, fh, self.max_det,
-                                         C.c_void_p(boxes.data_ptr()), C.c_void_p(count.data_ptr()), C.c_void_p(ws.data_ptr()), need)
+        rc = self.lib.pam_yolo_detect_heads_ws(C.c_void_p(st), n, nh, hp, gh, gw, cs, an.ctypes.data_as(C.c_void_p), W, H, self.num_classes,
+                                               self.class_id, self.score_thresh, self.nms_thresh, fw, fh, self.max_det,
+                                               C.c_void_p(boxes.data_ptr()), C.c_void_p(count.data_ptr()), C.c_void_p(ws.data_ptr()), need)
         if rc != 0:
-            raise _lib.PamError('pam_yolo_detect_ws failed: %d' % rc)
+            raise _lib.PamError('pam_yolo_detect_heads_ws failed: %d' % rc)
         return heads
 
     def detect_dev(self, frames):
