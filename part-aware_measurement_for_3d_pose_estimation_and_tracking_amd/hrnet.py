@@ -189,7 +189,7 @@ def algorithmic_work(n_crops, resolution=(384, 288), config=None):
     input + weights + bias + output, every fuse-layer sum as base + terms + output.  Un-fusing a block cannot raise this number.
     ``flops``; ``launches`` and ``bytes_as_executed`` (per launch: in + weights + bias [+ residual] + out) of the given executor
     configuration (HipHRNet.CONFIGS; None = the default)."""
-    from .hrnet_hip import HipHRNet
+    from .hrnet_hip import HipHRNet, TileCfg
 
     from . import _lib as _real
 
@@ -199,7 +199,7 @@ def algorithmic_work(n_crops, resolution=(384, 288), config=None):
                 return getattr(_real.load(), name)
             return lambda *a, **k: 0
     eng = HipHRNet.__new__(HipHRNet)
-    eng.lib = _MetaLib(); eng.device = torch.device('meta'); eng.tile_cfg = -1; eng.multi_stream = False
+    eng.lib = _MetaLib(); eng.device = torch.device('meta'); eng.tile_cfg = TileCfg.AUTO; eng.multi_stream = False
     model = fold_batchnorm(PoseHighResolutionNet())
     model.final_layer = nn.Identity()
     HipHRNet._pack(eng, model, torch.device('meta'))

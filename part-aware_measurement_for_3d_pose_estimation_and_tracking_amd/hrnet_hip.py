@@ -1,756 +1,21 @@
-"""HRNet-W48 / -W32 conv stack on the hand-written MFMA kernels of csrc/pam_conv.hip (no MIOpen in the loop).
+"""HRNet-W48 / -W32 and PoseResNet conv stacks on the hand-written MFMA kernels of csrc/ (no MIOpen in the loop): the executors.
 
-The folded (conv + bias) PyTorch module of hrnet.py is walked once into packed weights; ``forward`` then issues one
-``pam_conv2d_nhwc_bf16`` per convolution -- bias, residual add and ReLU fused into its epilogue -- plus one
-``pam_upsample_add_nhwc_bf16`` per fuse-layer output that has coarser inputs.  Activations are NHWC bf16 torch tensors
-(channels-last); torch is used for memory and the stream only.  The whole forward is hipGraph-capturable."""
-import contextlib
+The folded (conv + bias) PyTorch module of hrnet.py / poseresnet.py is walked once into packed weights (packing.py); a forward then
+issues the launches of engine.ConvEngine -- bias, residual add and ReLU fused into the convolutions' epilogues -- in the executor's
+schedule: HipHRNet runs the branches of an HR module on side streams and orders them by stream events or device-side flags,
+HipPoseResNet is one dependent chain.  The whole forward is hipGraph-capturable."""
 import ctypes as C
 
 import torch
-import torch.nn as nn
 
 from . import _lib
-
-
-class PackedConv(object):
-    def __init__(self, conv, device, pad_cin_to=None, pad_cout_to=None):
-        """Zero-padding input channels (pad_cin_to) or output channels (pad_cout_to: zero filters, zero bias) leaves the real
-        channels unchanged; the detector uses it for Darknet's 3-, 32- and 255-channel layers."""
-        w = conv.weight.detach().float()
-        b = conv.bias.detach().float() if conv.bias is not None else torch.zeros(w.shape[0])
-        cout, cin, kh, kw = w.shape
-        if pad_cin_to is not None and cin < pad_cin_to:
-            w = torch.cat([w, torch.zeros(cout, pad_cin_to - cin, kh, kw)], dim=1)
-            cin = pad_cin_to
-        if pad_cout_to is not None and cout < pad_cout_to:
-            w = torch.cat([w, torch.zeros(pad_cout_to - cout, cin, kh, kw)], dim=0)
-            b = torch.cat([b, torch.zeros(pad_cout_to - cout)])
-            cout = pad_cout_to
-        stem = cin == 8 and cout in (32, 64) and kh == 3 and kw == 3 and conv.stride[0] in (1, 2) and conv.padding[0] == 1
-        # widths that are multiples of 32 only (HRNet-W32: 32, 224): the implicit GEMM with 32-channel slabs, k_conv3x3<32 | 256, 2>
-        assert cin % 8 == 0 and (cout % 48 == 0 or cout % 64 == 0 or cout % 32 == 0 or stem), (cin, cout)
-        ktot = kh * kw * cin
-        kpad = (ktot + 63) // 64 * 64
-        wp = torch.zeros((cout, kpad), dtype=torch.float32)
-        wp[:, :ktot] = w.permute(0, 2, 3, 1).reshape(cout, ktot)          # k = (ky, kx, cin), cin fastest
-        self.w = wp.to(torch.bfloat16).to(device).contiguous()
-        self.bias = b.to(device).contiguous()
-        self.cin, self.cout, self.kh, self.kw = cin, cout, kh, kw
-        self.stride, self.pad = conv.stride[0], conv.padding[0]
-        # per-chunk LDS images for k_conv3x3, built lazily per slab width (the kernel picks the slab from the layer's H x W)
-        self._w_ohwi = w.permute(0, 2, 3, 1).contiguous() if (kh == 3 and kw == 3 and self.stride == 1 and self.pad == 1 and
-                                                              (cin in (48, 64, 96, 128, 192, 256, 384, 512) or
-                                                               (cin == 32 and cout == 32))) else None
-        self._images = {}
-        self._device = device
-        # stem convolution (8 -> 32 / 64 channels, 3x3, stride 1 / 2): the MFMA A fragments of k_conv_stem, [n-tile j][ky][lane][8]:
-        # lane l holds, for output channel 4*nt*((l & 15) >> 2) + 4*j + (l & 3), the 8 input channels of tap (ky, kx = l >> 4)
-        self._stem = None
-        if stem:
-            nt = cout // 16
-            lanes = torch.arange(64)
-            q, kx = lanes & 15, lanes >> 4
-            frag = torch.zeros((nt, 3, 64, 8), dtype=torch.float32)
-            for j in range(nt):
-                ch = 4 * nt * (q >> 2) + 4 * j + (q & 3)
-                for ky in range(3):
-                    sel = kx < 3
-                    frag[j, ky, sel] = w[ch[sel], :, ky, kx[sel]]
-            self._stem = frag.to(torch.bfloat16).to(device).contiguous()
-
-    @staticmethod
-    def merged(convs, device):
-        """One convolution computing several same-shaped convolutions of the same input: weights / biases concatenated along
-        the output channels, in the given order."""
-        c0 = convs[0]
-        assert all(c.kernel_size == c0.kernel_size and c.stride == c0.stride and c.padding == c0.padding and
-                   c.in_channels == c0.in_channels for c in convs)
-        m = nn.Conv2d(c0.in_channels, sum(c.out_channels for c in convs), c0.kernel_size, c0.stride, c0.padding, bias=True)
-        with torch.no_grad():
-            m.weight.copy_(torch.cat([c.weight.detach().float() for c in convs], 0))
-            m.bias.copy_(torch.cat([(c.bias.detach().float() if c.bias is not None else torch.zeros(c.out_channels)) for c in convs]))
-        return PackedConv(m, device)
-
-    layout_lib = None           # tools/ab_conv_defs.py: a build variant whose layout functions decide the image (default: the library)
-
-    def image(self, h, w, classic=False, c96_slab=0):
-        """Weight image of this layer at input h x w for the rows-in-LDS kernels (layouts: include/pam.h): the classic per-chunk image
-        [cout/BN][cin/CK][BN][pitch/2] (row = 9 taps x CK channels + pad), or -- where pam_conv3x3_layout() says so and the caller does
-        not force the classic kernel -- the streamed kernel's [cout/BN][cin/32][9][BN][4][8] with swizzled 16-byte pieces."""
-        if self._stem is not None:
-            return self._stem
-        if self._w_ohwi is None:
-            return None
-        lib = self.layout_lib or _lib.load()
-        bn_s = 0 if classic else lib.pam_conv3x3_layout_ex(int(h), int(w), self.cin, self.cout, int(c96_slab))     # > 0: streamed kernel, with this slab width
-        streamed = bn_s > 0
-        bn = bn_s if streamed else lib.pam_conv3x3_slab(int(h), int(w), self.cin, self.cout)
-        if self.cout % bn != 0:
-            return None                                  # no whole number of slabs: the generic kernel takes this layer
-        self.last_streamed = streamed                    # layout of the image this call returns (conv() states it to the library)
-        self.last_c96 = bn if (streamed and self.cin == 96 and self.cout == 96) else 0
-        img = self._images.get((bn, streamed))
-        if img is None:
-            cin, cout = self.cin, self.cout
-            # row j*16 + q of a slab holds channel 4*ntw*(q >> 2) + 4*j + (q & 3): with the weights as the MFMA A operand a
-            # lane's accumulators are then 4*ntw contiguous output channels (16-byte epilogue accesses, see k_conv3x3)
-            ntw = bn // 16
-            perm = [4 * ntw * (q >> 2) + 4 * j + (q & 3) for j in range(ntw) for q in range(16)]
-            if streamed:
-                w5 = self._w_ohwi.reshape(cout // bn, bn, 9, cin // 32, 32)[:, perm]       # [slab][row][tap][chunk][c]
-                t = w5.permute(0, 3, 2, 1, 4).reshape(cout // bn, cin // 32, 9, bn, 4, 8)  # [slab][chunk][tap][row][piece][8]
-                rows = torch.arange(bn)
-                src = torch.arange(4)[None, :] ^ ((rows >> 1) & 2)[:, None]                # physical piece p of row r holds logical piece p ^ ((r >> 1) & 2)
-                t = torch.gather(t, 4, src[None, None, None, :, :, None].expand(t.shape))
-            else:
-                ck = 48 if cin == 48 else (64 if cin >= 192 else 32)
-                pitch = {48: 864, 32: 608, 64: 1184}[ck] // 2
-                w5 = self._w_ohwi.reshape(cout // bn, bn, 9, cin // ck, ck)[:, perm]       # [slab][co][tap][chunk][c]
-                t = torch.zeros((cout // bn, cin // ck, bn, pitch), dtype=torch.float32)
-                t[:, :, :, :9 * ck] = w5.permute(0, 3, 1, 2, 4).reshape(cout // bn, cin // ck, bn, 9 * ck)
-            img = t.to(torch.bfloat16).to(self._device).contiguous()
-            self._images[(bn, streamed)] = img
-        return img
-
-
-def down48_image(op):
-    """Weight image of a 3x3 stride-2 convolution with 48 input channels for ``pam_conv3x3s2_c48_nhwc_bf16`` (csrc/pam_down.hip; layout:
-    include/pam.h): per 48-channel slab of the output [14 k-steps][48 rows][4 pieces][8] -- K = (tap, cin) flattened and zero-padded to
-    14 * 32, rows permuted and 16-byte pieces swizzled exactly as one convolution of PackedBlock's C = 48 image."""
-    assert op.cin == 48 and op.kh == 3 and op.kw == 3 and op.cout % 48 == 0
-    img = getattr(op, '_down48', None)
-    if img is None:
-        ns, nstep = op.cout // 48, 14
-        rows = torch.arange(48)
-        j, qq, r = rows // 16, (rows % 16) >> 2, rows & 3
-        chan = torch.where(j < 2, 8 * qq + 4 * j + r, 32 + 4 * qq + r)
-        src = torch.arange(4)[None, :] ^ torch.tensor([0, 2, 3, 1])[qq][:, None]
-        wk = torch.zeros((op.cout, nstep * 32), dtype=torch.float32)
-        wk[:, :432] = op.w[:, :432].float().cpu()                                           # [cout][k = tap * 48 + cin]
-        wk = wk.reshape(ns, 48, nstep, 4, 8)[:, chan]                                        # [slab][row][k-step][piece][8]
-        wk = torch.gather(wk, 3, src[None, :, None, :, None].expand(ns, 48, nstep, 4, 8)).permute(0, 2, 1, 3, 4)
-        img = op._down48 = wk.to(torch.bfloat16).to(op._device).contiguous()
-        assert img.numel() * 2 == ns * 43008
-    return img
-
-
-def streamed_image(w_ohwi, bn, device):
-    """The streamed 3x3 kernels' weight image (layout: include/pam.h): [cout / bn][cin / 32][9 taps][bn rows][4 pieces][8] -- row j*16 + q
-    of a slab = its channel 4*ntw*(q >> 2) + 4*j + (q & 3) (a lane's accumulators are then 4*ntw contiguous output channels), physical
-    16-byte piece p of row r = the chunk's input channels 8*(p ^ ((r >> 1) & 2)) .. + 7 (LDS bank swizzle)."""
-    cout, _, _, cin = w_ohwi.shape
-    ntw = bn // 16
-    perm = [4 * ntw * (q >> 2) + 4 * j + (q & 3) for j in range(ntw) for q in range(16)]
-    w5 = w_ohwi.reshape(cout // bn, bn, 9, cin // 32, 32)[:, perm]                              # [slab][row][tap][chunk][c]
-    t = w5.permute(0, 3, 2, 1, 4).reshape(cout // bn, cin // 32, 9, bn, 4, 8)                   # [slab][chunk][tap][row][piece][8]
-    rows = torch.arange(bn)
-    src = torch.arange(4)[None, :] ^ ((rows >> 1) & 2)[:, None]
-    t = torch.gather(t, 4, src[None, None, None, :, :, None].expand(t.shape))
-    return t.to(torch.bfloat16).to(device).contiguous()
-
-
-class PackedUp(object):
-    """The 1x1 convolutions into ONE output of an HR module's fuse layer, packed for ``pam_fuse_sum_nhwc_bf16`` (csrc/pam_fuse.hip):
-    per coarser source branch the weights as MFMA A fragments [C / 16][Cs / 32][64 lanes][8] (lane l of fragment (j, ks) holds
-    W[16 j + (l & 15)][32 ks + 8 (l >> 4) .. + 7]) and the float32 bias."""
-
-    def __init__(self, convs, shifts, device):
-        self.c = convs[0].weight.shape[0]
-        self.shifts, self.chans, self.wimg, self.bias = list(shifts), [], [], []
-        for cv in convs:
-            c, cs = cv.weight.shape[0], cv.weight.shape[1]
-            assert c == self.c and cv.weight.shape[2:] == (1, 1) and cs % 32 == 0 and c % 16 == 0
-            w = cv.weight.detach().float().reshape(c // 16, 16, cs // 32, 4, 8).permute(0, 2, 3, 1, 4)     # [j][ks][g][q][8]
-            self.wimg.append(w.reshape(c // 16, cs // 32, 64, 8).to(torch.bfloat16).to(device).contiguous())
-            self.bias.append((cv.bias.detach().float() if cv.bias is not None else torch.zeros(c)).to(device).contiguous())
-            self.chans.append(cs)
-        n = len(convs)
-        self.c_w = (C.c_void_p * n)(*[C.c_void_p(t.data_ptr()) for t in self.wimg])
-        self.c_b = (C.c_void_p * n)(*[C.c_void_p(t.data_ptr()) for t in self.bias])
-        self.c_sh = (C.c_int32 * n)(*self.shifts)
-        self.c_ch = (C.c_int32 * n)(*self.chans)
-
-
-class PackedBlock(object):
-    """One BasicBlock (conv3x3 -> ReLU -> conv3x3 -> + x -> ReLU) of the 32-, 48- or 96-channel branch packed for
-    ``pam_basic_block2_nhwc_bf16`` (csrc/pam_block2.hip; layouts: include/pam.h): ONE buffer ``wpack`` =
-    [float32 bias of conv1, conv2, padded to 1 KiB][k-step weight images of conv1][... of conv2]."""
-
-    def __init__(self, conv1, conv2, device):
-        c = conv1.weight.shape[0]
-        assert c in (32, 48, 96) and conv1.weight.shape == (c, c, 3, 3) and conv2.weight.shape == (c, c, 3, 3)
-        rows = torch.arange(c)
-        zb = lambda cv: cv.bias.detach().float() if cv.bias is not None else torch.zeros(c)
-        head = torch.zeros(256, dtype=torch.float32)
-        head[:2 * c] = torch.cat([zb(conv1), zb(conv2)])
-        if c == 32:
-            # k_bblock2_32: K = (tap, cin), 9 k-steps of 32 (one per tap); a k-step image = [32 rows][4 pieces][8].  Row j * 16 + q =
-            # channel 8 (q >> 2) + 4 j + (q & 3) (a lane ends with channels 8 g .. 8 g + 7: one 16-byte piece of a pixel); physical piece
-            # p of row R holds logical piece p ^ ((R >> 2) & 3) (LDS bank swizzle)
-            chan = 8 * ((rows % 16) >> 2) + 4 * (rows // 16) + (rows & 3)
-            src = torch.arange(4)[None, :] ^ ((rows >> 2) & 3)[:, None]
-            imgs = []
-            for conv in (conv1, conv2):
-                w = conv.weight.detach().float().permute(0, 2, 3, 1)[chan].reshape(c, 9, 4, 8)      # [row][tap][piece][8]
-                imgs.append(torch.gather(w, 2, src[:, None, :, None].expand(c, 9, 4, 8)).permute(1, 0, 2, 3))
-            nbytes = 1024 + 2 * 9 * c * 64
-        elif c == 48:
-            # k_bblock2_48: K = (tap, cin) flattened, 14 k-steps of 32 (zero tail); a k-step image = [48 rows][4 pieces][8].  Row
-            # j * 16 + 4 q' + r = channel 8 q' + 4 j + r for N tiles j = 0, 1 and 32 + 4 q' + r for j = 2 (a lane ends with channels
-            # 8 g .. 8 g + 7 and 32 + 4 g .. + 3: aligned 16 + 8 bytes of a pixel); physical piece p of row R holds logical piece
-            # p ^ sigma[(R % 16) >> 2], sigma = (0, 2, 3, 1) (LDS bank swizzle)
-            nstep = 14
-            j, qq, r = rows // 16, (rows % 16) >> 2, rows & 3
-            chan = torch.where(j < 2, 8 * qq + 4 * j + r, 32 + 4 * qq + r)
-            src = torch.arange(4)[None, :] ^ torch.tensor([0, 2, 3, 1])[qq][:, None]
-            imgs = []
-            for conv in (conv1, conv2):
-                w = conv.weight.detach().float().permute(0, 2, 3, 1).reshape(c, 9 * c)[chan]       # [row][k = tap * C + cin]
-                wk = torch.zeros((c, nstep * 32), dtype=torch.float32)
-                wk[:, :9 * c] = w
-                wk = wk.reshape(c, nstep, 4, 8)                                                    # [row][k-step][piece][8]
-                imgs.append(torch.gather(wk, 2, src[:, None, :, None].expand(c, nstep, 4, 8)).permute(1, 0, 2, 3))
-            nbytes = 1024 + 2 * nstep * c * 64
-        else:
-            # k_bblock2_96: k-step images [96 rows][4 pieces][8] in the order (conv, chunk of 32 input channels, tap); row j * 16 + q =
-            # output channel 24 * (q >> 2) + 4 * j + (q & 3) (a lane ends with 24 contiguous channels), physical piece p of row r holds
-            # the chunk's input channels 8 * (p ^ ((r >> 1) & 2)) .. + 7
-            chan = 24 * ((rows % 16) >> 2) + 4 * (rows // 16) + (rows & 3)
-            src = torch.arange(4)[None, :] ^ ((rows >> 1) & 2)[:, None]
-            imgs = []
-            for conv in (conv1, conv2):
-                w = conv.weight.detach().float().permute(0, 2, 3, 1)[chan]                         # [row][ky][kx][cin]
-                w = w.reshape(c, 9, 3, 4, 8).permute(2, 1, 0, 3, 4)                                # [chunk][tap][row][piece][8]
-                imgs.append(torch.gather(w, 3, src[None, None, :, :, None].expand(3, 9, c, 4, 8)))
-            nbytes = 1024 + 2 * 27 * c * 64
-        self.wpack = torch.cat([head.view(torch.uint8), torch.stack(imgs).to(torch.bfloat16).reshape(-1).view(torch.uint8)]).to(device).contiguous()
-        assert self.wpack.numel() == nbytes
-        self.c = c
-
-
-class PackedTail(object):
-    """The pointwise tail of a layer1 Bottleneck packed for ``pam_bottleneck_tail_nhwc_bf16`` (csrc/pam_pw.hip; layouts: include/pam.h):
-    conv3 (64 -> 256) [+ the first block's 1x1 downsample as a second K chunk] and, optionally, the NEXT block's conv1 (256 -> 64)."""
-
-    def __init__(self, conv3, down, conv1_next, device):
-        assert conv3.weight.shape == (256, 64, 1, 1) and (down is None or down.weight.shape == (256, 64, 1, 1))
-        assert conv1_next is None or conv1_next.weight.shape == (64, 256, 1, 1)
-        zb = lambda cv: cv.bias.detach().float() if cv.bias is not None else torch.zeros(cv.weight.shape[0])
-        R = torch.arange(256)
-        rem = R % 64
-        ch3 = 64 * (R // 64) + 16 * ((rem % 16) >> 2) + 4 * (rem // 16) + (rem & 3)                   # LDS row -> output channel
-        q3 = torch.arange(8)[None, :] ^ ((R >> 1) & 7)[:, None]                                    # [row][physical piece] -> logical piece
-        srcs = [conv3] + ([down] if down is not None else [])
-        img = torch.zeros((len(srcs), 256, 8, 8), dtype=torch.float32)
-        for c, cv in enumerate(srcs):
-            w = cv.weight.detach().float().reshape(256, 64)[ch3].reshape(256, 8, 8)                # [row][logical piece][8]
-            img[c] = torch.gather(w, 1, q3[:, :, None].expand(256, 8, 8))
-        self.w3 = img.to(torch.bfloat16).to(device).contiguous()
-        self.b3 = (zb(conv3) + (zb(down) if down is not None else 0)).to(device).contiguous()
-        self.S = len(srcs)
-        self.w1 = self.b1 = None
-        if conv1_next is not None:
-            R1 = torch.arange(64)
-            ch1 = 16 * ((R1 % 16) >> 2) + 4 * (R1 // 16) + (R1 & 3)
-            q1 = torch.arange(8)[None, :] ^ ((R1 >> 1) & 7)[:, None]                               # [row][physical piece] -> logical piece q
-            w = conv1_next.weight.detach().float().reshape(64, 256)[ch1]                           # [row][input channel]
-            im1 = torch.zeros((4, 64, 8, 8), dtype=torch.float32)
-            e = torch.arange(8)
-            for sl in range(4):
-                cin = 64 * sl + 16 * (q1 & 3)[:, :, None] + 8 * (q1 >> 2)[:, :, None] + e[None, None, :]   # [row][piece][8] input channel
-                im1[sl] = torch.gather(w, 1, cin.reshape(64, 64)).reshape(64, 8, 8)
-            self.w1 = im1.to(torch.bfloat16).to(device).contiguous()
-            self.b1 = zb(conv1_next).to(device).contiguous()
-
-
-class PackedPointwise64(object):
-    """A 64 -> 64 1x1 convolution (+ ReLU) packed for ``pam_pointwise64_relu_nhwc_bf16`` (csrc/pam_pw.hip, k_pw1)."""
-
-    def __init__(self, conv, device):
-        assert conv.weight.shape == (64, 64, 1, 1)
-        R = torch.arange(64)
-        ch = 16 * ((R % 16) >> 2) + 4 * (R // 16) + (R & 3)
-        q = torch.arange(8)[None, :] ^ ((R >> 1) & 7)[:, None]
-        w = conv.weight.detach().float().reshape(64, 64)[ch].reshape(64, 8, 8)
-        self.w = torch.gather(w, 1, q[:, :, None].expand(64, 8, 8)).to(torch.bfloat16).to(device).contiguous()
-        self.b = (conv.bias.detach().float() if conv.bias is not None else torch.zeros(64)).to(device).contiguous()
-
-
-def conv64_image(conv, device):
-    """[9 taps][64 rows][64 K] bf16 LDS image of a 64 -> 64 3x3 convolution for the fused stem / Bottleneck kernels (layout: include/pam.h):
-    row 16 j + q of a tap = output channel 32 (j >> 1) + 8 (q >> 2) + 4 (j & 1) + (q & 3) -- a lane then ends with channels 32 h + 8 g .. + 7,
-    the natural K order of the pointwise product that consumes its accumulators --, 16-byte pieces swizzled by (q >> 1) & 7."""
-    assert conv.weight.shape == (64, 64, 3, 3)
-    R = torch.arange(64)
-    j, q = R // 16, R % 16
-    ch = 32 * (j >> 1) + 8 * (q >> 2) + 4 * (j & 1) + (q & 3)                                   # image row -> output channel
-    c = torch.arange(8)[None, :] ^ ((q >> 1) & 7)[:, None]                                      # [row][physical piece] -> logical piece
-    cin = (8 * c[:, :, None] + torch.arange(8)[None, None, :]).reshape(64, 64)                  # [row][physical K position] -> input channel
-    w = conv.weight.detach().float()[ch]                                                        # [row][cin][ky][kx]
-    img = torch.zeros((9, 64, 64), dtype=torch.float32)
-    for ky in range(3):
-        for kx in range(3):
-            img[ky * 3 + kx] = torch.gather(w[:, :, ky, kx], 1, cin)
-    return img.to(torch.bfloat16).to(device).contiguous()
-
-
-class PackedBneck(object):
-    """A layer1 Bottleneck from its 3x3 convolution on, packed for ``pam_bottleneck_fused_nhwc_bf16`` (csrc/pam_bneck.hip): the 3x3's LDS
-    image + the pointwise tail's images (PackedTail with one K source)."""
-
-    def __init__(self, conv2, tail, device):
-        assert conv2.stride[0] == 1 and conv2.padding[0] == 1
-        self.tail = tail
-        self.w2 = conv64_image(conv2, device)
-        self.b2 = (conv2.bias.detach().float() if conv2.bias is not None else torch.zeros(64)).to(device).contiguous()
-
-
-class PackedStem(object):
-    """HRNet's stem (conv1 8 -> 64 s2, conv2 64 -> 64 s2) and layer1[0].conv1 (64 -> 64 1x1) packed for ``pam_stem_fused_nhwc_bf16``
-    (csrc/pam_stem.hip; layouts: include/pam.h): conv1 and the pointwise keep the images of their own kernels, conv2 gets the
-    [9 taps][64 rows][64 K] LDS image."""
-
-    def __init__(self, conv1_packed, conv2, pw_packed, device):
-        assert conv1_packed._stem is not None and conv1_packed.cout == 64 and conv1_packed.stride == 2
-        assert conv2.weight.shape == (64, 64, 3, 3) and conv2.stride[0] == 2 and conv2.padding[0] == 1
-        self.c1, self.pw = conv1_packed, pw_packed
-        self.w2 = conv64_image(conv2, device)
-        self.b2 = (conv2.bias.detach().float() if conv2.bias is not None else torch.zeros(64)).to(device).contiguous()
-
-
-class ActivationArena(object):
-    """Activations of the captured forwards of ONE replay slot: a bump allocator over one device buffer of two halves.  The executor
-    calls ``epoch()`` at the start of the stem, of layer1's successor and of every HR module; an epoch allocates from the half the
-    epoch before last used -- everything produced two epochs ago is dead by then (a module's tensors are read by that module and by the
-    next one's first kernels only, and a full join of the branch streams lies between any two epochs).  Every capture of the slot (one
-    per crop-count bucket) replays into the same buffer: they run one after the other, never at the same time.  Round 3 let every
-    capture keep its own tensors: 197 GiB after a sweep over the 55 crop-count buckets of the Panoptic workload (tools/graph_memory.py).
-    Without a device (``half_bytes`` None) the arena only measures: the largest epoch of a shape-only walk sizes the real one."""
-
-    def __init__(self, device=None, half_bytes=None):
-        self.half_bytes = half_bytes
-        self.buf = torch.empty(2 * half_bytes, dtype=torch.uint8, device=device) if half_bytes else None
-        self.half, self.off, self.peak = 1, 0, 0
-
-    def epoch(self):
-        self.half ^= 1
-        self.off = 0
-
-    def count(self, nbytes):
-        self.off += (nbytes + 255) // 256 * 256
-        self.peak = max(self.peak, self.off)
-
-    def alloc(self, n, c, h, w):
-        nbytes = 2 * n * c * h * w
-        a = self.half * self.half_bytes + self.off
-        self.count(nbytes)
-        if self.off > self.half_bytes:
-            raise _lib.PamError('activation arena too small: epoch needs > %d bytes' % self.half_bytes)
-        return self.buf[a:a + nbytes].view(torch.bfloat16).as_strided((n, c, h, w), (h * w * c, 1, w * c, c))
-
-
-class ConvEngine(object):
-    """Kernel launchers shared by the pose network (HipHRNet) and the person detector (yolov3.HipDarknet)."""
-    count = None            # set to a dict to tally algorithmic bytes / flops of one forward (bench.py)
-    prof = None             # set to a list: every launch appends dict(family, sig, bytes, flops, fn) -- fn re-issues exactly that launch
-                            # (bench.py times each distinct one alone for the per-family roofline)
-
-    def _prof_add(self, x, family, sig, nbytes, flops, fn):
-        if self.prof is not None and x.device.type == 'cuda':
-            self.prof.append(dict(family=family, sig=(family,) + tuple(sig), bytes=nbytes, flops=flops, fn=fn))
-    arena = None                # an ActivationArena: outputs are carved from it instead of torch.empty (HRNetPose's captured replays)
-
-    def _new(self, n, c, h, w, device):
-        """A fresh (n, c, h, w) channels-last bf16 activation: from the arena when one is set, else from the caching allocator (kept
-        alive until the forward has been issued: another stream may still read what a freed block held)."""
-        if self.arena is not None and device.type != 'meta':
-            return self.arena.alloc(n, c, h, w)
-        if self.arena is not None:
-            self.arena.count(2 * n * c * h * w)
-        y = torch.empty((n, c, h, w), dtype=torch.bfloat16, device=device, memory_format=torch.channels_last)
-        if self._keep is not None:
-            self._keep.append(y)
-        return y
-
-    pw64 = True                 # 64 -> 64 pointwise layers over >= 64 k pixels on the streaming kernel k_pw1 (ReLU or leaky)
-    slab32 = False              # round 5: the 192- / 384-channel 3x3 layers with 32-channel slabs (pam_conv3x3_layout_small): for forwards of a few crops
-    gen_streamed = True         # Darknet 3x3 layers with Cin 128 / 256 / 512 on k_conv3x3s<.., GEN> (False: the classic k_conv3x3)
-    tile_cfg = -1
-    c96_slab = 0                # 96 -> 96 3x3 layers: 0 = k_conv3x3, 48 / 96 = the streamed kernel with slabs of that many output channels
-    _keep = None
-    ACT = {None: 0, False: 0, True: 1, 'linear': 0, 'relu': 1, 'leaky': 2}
-
-    def conv(self, op, x, res=None, relu=False, res_after_act=False, relu_from=0):
-        """relu: False/True, or 'linear' | 'relu' | 'leaky' (slope 0.1); res_after_act: out = act(conv + b) + res (Darknet shortcut).
-        x may be a channel slice of a wider channels-last tensor; relu_from: the activation applies to channels >= relu_from."""
-        n, cin, h, w = x.shape
-        if (self.down48 and op.stride == 2 and op.kh == 3 and op.kw == 3 and op.pad == 1 and op.cin == 48 and op.cout % 48 == 0 and
-                self.ACT[relu] <= 1 and not res_after_act and relu_from % 8 == 0):
-            return self.conv_down48(op, x, res=res, relu=bool(self.ACT[relu]), relu_from=relu_from)
-        if (self.down_s and op.stride == 2 and op.kh == 3 and op.kw == 3 and op.pad == 1 and op.cin in (96, 192) and res is None and
-                self.ACT[relu] <= 1 and relu_from % 16 == 0 and self.tile_cfg == -1 and
-                (x.device.type == 'meta' or self.lib.pam_conv3x3s2_slab(h, w, cin, op.cout) > 0)):
-            return self.conv_down_s(op, x, relu=bool(self.ACT[relu]), relu_from=relu_from)
-        if (self.pw64 and op.kh == 1 and op.kw == 1 and op.stride == 1 and cin == 64 and op.cout == 64 and res is None and relu_from == 0 and
-                self.ACT[relu] in (1, 2) and x.device.type != 'meta' and x.is_contiguous(memory_format=torch.channels_last) and n * h * w >= 65536):
-            # a 64 -> 64 pointwise layer over many pixels (Darknet's 64 -> 32, zero-padded, at 208 x 208) is a pure stream: k_pw1
-            img = op._images.get('pw64')
-            if img is None:
-                R = torch.arange(64)
-                ch = 16 * ((R % 16) >> 2) + 4 * (R // 16) + (R & 3)
-                q = torch.arange(8)[None, :] ^ ((R >> 1) & 7)[:, None]
-                w64 = op.w[:, :64].float().cpu()[ch].reshape(64, 8, 8)
-                img = op._images['pw64'] = torch.gather(w64, 1, q[:, :, None].expand(64, 8, 8)).to(torch.bfloat16).to(op._device).contiguous()
-            y = self._new(n, 64, h, w, x.device)
-            if self.count is not None:
-                self.count['bytes'] += 2 * (x.numel() + y.numel() + 64 * 64) + 4 * 64; self.count['flops'] += 2 * y.numel() * 64; self.count['launches'] += 1
-            rc = self.lib.pam_pointwise64_act_nhwc_bf16(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), C.c_void_p(x.data_ptr()),
-                                                        C.c_void_p(img.data_ptr()), C.c_void_p(op.bias.data_ptr()), C.c_void_p(y.data_ptr()), n * h * w, self.ACT[relu])
-            if rc != 0:
-                raise _lib.PamError('pam_pointwise64_act_nhwc_bf16 failed (%d)' % rc)
-            return y
-        in_cs = cin if x.device.type == 'meta' else x.stride(3)          # channels between neighbouring pixels
-        assert cin == op.cin and (x.device.type == 'meta' or (x.stride(1) == 1 and x.stride(2) == w * in_cs and x.stride(0) == h * w * in_cs)), (x.shape, op.cin)
-        ho = (h + 2 * op.pad - op.kh) // op.stride + 1
-        wo = (w + 2 * op.pad - op.kw) // op.stride + 1
-        y = self._new(n, op.cout, ho, wo, x.device)
-        if self.count is not None:       # unique bytes this conv must move: input + weights + bias [+ residual] + output
-            self.count['bytes'] += 2 * (x.numel() + y.numel() + op.cout * op.kh * op.kw * op.cin + (y.numel() if res is not None else 0)) + 4 * op.cout
-            self.count['flops'] += 2 * y.numel() * op.kh * op.kw * op.cin
-            self.count['launches'] += 1
-        if x.device.type == 'meta':
-            return y
-        act = self.ACT[relu] | (4 if (res_after_act and res is not None) else 0)
-        # the streamed kernels (k_conv3x3s / k_conv_gs) take the activation codes 0 / 1 only: leaky / shortcut-after-activation layers
-        # (the detector's) ask for the classic kernels and the classic weight image
-        tile_cfg = -2 if (self.tile_cfg == -1 and act > 1) else self.tile_cfg
-        wimg = None
-        if (tile_cfg == -2 and self.gen_streamed and op.kh == 3 and op.kw == 3 and op.stride == 1 and op.pad == 1 and in_cs == cin and relu_from == 0
-                and op._w_ohwi is not None and self.lib.pam_conv3x3_layout_gen(h, w, cin, op.cout) > 0):
-            # round 5: Darknet's 3x3 layers (leaky, shortcut after the activation) on the streamed kernel's general-activation instantiations
-            bn = self.lib.pam_conv3x3_layout_gen(h, w, cin, op.cout)
-            wimg = op._images.get(('gen', bn))
-            if wimg is None:
-                wimg = op._images[('gen', bn)] = streamed_image(op._w_ohwi, bn, op._device)
-            tile_cfg = -7
-        if (wimg is None and self.slab32 and tile_cfg == -1 and op.kh == 3 and op.kw == 3 and op.stride == 1 and op.pad == 1 and cin in (192, 384) and
-                in_cs == cin and relu_from == 0 and op._w_ohwi is not None and self.lib.pam_conv3x3_layout_small(h, w, cin, op.cout) > 0):
-            # forwards of a few crops: the deep branches' layers with 32-channel slabs (twice the workgroups, each half as long; bit-identical)
-            wimg = op._images.get(('s32', 32))
-            if wimg is None:
-                wimg = op._images[('s32', 32)] = streamed_image(op._w_ohwi, 32, op._device)
-            tile_cfg = -8
-        if wimg is None:
-            wimg = op.image(h, w, classic=(tile_cfg != -1), c96_slab=self.c96_slab) if (in_cs == cin and relu_from == 0) else None
-        if tile_cfg == -1 and wimg is not None and op._stem is None:
-            # automatic choice, but the layout of THIS image is stated: -3 streamed / -4 classic, -5 / -6 a 96 -> 96 layer streamed with
-            # slabs of 48 / 96 output channels (the executor's choice, c96_slab)
-            tile_cfg = ({48: -5, 96: -6}.get(getattr(op, 'last_c96', 0), -3)) if getattr(op, 'last_streamed', False) else -4
-        st = torch.cuda.current_stream(x.device).cuda_stream
-        launch = lambda: self.lib.pam_conv2d_nhwc_bf16_ex(
-            C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), C.c_void_p(x.data_ptr()), C.c_void_p(op.w.data_ptr()),
-            C.c_void_p(wimg.data_ptr()) if wimg is not None else None,
-            C.c_void_p(op.bias.data_ptr()), C.c_void_p(res.data_ptr()) if res is not None else None,
-            C.c_void_p(y.data_ptr()), n, h, w, op.cin, op.cout, op.kh, op.kw, op.stride, op.pad, act, tile_cfg, in_cs, relu_from)
-        rc = launch()
-        if rc != 0:
-            raise _lib.PamError('pam_conv2d_nhwc_bf16 failed (%d) for %s' % (rc, (x.shape, op.cout, op.kh, op.stride)))
-        if self.prof is not None:
-            kind = self.lib.pam_conv_last_kernel()
-            if kind == 4:
-                fam = 'k_conv_stem %d->%d' % (3, op.cout)
-            elif kind in (1, 2):
-                fam = '%s C=%d %dx%d' % ('k_conv3x3s' if kind == 2 else 'k_conv3x3', op.cin, h, w)
-            else:
-                fam = '%s %dx%d stride %d' % ('k_conv_gs' if kind == 3 else 'k_conv_igemm', op.kh, op.kw, op.stride)
-            self._prof_add(x, fam, (n, h, w, op.cin, op.cout, res is not None, in_cs, relu_from),
-                           2 * (x.numel() + y.numel() + op.cout * op.kh * op.kw * op.cin + (y.numel() if res is not None else 0)) + 4 * op.cout,
-                           2 * y.numel() * op.kh * op.kw * op.cin, launch)
-        return y
-
-    def basic_block2(self, op, x, tile=None):
-        """One BasicBlock (PackedBlock with ``wpack``: C = 32, 48 or 96) on x through the resident-weights kernel; tile = (rows, cols) or None."""
-        n, c, h, w = x.shape
-        assert c == op.c, (x.shape, op.c)
-        y = self._new(n, c, h, w, x.device)
-        nbytes, flops = 2 * (2 * x.numel() + 2 * 9 * c * c) + 8 * c, 2 * 2 * x.numel() * 9 * c
-        if self.count is not None:
-            self.count['bytes'] += nbytes; self.count['flops'] += flops; self.count['launches'] += 1
-        if x.device.type == 'meta':
-            return y
-        assert x.is_contiguous(memory_format=torch.channels_last)
-        if tile is None and c == 96 and self.b96_tile:
-            tile = tuple(self.b96_tile)
-        if tile is None and c == 48 and self.b48_tile:
-            tile = tuple(self.b48_tile)
-        if tile is None:
-            tile = self._bb2_tiles.get((c, n, h, w))
-            if tile is None:
-                t2 = (C.c_int32 * 2)()
-                if self.lib.pam_basic_block2_tile(c, n, h, w, t2) != 0:
-                    raise _lib.PamError('no resident-weights block tile for %s' % (tuple(x.shape),))
-                tile = self._bb2_tiles[(c, n, h, w)] = (int(t2[0]), int(t2[1]))
-        launch = lambda: self.lib.pam_basic_block2_nhwc_bf16(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), C.c_void_p(x.data_ptr()),
-                                                              C.c_void_p(op.wpack.data_ptr()), C.c_void_p(y.data_ptr()), n, h, w, c, tile[0], tile[1])
-        rc = launch()
-        if rc != 0:
-            raise _lib.PamError('pam_basic_block2_nhwc_bf16 failed (%d) for %s tile %s' % (rc, tuple(x.shape), tile))
-        self._prof_add(x, 'k_bblock2 C=%d' % c, (n, h, w, c) + tuple(tile), nbytes, flops, launch)
-        return y
-
-    _bb2_tiles = {}             # (C, N, H, W) -> the library's tile choice (pam_basic_block2_tile searches ~H x W candidates)
-    b48_tile = None             # the same for the 48-channel block
-    b96_tile = None             # (rows, cols) of the 96-channel fused block's items instead of the library's choice (tuning)
-
-    def pointwise64(self, op, x):
-        """ReLU(conv1x1 64 -> 64 (x)) as a pure stream (k_pw1)."""
-        n, c, h, w = x.shape
-        assert c == 64
-        y = self._new(n, c, h, w, x.device)
-        nbytes, flops = 2 * (2 * x.numel() + 64 * 64) + 4 * 64, 2 * n * h * w * 64 * 64
-        if self.count is not None:
-            self.count['bytes'] += nbytes; self.count['flops'] += flops; self.count['launches'] += 1
-        if x.device.type == 'meta':
-            return y
-        assert x.is_contiguous(memory_format=torch.channels_last)
-        launch = lambda: self.lib.pam_pointwise64_relu_nhwc_bf16(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), C.c_void_p(x.data_ptr()),
-                                                                  C.c_void_p(op.w.data_ptr()), C.c_void_p(op.b.data_ptr()), C.c_void_p(y.data_ptr()), n * h * w)
-        rc = launch()
-        if rc != 0:
-            raise _lib.PamError('pam_pointwise64_relu_nhwc_bf16 failed (%d)' % rc)
-        self._prof_add(x, 'k_pw1 64->64 pointwise', (n, h, w), nbytes, flops, launch)
-        return y
-
-    def stem_fused(self, op, x8):
-        """(x0, y1) = stem + the first Bottleneck's conv1 in one launch (k_stem_fused): bit-identical to conv(conv1), conv(conv2), pointwise64."""
-        n, c, h, w = x8.shape
-        assert c == 8
-        h2, w2 = ((h - 1) // 2 + 1 - 1) // 2 + 1, ((w - 1) // 2 + 1 - 1) // 2 + 1
-        x0 = self._new(n, 64, h2, w2, x8.device)
-        y1 = self._new(n, 64, h2, w2, x8.device)
-        h1, w1 = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-        nbytes = 2 * (x8.numel() + x0.numel() + y1.numel() + 64 * 72 + 64 * 576 + 64 * 64) + 4 * 192
-        flops = 2 * n * (h1 * w1 * 64 * 72 + h2 * w2 * 64 * (576 + 64))
-        if self.count is not None:
-            self.count['bytes'] += nbytes; self.count['flops'] += flops; self.count['launches'] += 1
-        if x8.device.type == 'meta':
-            return x0, y1
-        assert x8.is_contiguous(memory_format=torch.channels_last)
-        launch = lambda: self.lib.pam_stem_fused_nhwc_bf16(
-            C.c_void_p(torch.cuda.current_stream(x8.device).cuda_stream), C.c_void_p(x8.data_ptr()), C.c_void_p(op.c1._stem.data_ptr()),
-            C.c_void_p(op.c1.bias.data_ptr()), C.c_void_p(op.w2.data_ptr()), C.c_void_p(op.b2.data_ptr()), C.c_void_p(op.pw.w.data_ptr()),
-            C.c_void_p(op.pw.b.data_ptr()), C.c_void_p(x0.data_ptr()), C.c_void_p(y1.data_ptr()), n, h, w)
-        rc = launch()
-        if rc != 0:
-            raise _lib.PamError('pam_stem_fused_nhwc_bf16 failed (%d) for %s' % (rc, tuple(x8.shape)))
-        self._prof_add(x8, 'k_stem_fused stem + conv1 of layer1', (n, h, w), nbytes, flops, launch)
-        return x0, y1
-
-    def bottleneck_fused(self, op, y1, res=None, x0=None):
-        """(X, y1' or None) = conv3x3 + pointwise tail of a layer1 Bottleneck in one launch (k_bneck): bit-identical to conv(c2) + bottleneck_tail.
-        res: the block input (blocks 1-3); x0: the first block's 64-channel input (its downsample convolution is part of the tail)."""
-        n, c, h, w = y1.shape
-        t = op.tail
-        assert c == 64 and (res is None) != (x0 is None) and (x0 is None) == (t.S == 1)
-        assert res is None or tuple(res.shape) == (n, 256, h, w)
-        X = self._new(n, 256, h, w, y1.device)
-        Y = self._new(n, 64, h, w, y1.device) if t.w1 is not None else None
-        M = n * h * w
-        side = res if res is not None else x0
-        nbytes = 2 * (y1.numel() + side.numel() + X.numel() + (Y.numel() if Y is not None else 0) + 64 * 576 + t.S * 256 * 64 +
-                      (64 * 256 if t.w1 is not None else 0)) + 4 * (64 + 256 + (64 if t.w1 is not None else 0))
-        flops = 2 * M * (64 * 576 + t.S * 64 * 256 + (256 * 64 if t.w1 is not None else 0))
-        if self.count is not None:
-            self.count['bytes'] += nbytes; self.count['flops'] += flops; self.count['launches'] += 1
-        if y1.device.type == 'meta':
-            return X, Y
-        for q in (y1, side):
-            assert q.is_contiguous(memory_format=torch.channels_last)
-        launch = lambda: self.lib.pam_bottleneck_fused_nhwc_bf16(
-            C.c_void_p(torch.cuda.current_stream(y1.device).cuda_stream), C.c_void_p(y1.data_ptr()),
-            C.c_void_p(x0.data_ptr()) if x0 is not None else None, C.c_void_p(res.data_ptr()) if res is not None else None,
-            C.c_void_p(op.w2.data_ptr()), C.c_void_p(op.b2.data_ptr()), C.c_void_p(t.w3.data_ptr()), C.c_void_p(t.b3.data_ptr()),
-            C.c_void_p(t.w1.data_ptr()) if t.w1 is not None else None, C.c_void_p(t.b1.data_ptr()) if t.w1 is not None else None,
-            C.c_void_p(X.data_ptr()), C.c_void_p(Y.data_ptr()) if Y is not None else None, n, h, w)
-        rc = launch()
-        if rc != 0:
-            raise _lib.PamError('pam_bottleneck_fused_nhwc_bf16 failed (%d) for %s' % (rc, tuple(y1.shape)))
-        self._prof_add(y1, 'k_bneck 3x3 + bottleneck tail', (n, h, w, t.S, t.w1 is not None), nbytes, flops, launch)
-        return X, Y
-
-    def bottleneck_tail(self, op, y2, x0=None, res=None, tile_cfg=0):
-        """X = ReLU(conv3(y2) [+ downsample(x0)] [+ res]); y1 = ReLU(conv1_next(X)) in one launch -> (X, y1 or None)."""
-        n, c, h, w = y2.shape
-        assert c == 64 and (x0 is None) == (op.S == 1), (y2.shape, op.S)
-        X = self._new(n, 256, h, w, y2.device)
-        Y = self._new(n, 64, h, w, y2.device) if op.w1 is not None else None
-        M = n * h * w
-        nbytes = 2 * (y2.numel() + (x0.numel() if x0 is not None else 0) + (res.numel() if res is not None else 0) + X.numel() +
-                      (Y.numel() if Y is not None else 0) + op.S * 256 * 64 + (64 * 256 if op.w1 is not None else 0)) + 4 * (256 + (64 if op.w1 is not None else 0))
-        flops = 2 * M * (op.S * 64 * 256 + (256 * 64 if op.w1 is not None else 0))
-        if self.count is not None:
-            self.count['bytes'] += nbytes; self.count['flops'] += flops; self.count['launches'] += 1
-        if y2.device.type == 'meta':
-            return X, Y
-        for t in (y2, x0, res):
-            assert t is None or t.is_contiguous(memory_format=torch.channels_last)
-        launch = lambda: self.lib.pam_bottleneck_tail_nhwc_bf16(
-            C.c_void_p(torch.cuda.current_stream(y2.device).cuda_stream), C.c_void_p(y2.data_ptr()),
-            C.c_void_p(x0.data_ptr()) if x0 is not None else None, C.c_void_p(res.data_ptr()) if res is not None else None,
-            C.c_void_p(op.w3.data_ptr()), C.c_void_p(op.b3.data_ptr()),
-            C.c_void_p(op.w1.data_ptr()) if op.w1 is not None else None, C.c_void_p(op.b1.data_ptr()) if op.w1 is not None else None,
-            C.c_void_p(X.data_ptr()), C.c_void_p(Y.data_ptr()) if Y is not None else None, M, tile_cfg)
-        rc = launch()
-        if rc != 0:
-            raise _lib.PamError('pam_bottleneck_tail_nhwc_bf16 failed (%d) for %s' % (rc, tuple(y2.shape)))
-        self._prof_add(y2, 'k_pw2 bottleneck tail', (n, h, w, op.S, res is not None, op.w1 is not None), nbytes, flops, launch)
-        return X, Y
-
-    def upsample_add(self, base, terms, shifts, relu):
-        n, c, h, w = base.shape
-        y = self._new(n, c, h, w, base.device)
-        if self.count is not None:
-            self.count['bytes'] += 2 * (2 * base.numel() + sum(t.numel() for t in terms))
-            self.count['launches'] += 1
-        if base.device.type == 'meta':
-            return y
-        st = torch.cuda.current_stream(base.device).cuda_stream
-        ptrs = (C.c_void_p * 3)(*[C.c_void_p(t.data_ptr()) for t in terms] + [None] * (3 - len(terms)))
-        sh = (C.c_int32 * 3)(*(list(shifts) + [0] * (3 - len(shifts))))
-        cs = (C.c_int32 * 3)(*([t.stride(3) for t in terms] + [0] * (3 - len(terms))))       # terms may be channel slices
-        launch = lambda: self.lib.pam_upsample_add_nhwc_bf16_ex(C.c_void_p(torch.cuda.current_stream(base.device).cuda_stream),
-                                                                 C.c_void_p(base.data_ptr()), len(terms), ptrs, sh, cs,
-                                                                 C.c_void_p(y.data_ptr()), n, h, w, c, 1 if relu else 0)
-        rc = launch()
-        if rc != 0:
-            raise _lib.PamError('pam_upsample_add_nhwc_bf16 failed (%d)' % rc)
-        self._prof_add(base, 'k_upsample_add', (n, h, w, c, len(terms)), 2 * (2 * base.numel() + sum(t.numel() for t in terms)), 0, launch)
-        return y
-
-    def fuse_sum(self, op, base, plain, srcs, relu=True, tile=(0, 0), max_wg=0):
-        """One output of an HR module's fuse layer in one launch (k_fuse_sum): relu(base + sum plain + sum up(conv1x1(src))).
-        op: PackedUp; plain: tensors of base's shape (channel slices allowed); srcs: the coarser branches' tensors in op's order."""
-        n, c, h, w = base.shape
-        assert c == op.c and len(srcs) == len(op.shifts) and len(plain) <= 2
-        y = self._new(n, c, h, w, base.device)
-        nbytes = 2 * (2 * base.numel() + sum(t.numel() for t in plain) + sum(t.numel() for t in srcs) + sum(c * cs for cs in op.chans)) + 4 * c * len(srcs)
-        flops = sum(2 * t.shape[0] * t.shape[2] * t.shape[3] * t.shape[1] * c for t in srcs)
-        if self.count is not None:
-            self.count['bytes'] += nbytes; self.count['flops'] += flops; self.count['launches'] += 1
-        if base.device.type == 'meta':
-            return y
-        for t, sh, cs in zip(srcs, op.shifts, op.chans):
-            assert tuple(t.shape) == (n, cs, h >> sh, w >> sh) and t.is_contiguous(memory_format=torch.channels_last), (t.shape, base.shape, sh)
-        pp = (C.c_void_p * 2)(*[C.c_void_p(t.data_ptr()) for t in plain] + [None] * (2 - len(plain)))
-        pcs = (C.c_int32 * 2)(*([t.stride(3) for t in plain] + [0] * (2 - len(plain))))
-        sp = (C.c_void_p * len(srcs))(*[C.c_void_p(t.data_ptr()) for t in srcs])
-        launch = lambda: self.lib.pam_fuse_sum_nhwc_bf16(
-            C.c_void_p(torch.cuda.current_stream(base.device).cuda_stream), C.c_void_p(base.data_ptr()), len(plain), pp, pcs, len(srcs), sp,
-            op.c_sh, op.c_ch, op.c_w, op.c_b, C.c_void_p(y.data_ptr()), n, h, w, c, 1 if relu else 0, int(tile[0]), int(tile[1]), int(max_wg))
-        rc = launch()
-        if rc != 0:
-            raise _lib.PamError('pam_fuse_sum_nhwc_bf16 failed (%d) for %s' % (rc, tuple(base.shape)))
-        self._prof_add(base, 'k_fuse_sum', (n, h, w, c, len(plain), len(srcs)), nbytes, flops, launch)
-        return y
-
-    down_s = True               # 3x3 stride-2 layers with 96 / 192 input channels on k_down_s (csrc/pam_down.hip); False: the generic kernels
-
-    def conv_down_s(self, op, x, relu=False, relu_from=0):
-        """3x3 stride-2 convolution of a 96- / 192-channel input (channel slices allowed) through the streamed stride-2 kernel."""
-        n, cin, h, w = x.shape
-        in_cs = cin if x.device.type == 'meta' else x.stride(3)
-        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-        y = self._new(n, op.cout, ho, wo, x.device)
-        nbytes = 2 * (x.numel() + y.numel() + op.cout * 9 * cin) + 4 * op.cout
-        flops = 2 * y.numel() * 9 * cin
-        if self.count is not None:
-            self.count['bytes'] += nbytes; self.count['flops'] += flops; self.count['launches'] += 1
-        if x.device.type == 'meta':
-            return y
-        assert x.stride(1) == 1 and x.stride(2) == w * in_cs and x.stride(0) == h * w * in_cs, (x.shape, x.stride())
-        bn = self.lib.pam_conv3x3s2_slab(h, w, cin, op.cout)
-        img = op._images.get(('s2', bn))
-        if img is None:
-            w_ohwi = op.w[:, :9 * cin].float().cpu().reshape(op.cout, 3, 3, cin)               # op.w: [cout][k = (ky, kx, cin)]
-            img = op._images[('s2', bn)] = streamed_image(w_ohwi, bn, op._device)
-        launch = lambda: self.lib.pam_conv3x3s2_nhwc_bf16(
-            C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), C.c_void_p(x.data_ptr()), in_cs, C.c_void_p(img.data_ptr()),
-            C.c_void_p(op.bias.data_ptr()), C.c_void_p(y.data_ptr()), n, h, w, cin, op.cout, 1 if relu else 0, int(relu_from))
-        rc = launch()
-        if rc != 0:
-            raise _lib.PamError('pam_conv3x3s2_nhwc_bf16 failed (%d) for %s -> %d' % (rc, tuple(x.shape), op.cout))
-        self._prof_add(x, 'k_down_s 3x3 stride 2 C=%d %dx%d' % (cin, h, w), (n, h, w, op.cout, in_cs, relu_from), nbytes, flops, launch)
-        return y
-
-    down48 = True               # 3x3 stride-2 layers with 48 input channels on k_down48 (csrc/pam_down.hip); False: the generic kernels
-    d48_tile = None             # (rows, cols, slab groups) instead of the library's choice (tuning)
-
-    def conv_down48(self, op, x, res=None, relu=False, relu_from=0):
-        """3x3 stride-2 convolution of a 48-channel input (a channel slice of a wider tensor is fine) through k_down48."""
-        n, cin, h, w = x.shape
-        assert cin == 48 and op.cin == 48 and op.stride == 2 and op.kh == 3 and op.pad == 1
-        in_cs = cin if x.device.type == 'meta' else x.stride(3)
-        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
-        y = self._new(n, op.cout, ho, wo, x.device)
-        nbytes = 2 * (x.numel() + y.numel() + op.cout * 9 * 48 + (y.numel() if res is not None else 0)) + 4 * op.cout
-        flops = 2 * y.numel() * 9 * 48
-        if self.count is not None:
-            self.count['bytes'] += nbytes; self.count['flops'] += flops; self.count['launches'] += 1
-        if x.device.type == 'meta':
-            return y
-        assert x.stride(1) == 1 and x.stride(2) == w * in_cs and x.stride(0) == h * w * in_cs, (x.shape, x.stride())
-        img = down48_image(op)
-        t = self.d48_tile or (0, 0, 0)
-        launch = lambda: self.lib.pam_conv3x3s2_c48_nhwc_bf16(
-            C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), C.c_void_p(x.data_ptr()), in_cs, C.c_void_p(img.data_ptr()),
-            C.c_void_p(op.bias.data_ptr()), C.c_void_p(res.data_ptr()) if res is not None else None, op.cout if res is not None else 0,
-            C.c_void_p(y.data_ptr()), op.cout, n, h, w, op.cout, 1 if relu else 0, int(relu_from), int(t[0]), int(t[1]), int(t[2]))
-        rc = launch()
-        if rc != 0:
-            raise _lib.PamError('pam_conv3x3s2_c48_nhwc_bf16 failed (%d) for %s -> %d' % (rc, tuple(x.shape), op.cout))
-        self._prof_add(x, 'k_down48 3x3 stride 2 C=48 %dx%d' % (h, w), (n, h, w, op.cout, res is not None, in_cs, relu_from), nbytes, flops, launch)
-        return y
-
-    def upsample_concat(self, a, b):
-        """Darknet upsample(x2) + route: concat(nearest_up2(a), b) along channels."""
-        n, ca, h2, w2 = a.shape
-        _, cb, h, w = b.shape
-        assert h == 2 * h2 and w == 2 * w2 and b.shape[0] == n, (a.shape, b.shape)
-        y = self._new(n, ca + cb, h, w, a.device)
-        if self.count is not None:
-            self.count['bytes'] += 2 * (a.numel() + b.numel() + y.numel())
-            self.count['launches'] += 1
-        if a.device.type == 'meta':
-            return y
-        st = torch.cuda.current_stream(a.device).cuda_stream
-        rc = self.lib.pam_upsample_concat_nhwc_bf16(C.c_void_p(st), C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
-                                                    C.c_void_p(y.data_ptr()), n, h, w, ca, cb)
-        if rc != 0:
-            raise _lib.PamError('pam_upsample_concat_nhwc_bf16 failed (%d)' % rc)
-        return y
-
-    def maxpool(self, x, size, stride):
-        """Darknet [maxpool]: pad = size - 1, out = (in + pad - size) / stride + 1, windows start at -pad / 2, taps outside the image
-        do not take part (size 2 or 3, stride 1 or 2)."""
-        n, c, h, w = x.shape
-        ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-        y = self._new(n, c, ho, wo, x.device)
-        if self.count is not None:
-            self.count['bytes'] += 2 * (x.numel() + y.numel())
-            self.count['launches'] += 1
-        if x.device.type == 'meta':
-            return y
-        assert x.is_contiguous(memory_format=torch.channels_last), (x.shape, x.stride())
-        st = torch.cuda.current_stream(x.device).cuda_stream
-        rc = self.lib.pam_maxpool_nhwc_bf16(C.c_void_p(st), C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), n, h, w, c, int(size), int(stride))
-        if rc != 0:
-            raise _lib.PamError('pam_maxpool_nhwc_bf16 failed (%d) for %s size %d stride %d' % (rc, tuple(x.shape), size, stride))
-        return y
+from .engine import ActivationArena, ConvEngine, TileCfg, ptr  # noqa: F401
+# the packers lived in this module before packing.py: tests and tools reach them as hrnet_hip.X
+from .packing import (PackedBlock, PackedBneck, PackedConv, PackedDeconv, PackedPointwise64, PackedResNetStem, PackedStem,  # noqa: F401
+                      PackedTail, PackedUp, conv64_image, down48_image, streamed_image)
 
 
 class HipHRNet(ConvEngine):
-    multi_stream = False
     merge_fuse = True           # merged first-level fuse convolutions (False: one launch per convolution)
     merge_up = True
 
@@ -758,7 +23,7 @@ class HipHRNet(ConvEngine):
         self.lib = _lib.load()
         self.device = device
         self._pack(folded_model, device)
-        self.tile_cfg = -1
+        self.tile_cfg = TileCfg.AUTO
         # concurrency: the 2-4 branches of an HR module run on side streams (the coarse branches do not fill the chip)
         # equal priorities: a high-priority stream for the deep branches (whose short kernels wait for CUs behind the fused blocks' long items)
         # doubles the forward -- round 4: 4.2-4.6 ms vs 2.31 ms with side streams 2 / 2 + 3 at priority -1; all three: 2.65 ms
@@ -875,11 +140,6 @@ class HipHRNet(ConvEngine):
         'fused48_fused96_fsum_s32': dict(block2=3, c96_slab=48, fused_sums=True, slab32=True),
     }
 
-    def apply_config(self, name):
-        for k, v in self.CONFIGS[name].items():
-            setattr(self, k, v)
-        self.config_name = name
-
     config_name = 'fused48_fused96'
     block2 = 3                  # bit 0: the finest branch (48 channels; 32 in HipHRNetW32) as one resident-weights fused BasicBlock launch per
                                 # block (k_bblock2_48 / k_bblock2_32), bit 1: the
@@ -907,18 +167,7 @@ class HipHRNet(ConvEngine):
     # meet through a counter in device memory: a branch's chain ends with a signal launch, a one-wave gate launch in front of every sum polls
     # the module's counter.  HRNetPose switches this on around a capture (flags_on) and checks the error word after the first replay: a
     # gate that timed out (two chains mapped onto one in-order hardware queue, a profiler serialising kernels) means a re-capture with stream events.
-    flag_sync = True            # policy: captured replays use flags (HRNetPose._run); False / PAM_FLAG_SYNC=0: stream events everywhere
-    flags_on = False            # state: this forward is being issued with flags
-    flag_host_err = None        # pinned int32 word that receives 1 when a gate of ANY replay times out (HRNetPose reads it before every replay)
-    flag_max_us = 2000000       # a gate gives up after 2 s (a systematic deadlock, found by the check after the first replay) and raises the error word
-    flag_dev_void = None        # device int32 word that receives 1 at any time-out: what the frame kernel's input guard reads (HRNetPose.void_word)
-    _flag_limit = None          # the bound as a device word the gates read when they start (set_flag_limit changes it for captured gates too)
-    _flags = None
-
-    def flag_limit(self):
-        if self._flag_limit is None:
-            self._flag_limit = torch.tensor([int(self.flag_max_us)], dtype=torch.int32, device=self.device)
-        return self._flag_limit
+    # The policy switch, the state and the words HRNetPose hands over (flag_sync, flags_on, flag_host_err, ...) are ConvEngine's.
 
     def set_flag_limit(self, us):
         """Bound (microseconds) of every gate that STARTS after the current stream's work so far, captured ones included (tests force a
@@ -1065,11 +314,6 @@ class HipHRNet(ConvEngine):
                 self._st('sum%d' % i)
         return out
 
-    def features(self, x8):
-        """x8: (N, 8, H, W) channels-last bf16 (RGB + 5 zero channels) -> (N, 48, H/4, W/4) channels-last bf16."""
-        self._keep = []
-        return self._features(x8)
-
     fuse_tail = True            # layer1: conv3 + residual + next conv1 of every Bottleneck in one launch (csrc/pam_pw.hip)
     tail_cfg = 0                # its wave-tile size (0 = automatic)
     fuse_bneck0 = True          # the first block too (its downsample fragments live in registers: they do not fit LDS beside the rest): -0.7 % at 20 crops, -1.2 % at 8
@@ -1084,11 +328,8 @@ class HipHRNet(ConvEngine):
                 cur.wait_stream(st)
         return xs[0]
 
-    def _epoch(self):
-        if self.arena is not None:
-            self.arena.epoch()
-
     def _features(self, x8):
+        """x8: (N, 8, H, W) channels-last bf16 (RGB + 5 zero channels) -> (N, 48 | 32, H/4, W/4) channels-last bf16."""
         if self.flags_on and self.multi_stream and x8.device.type != 'meta':
             self._flag_begin()
         x = self._head(x8)
@@ -1176,29 +417,6 @@ class HipHRNetW32(HipHRNet):
     c96_slab = 0
 
 
-class PackedResNetStem(object):
-    """PoseResNet's conv1 (3 -> 64, 7x7 stride 2, BN folded) packed for ``pam_resnet_stem_nhwc_bf16`` (csrc/pam_resnet.hip; layout:
-    include/pam.h, poseresnet.stem_fragments); the max-pool after it has no weights."""
-
-    def __init__(self, conv, device):
-        from .poseresnet import stem_fragments
-        self.frag = stem_fragments(conv).to(torch.bfloat16).to(device).contiguous()
-        self.bias = (conv.bias.detach().float() if conv.bias is not None else torch.zeros(64)).to(device).contiguous()
-
-
-class PackedDeconv(object):
-    """A 4x4 stride-2 transposed convolution (BN folded) packed for ``pam_deconv4x4s2_nhwc_bf16``: the per-parity weight image of
-    poseresnet.deconv_image (layout: include/pam.h)."""
-
-    def __init__(self, deconv, device):
-        from .poseresnet import deconv_image
-        w = deconv.weight.detach().float()
-        assert tuple(w.shape[2:]) == (4, 4) and deconv.stride == (2, 2) and deconv.padding == (1, 1) and deconv.output_padding == (0, 0)
-        self.cin, self.cout = int(w.shape[0]), int(w.shape[1])
-        self.w = deconv_image(w).to(torch.bfloat16).to(device).contiguous()
-        self.bias = (deconv.bias.detach().float() if deconv.bias is not None else torch.zeros(self.cout)).to(device).contiguous()
-
-
 class HipPoseResNet(ConvEngine):
     """PoseResNet-{50,101,152} (poseresnet.PoseResNet, BN folded) on the conv stack: ONE dependent chain on the caller's stream.
     k_resnet_stem (7x7 conv + ReLU + max-pool), layer1 on HRNet's fused Bottleneck kernels (k_pw1 + k_bneck; or the un-fused
@@ -1210,14 +428,7 @@ class HipPoseResNet(ConvEngine):
     }
     config_name = 'resnet_fused'
     fuse_layer1 = True
-    multi_stream = False
     flag_sync = False           # one chain: HRNetPose captures the stream-event form only
-    flags_on = False
-    flag_host_err = None
-    flag_dev_void = None
-    flag_max_us = 2000000
-    _flag_limit = None
-    _flags = None
     stop_after = None           # tests / tools: 'stem' | 'layer1' .. 'layer4' | 'deconv0' | 'deconv1' -> the forward ends there
     STAGES = ('stem', 'layer1', 'layer2', 'layer3', 'layer4', 'deconv0', 'deconv1', 'deconv2')
 
@@ -1242,20 +453,6 @@ class HipPoseResNet(ConvEngine):
         dl = m.deconv_layers
         self.deconvs = [PackedDeconv(dl[i], device) for i in (0, 3, 6)]
 
-    def apply_config(self, name):
-        for k, v in self.CONFIGS[name].items():
-            setattr(self, k, v)
-        self.config_name = name
-
-    def flag_limit(self):
-        if self._flag_limit is None:
-            self._flag_limit = torch.tensor([int(self.flag_max_us)], dtype=torch.int32, device=self.device)
-        return self._flag_limit
-
-    def _epoch(self):
-        if self.arena is not None:
-            self.arena.epoch()
-
     # -- launches of csrc/pam_resnet.hip ------------------------------------------------------------------------------------------------
     def resnet_stem(self, op, x8):
         """ReLU(conv7x7 s2 (x8) + b), then max-pool 3x3 s2 p1: (N, 8, H, W) -> (N, 64, Hp, Wp) in one launch (k_resnet_stem)."""
@@ -1266,17 +463,12 @@ class HipPoseResNet(ConvEngine):
         y = self._new(n, 64, hp, wp, x8.device)
         nbytes = 2 * (x8.numel() + y.numel() + 64 * 7 * 7 * 8) + 4 * 64
         flops = 2 * n * hc * wc * 64 * 3 * 49                           # counted at the 3 real input channels
-        if self.count is not None:
-            self.count['bytes'] += nbytes; self.count['flops'] += flops; self.count['launches'] += 1
-        if x8.device.type == 'meta':
+        if self._tally(x8, nbytes, flops):
             return y
         assert x8.is_contiguous(memory_format=torch.channels_last)
-        launch = lambda: self.lib.pam_resnet_stem_nhwc_bf16(C.c_void_p(torch.cuda.current_stream(x8.device).cuda_stream), C.c_void_p(x8.data_ptr()),
-                                                             C.c_void_p(op.frag.data_ptr()), C.c_void_p(op.bias.data_ptr()), C.c_void_p(y.data_ptr()), n, h, w)
-        rc = launch()
-        if rc != 0:
-            raise _lib.PamError('pam_resnet_stem_nhwc_bf16 failed (%d) for %s' % (rc, tuple(x8.shape)))
-        self._prof_add(x8, 'k_resnet_stem 7x7 s2 + max-pool', (n, h, w), nbytes, flops, launch)
+        self._run(x8, 'pam_resnet_stem_nhwc_bf16', lambda: self.lib.pam_resnet_stem_nhwc_bf16(
+            self._cur(x8), ptr(x8), ptr(op.frag), ptr(op.bias), ptr(y), n, h, w),
+            nbytes, flops, 'k_resnet_stem 7x7 s2 + max-pool', (n, h, w), what=(' for %s', tuple(x8.shape)))
         return y
 
     def deconv(self, op, x, relu=True):
@@ -1286,26 +478,15 @@ class HipPoseResNet(ConvEngine):
         y = self._new(n, op.cout, 2 * h, 2 * w, x.device)
         nbytes = 2 * (x.numel() + y.numel() + op.cin * op.cout * 16) + 4 * op.cout
         flops = 2 * y.numel() * op.cin * 4                               # 4 live taps per output pixel
-        if self.count is not None:
-            self.count['bytes'] += nbytes; self.count['flops'] += flops; self.count['launches'] += 1
-        if x.device.type == 'meta':
+        if self._tally(x, nbytes, flops):
             return y
         assert x.is_contiguous(memory_format=torch.channels_last)
-        launch = lambda: self.lib.pam_deconv4x4s2_nhwc_bf16(C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream), C.c_void_p(x.data_ptr()),
-                                                             C.c_void_p(op.w.data_ptr()), C.c_void_p(op.bias.data_ptr()), C.c_void_p(y.data_ptr()),
-                                                             n, h, w, op.cin, op.cout, 1 if relu else 0)
-        rc = launch()
-        if rc != 0:
-            raise _lib.PamError('pam_deconv4x4s2_nhwc_bf16 failed (%d) for %s' % (rc, tuple(x.shape)))
-        self._prof_add(x, 'k_deconv4x4s2 %d->%d' % (op.cin, op.cout), (n, h, w, op.cin, op.cout, bool(relu)), nbytes, flops, launch)
+        self._run(x, 'pam_deconv4x4s2_nhwc_bf16', lambda: self.lib.pam_deconv4x4s2_nhwc_bf16(
+            self._cur(x), ptr(x), ptr(op.w), ptr(op.bias), ptr(y), n, h, w, op.cin, op.cout, 1 if relu else 0),
+            nbytes, flops, 'k_deconv4x4s2 %d->%d' % (op.cin, op.cout), (n, h, w, op.cin, op.cout, bool(relu)), what=(' for %s', tuple(x.shape)))
         return y
 
     # -- network ------------------------------------------------------------------------------------------------------------------------
-    def features(self, x8):
-        """x8: (N, 8, H, W) channels-last bf16 (RGB + 5 zero channels) -> (N, 256, H/4, W/4) channels-last bf16."""
-        self._keep = []
-        return self._features(x8)
-
     def _layer1(self, x0):
         n, _, h, w = x0.shape
         small = n * h * w * 512 < 2 ** 31                                # the fused kernels index with 32 bits (as HipHRNet._head)
@@ -1330,6 +511,7 @@ class HipPoseResNet(ConvEngine):
         return self.conv(b['c3'], y, res=r, relu=True)
 
     def _features(self, x8):
+        """x8: (N, 8, H, W) channels-last bf16 (RGB + 5 zero channels) -> (N, 256, H/4, W/4) channels-last bf16."""
         if x8.device.type == 'meta' and self.arena is not None and self.arena.buf is None:
             # a measuring arena (HRNetPose._arena_for sizes the activation arena ONCE, before the first capture): the largest epoch of every
             # configuration -- the un-fused layer1 holds 640 channels at H/4 in one epoch, the fused one 320

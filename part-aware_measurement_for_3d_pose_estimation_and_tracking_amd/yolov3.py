@@ -22,7 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .hrnet_hip import ConvEngine, PackedConv
+from .hrnet_hip import ConvEngine, PackedConv, TileCfg
 
 ANCHORS = [(10, 13), (16, 30), (33, 23), (30, 61), (62, 45), (59, 119), (116, 90), (156, 198), (373, 326)]
 
@@ -292,7 +292,7 @@ class HipDarknet(ConvEngine):
         self.lib = _lib.load()
         self.device = device
         self.count = None
-        self.tile_cfg = -1
+        self.tile_cfg = TileCfg.AUTO
         self.unfuse_wide = True
         layers = model.layers
         n = len(layers)
