@@ -207,6 +207,38 @@ int pam_preprocess_crops(void* stream, int n, const void* const* dev_frames /*de
 int pam_preprocess_crops_ex(void* stream, int n, int n_total, const void* const* dev_frames, int frame_h, int frame_w,
                             const int32_t* dev_view_of, const float* dev_boxes, int out_h, int out_w, int out_c, void* dev_out_bf16,
                             int antialias);
+/* ---- flip test (the official HRNet / Simple Baselines test protocol: TEST.FLIP_TEST, TEST.SHIFT_HEATMAP, TEST.POST_PROCESS) ----
+ * pam_preprocess_crops_flip: the crops of one flip-test forward in one buffer of n_total >= 2 n rows: rows [0, n) as
+ * pam_preprocess_crops_ex writes them (bit for bit), rows [n, 2n) the column reversal of row r - n (out[oy][ox] = plain[oy][out_w-1-ox]
+ * bit for bit on both resize paths: the official input.flip(3), the same samples stored mirrored, not a resample of a mirrored box),
+ * rows [2n, n_total) repeat row 2n - 1 (bucket padding, never decoded).  Other arguments as pam_preprocess_crops_ex. */
+int pam_preprocess_crops_flip(void* stream, int n, int n_total, const void* const* dev_frames, int frame_h, int frame_w,
+                              const int32_t* dev_view_of, const float* dev_boxes, int out_h, int out_w, int out_c, void* dev_out_bf16,
+                              int antialias);
+/* pam_head_decode_flip: pam_head_decode on the merged map of a plain and a mirrored crop, with the optional quarter-pixel offset.
+ * feat: the feature batch of the forward above; crop i's plain features are row i, its mirrored features row flip_row0 + i (flip_row0 = n
+ * in the layout of pam_preprocess_crops_flip).  P / F: the head's maps of the two (the FMA chain of pam_head_heatmaps, bit for bit).
+ * flags, a bit set:
+ *   PAM_FLIP_MERGE    M[j][y][x] = 0.5f * (P[j][y][x] + F[pair(j)][y][xs]): one float32 add, an exact halving; pair = the COCO left/right
+ *                     swap 1<->2, 3<->4, ... 15<->16, 0<->0; xs = hm_w - 1 - x.  Without it M = P and the mirrored rows are never read.
+ *   PAM_FLIP_SHIFT    (with MERGE only) xs = hm_w - x for x >= 1 and hm_w - 1 at x = 0: the official flipped[..., 1:] = flipped[..., :-1]
+ *                     after the flip-back; column 0 keeps its own value.
+ *   PAM_FLIP_QUARTER  the official get_final_preds offset: at an arg-max cell with 1 < px < hm_w - 1 and 1 < py < hm_h - 1 (both strict)
+ *                     x += 0.25 sign(M[py][px+1] - M[py][px-1]), y likewise along the rows; a difference that is neither > 0 nor < 0
+ *                     (zero, NaN) adds nothing.  The fractional cell goes through the box mapping of pam_decode_heatmaps (float64
+ *                     arithmetic, one float32 rounding).  The official maxvals > 0 mask is not applied.
+ * The arg-max (first maximum in flat order; a map with no value above -inf: cell 0, score -inf, no offset) and the score are those of M;
+ * dev_heatmaps_or_null, when given, receives M (n, hm_h, hm_w, 17).  flags == 0: pam_head_decode itself, byte for byte.
+ * dev_scratch: pam_head_decode_flip_scratch_bytes(n, hm_h, hm_w) bytes.  PAM_E_ARG: SHIFT without MERGE, unknown bits, MERGE with
+ * flip_row0 < n, J != 17, C % 8 != 0, a null pointer. */
+#define PAM_FLIP_MERGE 1
+#define PAM_FLIP_SHIFT 2
+#define PAM_FLIP_QUARTER 4
+long long pam_head_decode_flip_scratch_bytes(int n, int hm_h, int hm_w);
+int pam_head_decode_flip(void* stream, int n, int flip_row0, int hm_h, int hm_w, const void* feat_bf16, int C, const float* w,
+                         const float* bias, int J, int flags, float* dev_heatmaps_or_null, const int32_t* dev_view_of,
+                         const int32_t* dev_slot_of, const float* dev_boxes, int max_dets, double* dev_det, float* dev_kp_xyc,
+                         void* dev_scratch);
 int pam_decode_heatmaps(void* stream, int n, const float* dev_heatmaps, int nchw, int hm_h, int hm_w,
                         const int32_t* dev_view_of, const int32_t* dev_slot_of, const float* dev_boxes,
                         int max_dets, double* dev_det, float* dev_kp_xyc /*optional n*17*3 (x,y,conf) or NULL*/);

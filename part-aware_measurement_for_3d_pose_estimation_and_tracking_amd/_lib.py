@@ -64,6 +64,7 @@ _SIGS = {
     'pam_op_hyp_cost': (_I, [_P, _I, _P, _P, _I, _P, _P, _P]),
     'pam_preprocess_crops': (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
     'pam_preprocess_crops_ex': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I]),
+    'pam_preprocess_crops_flip': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I]),
     'pam_decode_heatmaps': (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     'pam_clock_probe': (_I, [_P, _P, _I]),
     'pam_conv2d_nhwc_bf16': (_I, [_P, _P, _P, _P, _P, _P, _P] + [_I] * 11),
@@ -105,6 +106,8 @@ _SIGS = {
     'pam_head_decode': (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
     'pam_head_decode_soft_scratch_bytes': (C.c_longlong, [_I, _I, _I]),
     'pam_head_decode_soft': (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _I, C.c_float, _P, _P, _P, _P, _I, _P, _P, _P]),
+    'pam_head_decode_flip_scratch_bytes': (C.c_longlong, [_I, _I, _I]),
+    'pam_head_decode_flip': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
     'pam_head_heatmaps': (_I, [_P, _I, _P, _I, _P, _P, _I, _P]),
     'pam_resize_frames': (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
     'pam_upsample_concat_nhwc_bf16': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I]),

@@ -18,92 +18,16 @@
 // in float32: PIL's own uint8 rounding between its two passes is not reproduced).  Crops n_src .. (grid) repeat crop n_src - 1: a replay
 // bucket larger than the call (HRNetPose pads a batch to a multiple of graph_bucket) needs no padded box table.
 constexpr int AA_MAXT = 24;             // taps per axis at most (down-scaling by up to 11.5)
-__global__ __launch_bounds__(256) void k_preprocess_crops(int n_src, const uint8_t* const* __restrict__ frames, int H, int W,
-                                                          const int* __restrict__ view_of, const float* __restrict__ boxes,
-                                                          int oh, int ow, int oc, uint16_t* __restrict__ out, int antialias) {
-    const int crop = blockIdx.y, src = min(crop, n_src - 1);
-    const int px = blockIdx.x * blockDim.x + threadIdx.x;
-    if (px >= oh * ow) return;
-    const int oy = px / ow, ox = px % ow;
-    const uint8_t* __restrict__ img = frames[view_of[src]];
-    const float bx = boxes[src * 4 + 0], by = boxes[src * 4 + 1], bw = boxes[src * 4 + 2], bh = boxes[src * 4 + 3];
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, istd[3] = {1.0f / 0.229f, 1.0f / 0.224f, 1.0f / 0.225f};
-    uint16_t o[3];
-    if (!antialias) {
-        float sx = bx + (ox + 0.5f) * (bw / (float)ow) - 0.5f;
-        float sy = by + (oy + 0.5f) * (bh / (float)oh) - 0.5f;
-        sx = fminf(fmaxf(sx, 0.0f), (float)(W - 1));
-        sy = fminf(fmaxf(sy, 0.0f), (float)(H - 1));
-        const int x0 = (int)sx, y0 = (int)sy;
-        const int x1 = min(x0 + 1, W - 1), y1 = min(y0 + 1, H - 1);
-        const float fx = sx - (float)x0, fy = sy - (float)y0;
-        const uint8_t* r0 = img + ((size_t)y0 * W) * 3;
-        const uint8_t* r1 = img + ((size_t)y1 * W) * 3;
-        // the two pixels of a row are 6 consecutive bytes: ONE unaligned 8-byte load per row instead of six byte loads (the kernel was bound by
-        // the texture-address unit: 12 one-byte gathers per output pixel); not for the last two columns (x1 is clamped there / the load would
-        // leave the row)
-        uint8_t t0[6], t1[6];
-        if (x0 + 2 < W) {
-            struct __attribute__((packed)) U8 { uint32_t x, y; };              // alignment 1: the backend emits one dwordx2 load (unaligned access is on)
-            const U8 q0 = *(const U8*)(r0 + x0 * 3), q1 = *(const U8*)(r1 + x0 * 3);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                t0[k] = (uint8_t)((k < 4 ? q0.x >> (8 * k) : q0.y >> (8 * (k - 4))) & 0xff);
-                t1[k] = (uint8_t)((k < 4 ? q1.x >> (8 * k) : q1.y >> (8 * (k - 4))) & 0xff);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { t0[k] = r0[x0 * 3 + k]; t0[3 + k] = r0[x1 * 3 + k]; t1[k] = r1[x0 * 3 + k]; t1[3 + k] = r1[x1 * 3 + k]; }
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {          // c indexes RGB; source is BGR
-            const int sc = 2 - c;
-            const float a = (float)t0[sc], b = (float)t0[3 + sc];
-            const float cc = (float)t1[sc], d = (float)t1[3 + sc];
-            const float top = a + (b - a) * fx, bot = cc + (d - cc) * fx;
-            const float v = (top + (bot - top) * fy) * (1.0f / 255.0f);
-            o[c] = f32_to_bf16((v - mean[c]) * istd[c]);
-        }
-    } else {
-        const float scx = bw / (float)ow, scy = bh / (float)oh, supx = fmaxf(scx, 1.0f), supy = fmaxf(scy, 1.0f);
-        const float cx = bx + (ox + 0.5f) * scx, cy = by + (oy + 0.5f) * scy;
-        // (a box wholly right of / below the frame: the window is the last column / row, whose weight is 0 there -- a black pixel, never a read past the frame)
-        const int xlo = min(max(0, (int)floorf(bx)), W - 1), xhi = max(xlo + 1, min(W, (int)ceilf(bx + bw)));
-        const int ylo = min(max(0, (int)floorf(by)), H - 1), yhi = max(ylo + 1, min(H, (int)ceilf(by + bh)));
-        int x0 = max(xlo, (int)(cx - supx + 0.5f)), x1 = min(xhi, (int)(cx + supx + 0.5f));
-        int y0 = max(ylo, (int)(cy - supy + 0.5f)), y1 = min(yhi, (int)(cy + supy + 0.5f));
-        if (x1 <= x0) { x0 = min(max((int)cx, xlo), xhi - 1); x1 = x0 + 1; }
-        if (y1 <= y0) { y0 = min(max((int)cy, ylo), yhi - 1); y1 = y0 + 1; }
-        // beyond the limit the window is cut to the AA_MAXT taps nearest the centre (symmetric: no shift of the sampled position)
-        if (x1 - x0 > AA_MAXT) { x0 = min(max((int)floorf(cx - 0.5f * AA_MAXT + 0.5f), x0), x1 - AA_MAXT); x1 = x0 + AA_MAXT; }
-        if (y1 - y0 > AA_MAXT) { y0 = min(max((int)floorf(cy - 0.5f * AA_MAXT + 0.5f), y0), y1 - AA_MAXT); y1 = y0 + AA_MAXT; }
-        const float isx = 1.0f / supx, isy = 1.0f / supy;
-        float acc[3] = {0.f, 0.f, 0.f}, wsum = 0.f;
-        for (int y = y0; y < y1; ++y) {
-            const float wy = fmaxf(0.0f, 1.0f - fabsf(((float)y + 0.5f - cy) * isy));
-            const uint8_t* r = img + ((size_t)y * W) * 3;
-            float row[3] = {0.f, 0.f, 0.f}, wr = 0.f;
-            for (int x = x0; x < x1; ++x) {
-                const float wx = fmaxf(0.0f, 1.0f - fabsf(((float)x + 0.5f - cx) * isx));
-                row[0] += wx * (float)r[x * 3 + 2]; row[1] += wx * (float)r[x * 3 + 1]; row[2] += wx * (float)r[x * 3 + 0];
-                wr += wx;
-            }
-            acc[0] += wy * row[0]; acc[1] += wy * row[1]; acc[2] += wy * row[2];
-            wsum += wy * wr;
-        }
-        const float inv = wsum > 0.f ? 1.0f / (wsum * 255.0f) : 0.f;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o[c] = f32_to_bf16((acc[c] * inv - mean[c]) * istd[c]);
-    }
-    if (oc == 3) {
-        uint16_t* dst = out + (((size_t)crop * oh + oy) * ow + ox) * 3;
-        dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
-    } else {            // 8-channel form for the MFMA conv kernel (Cin % 8 == 0): RGB + 5 zero channels, one 16-B store
-        uint4 v;
-        v.x = (uint32_t)o[0] | ((uint32_t)o[1] << 16); v.y = (uint32_t)o[2]; v.z = 0; v.w = 0;
-        *(uint4*)(out + (((size_t)crop * oh + oy) * ow + ox) * 8) = v;
-    }
-}
+#define CROP_KERNEL k_preprocess_crops
+#define CROP_FLIP 0
+#include "pam_crop_kernel.inc"
+#undef CROP_KERNEL
+#undef CROP_FLIP
+#define CROP_KERNEL k_preprocess_crops_flip             // plain + mirrored rows of a flip-test forward (see pam_crop_kernel.inc)
+#define CROP_FLIP 1
+#include "pam_crop_kernel.inc"
+#undef CROP_KERNEL
+#undef CROP_FLIP
 
 struct Best { float v; int i; };
 __device__ __forceinline__ Best better(Best a, Best b) {    // larger value wins; ties -> smaller flat index (np.argmax)
@@ -435,6 +359,183 @@ extern "C" int pam_head_decode_soft(void* stream, int n, int hm_h, int hm_w, con
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
 }
 
+// ---- flip test: head of a plain and a mirrored crop merged in registers, arg-max, optional quarter-pixel offset -------------------------
+// The official HRNet / Simple Baselines test protocol (FLIP_TEST, SHIFT_HEATMAP, POST_PROCESS): M[j][y][x] = 0.5f * (P[j][y][x] +
+// F[pair(j)][y][xs]) with P / F the head's maps of the plain / the mirrored crop (the FMA chain of k_head, bit for bit), pair() the COCO
+// left/right swap, xs = w - 1 - x, or with the one-column shift xs = w - x for x >= 1 and w - 1 at x = 0 (the official
+// flipped[..., 1:] = flipped[..., :-1] after the flip-back: column 0 keeps its own value).  One float32 add, then an exact halving.
+__host__ __device__ constexpr int flip_pair(int j) { return j == 0 ? 0 : ((j & 1) ? j + 1 : j - 1); }      // 1<->2, 3<->4, ... 15<->16
+__device__ __forceinline__ int flip_column(int x, int hm_w, int shift) { return shift ? (x ? hm_w - x : hm_w - 1) : hm_w - 1 - x; }
+
+// k_head_argmax_flip: k_head_argmax with a second accumulator set fed from pixel (y, xs) of crop flip_row0 + crop.  Workgroup = 256
+// consecutive flat pixels of one crop; a tile may straddle rows, the mirrored pixel may lie in another tile's range (it is only read).
+// The lanes of a row segment read their mirrored pixels at descending addresses, each still as full 16-byte pieces.  The joint swap is
+// a compile-time permutation of registers.  Weights through wave-uniform scalar loads as in k_head_argmax.
+template <int JN>
+__global__ __launch_bounds__(HEAD_T) void k_head_argmax_flip(int HW, int tiles, const uint16_t* __restrict__ feat, int C,
+                                                             const float* __restrict__ w, const float* __restrict__ bias,
+                                                             float* __restrict__ heat /* optional */, Best* __restrict__ cand,
+                                                             int hm_w, int flip_row0, int shift) {
+    extern __shared__ __attribute__((aligned(16))) float hsm[];       // [HEAD_T][JN + 1]: the merged values on their way to the reduction
+    const float* __restrict__ ws = w;
+    const int crop = blockIdx.x / tiles, tile = blockIdx.x - crop * tiles;
+    const int lp = tile * HEAD_T + threadIdx.x;
+    const bool ok = lp < HW;
+    float acc[JN], acf[JN];
+#pragma unroll
+    for (int j = 0; j < JN; ++j) acc[j] = acf[j] = bias ? bias[j] : 0.0f;
+    if (ok) {
+        const int y = lp / hm_w, x = lp - y * hm_w;
+        const uint16_t* f = feat + ((size_t)crop * HW + lp) * C;
+        const uint16_t* g = feat + ((size_t)(flip_row0 + crop) * HW + y * hm_w + flip_column(x, hm_w, shift)) * C;
+        auto fma8 = [&](float (&a)[JN], const uint4 v, int c8) {
+            const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+            float xk[8];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { xk[2 * k] = bf16_lo(d[k]); xk[2 * k + 1] = bf16_hi(d[k]); }
+#pragma unroll
+            for (int j = 0; j < JN; ++j)
+#pragma unroll
+                for (int k = 0; k < 8; ++k) a[j] = fmaf(xk[k], ws[j * C + c8 + k], a[j]);
+        };
+        if (C == 48) {                                   // HRNet-W48: the six pieces of each of the two pixels in flight at once
+            uint4 v[6], u[6];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) { v[q] = *(const uint4*)(f + 8 * q); u[q] = *(const uint4*)(g + 8 * q); }
+#pragma unroll
+            for (int q = 0; q < 6; ++q) { fma8(acc, v[q], 8 * q); fma8(acf, u[q], 8 * q); }
+        } else {
+            for (int c8 = 0; c8 < C; c8 += 8) {
+                const uint4 v = *(const uint4*)(f + c8), u = *(const uint4*)(g + c8);
+                fma8(acc, v, c8); fma8(acf, u, c8);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < JN; ++j) acc[j] = 0.5f * (acc[j] + acf[flip_pair(j)]);
+        if (heat) {
+            float* o = heat + ((size_t)crop * HW + lp) * JN;
+#pragma unroll
+            for (int j = 0; j < JN; ++j) o[j] = acc[j];
+        }
+    }
+    // the reduction of k_head_argmax: values through LDS pixel-major, 8 lanes per joint scan 32 pixels each, 3 shuffles
+    float* vs = hsm;                                                  // [HEAD_T][JN + 1]
+#pragma unroll
+    for (int j = 0; j < JN; ++j) vs[threadIdx.x * (JN + 1) + j] = ok ? acc[j] : -__builtin_huge_valf();
+    __syncthreads();
+    if (threadIdx.x < JN * 8) {
+        const int j = threadIdx.x >> 3, part = threadIdx.x & 7;
+        Best b; b.v = -__builtin_huge_valf(); b.i = 0x7fffffff;
+#pragma unroll 8
+        for (int q = 0; q < HEAD_T / 8; ++q) {
+            const int px = q * 8 + part;
+            const float v = vs[px * (JN + 1) + j];
+            if (v > b.v) { b.v = v; b.i = tile * HEAD_T + px; }            // strictly greater: the first maximum of the part
+        }
+#pragma unroll
+        for (int off = 4; off >= 1; off >>= 1) {
+            Best o; o.v = __shfl_xor(b.v, off, 64); o.i = __shfl_xor(b.i, off, 64);
+            b = better(b, o);
+        }
+        if (part == 0) cand[((size_t)crop * tiles + tile) * JN + j] = b;
+    }
+}
+// One value of the head's map of joint jj at the pixel whose features start at f, recomputed with the head's own chain: the map's own bits.
+__device__ __forceinline__ float head_chain(const uint16_t* __restrict__ f, int C, const float* __restrict__ w, const float* __restrict__ bias, int jj) {
+    float a = bias ? bias[jj] : 0.0f;
+    for (int c8 = 0; c8 < C; c8 += 8) {
+        const uint4 v = *(const uint4*)(f + c8);
+        const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            a = fmaf(bf16_lo(d[k]), w[jj * C + c8 + 2 * k], a);
+            a = fmaf(bf16_hi(d[k]), w[jj * C + c8 + 2 * k + 1], a);
+        }
+    }
+    return a;
+}
+// k_argmax_finish with the official get_final_preds offset: at an arg-max strictly inside (1 < px < w - 1 and 1 < py < h - 1) the cell
+// moves a quarter towards the higher neighbour along each axis; a difference that is neither > 0 nor < 0 (zero, NaN) moves nothing.
+// The winner is known only after the fold, so its four neighbours are recomputed from the features: 8 lanes per joint, lane `part`
+// takes neighbour part & 3 (x + 1, x - 1, y + 1, y - 1) of the plain (part < 4) or the mirrored crop (MERGE only) -- one chain of C FMAs
+// each, side by side (one lane per joint ran the 8 chains one after the other: + 9 us at C = 48, + 26 us at C = 256 for 20 crops) --
+// and three shuffles form the merged values and the two differences.  Every lane of a joint folds the tiles (the same loads).
+#define FIN_T 192             // 17 joints x 8 lanes = 136 lanes in 3 waves; a joint's 8 lanes sit in one wave
+template <bool MERGE>
+__global__ __launch_bounds__(FIN_T) void k_argmax_finish_flip(int tiles, const Best* __restrict__ cand, int hm_h, int hm_w,
+                                                              const uint16_t* __restrict__ feat, int C, const float* __restrict__ w,
+                                                              const float* __restrict__ bias, int flip_row0, int shift, int post,
+                                                              const int* __restrict__ view_of, const int* __restrict__ slot_of,
+                                                              const float* __restrict__ boxes, int max_dets, double* __restrict__ det,
+                                                              float* __restrict__ kp) {
+    const int crop = blockIdx.x, j = threadIdx.x >> 3, part = threadIdx.x & 7;
+    if (j >= J) return;                                  // whole 8-lane groups leave: no shuffle below reads a lane that left
+    Best b; b.v = -__builtin_huge_valf(); b.i = 0x7fffffff;
+    for (int t0 = 0; t0 < tiles; t0 += 8) {
+        Best c[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int t = min(t0 + q, tiles - 1);
+            c[q] = cand[((size_t)crop * tiles + t) * J + j];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if (t0 + q < tiles && c[q].v > b.v) b = c[q];
+    }
+    if (b.i == 0x7fffffff) b.i = 0;        // no value above -inf: cell 0 (never strictly inside: no offset)
+    const int py = b.i / hm_w, px = b.i - py * hm_w, HW = hm_h * hm_w;
+    const bool inside = post && 1 < px && px < hm_w - 1 && 1 < py && py < hm_h - 1;      // the same for the 8 lanes of a joint
+    float v = 0.0f;
+    if (inside && (MERGE || part < 4)) {
+        const int c = part & 3, y = py + (c == 2) - (c == 3), x = px + (c == 0) - (c == 1);
+        v = part < 4 ? head_chain(feat + ((size_t)crop * HW + y * hm_w + x) * C, C, w, bias, j)
+                     : head_chain(feat + ((size_t)(flip_row0 + crop) * HW + y * hm_w + flip_column(x, hm_w, shift)) * C, C, w, bias, flip_pair(j));
+    }
+    if constexpr (MERGE) v = 0.5f * (v + __shfl_xor(v, 4, 64));       // lanes 0 .. 3: plain + mirrored, the sum k_head_argmax_flip forms
+    const float e = v - __shfl_xor(v, 1, 64);                        // lane 0: M[py][px+1] - M[py][px-1]; lane 2: M[py+1][px] - M[py-1][px]
+    const float ey = __shfl_xor(e, 2, 64);
+    if (part != 0) return;
+    double dy = 0.0, dx = 0.0;
+    if (inside) {
+        dx = e > 0.0f ? 0.25 : (e < 0.0f ? -0.25 : 0.0);
+        dy = ey > 0.0f ? 0.25 : (ey < 0.0f ? -0.25 : 0.0);
+    }
+    double* row = det + ((size_t)view_of[crop] * max_dets + slot_of[crop]) * J * 3;
+    write_keypoint_at(j, (double)py + dy, (double)px + dx, b.v, hm_h, hm_w, boxes + crop * 4, row, kp ? kp + (size_t)crop * J * 3 : nullptr);
+}
+
+extern "C" long long pam_head_decode_flip_scratch_bytes(int n, int hm_h, int hm_w) { return pam_head_decode_scratch_bytes(n, hm_h, hm_w); }
+
+extern "C" int pam_head_decode_flip(void* stream, int n, int flip_row0, int hm_h, int hm_w, const void* feat_bf16, int C, const float* w,
+                                    const float* bias, int J_, int flags, float* dev_heatmaps_or_null, const int32_t* dev_view_of,
+                                    const int32_t* dev_slot_of, const float* dev_boxes, int max_dets, double* dev_det, float* dev_kp_xyc,
+                                    void* dev_scratch) {
+    const int merge = flags & PAM_FLIP_MERGE, shift = (flags & PAM_FLIP_SHIFT) ? 1 : 0, post = (flags & PAM_FLIP_QUARTER) ? 1 : 0;
+    if (n < 0 || !feat_bf16 || !w || !dev_view_of || !dev_slot_of || !dev_boxes || !dev_det || !dev_scratch || hm_h <= 0 || hm_w <= 0 ||
+        C <= 0 || C % 8 != 0 || J_ != PAM_J || (flags & ~(PAM_FLIP_MERGE | PAM_FLIP_SHIFT | PAM_FLIP_QUARTER)) || (shift && !merge) ||
+        (merge && flip_row0 < n))
+        return PAM_E_ARG;
+    if (flags == 0)                                                    // nothing asked for: pam_head_decode itself
+        return pam_head_decode(stream, n, hm_h, hm_w, feat_bf16, C, w, bias, J_, dev_heatmaps_or_null, dev_view_of, dev_slot_of, dev_boxes,
+                               max_dets, dev_det, dev_kp_xyc, dev_scratch);
+    if (n == 0) return PAM_OK;
+    const int HW = hm_h * hm_w, tiles = (HW + HEAD_T - 1) / HEAD_T;
+    const uint16_t* f = (const uint16_t*)feat_bf16;
+    if (merge) {
+        hipLaunchKernelGGL((k_head_argmax_flip<PAM_J>), dim3(n * tiles), dim3(HEAD_T), (size_t)HEAD_T * (J_ + 1) * sizeof(float),
+                           (hipStream_t)stream, HW, tiles, f, C, w, bias, dev_heatmaps_or_null, (Best*)dev_scratch, hm_w, flip_row0, shift);
+        hipLaunchKernelGGL((k_argmax_finish_flip<true>), dim3(n), dim3(FIN_T), 0, (hipStream_t)stream, tiles, (const Best*)dev_scratch, hm_h, hm_w,
+                           f, C, w, bias, flip_row0, shift, post, dev_view_of, dev_slot_of, dev_boxes, max_dets, dev_det, dev_kp_xyc);
+    } else {                                                           // quarter-pixel offset on the plain maps: the mirrored rows are never read
+        const size_t lds = (size_t)J_ * C * sizeof(float) + (size_t)(HEAD_T / 64) * J_ * sizeof(Best) + (size_t)HEAD_T * (J_ + 1) * sizeof(float);
+        hipLaunchKernelGGL((k_head_argmax<PAM_J, false>), dim3(n * tiles), dim3(HEAD_T), lds, (hipStream_t)stream, HW, tiles, f, C, w, bias,
+                           dev_heatmaps_or_null, (Best*)dev_scratch, hm_w, 0.0f, (Soft*)nullptr);
+        hipLaunchKernelGGL((k_argmax_finish_flip<false>), dim3(n), dim3(FIN_T), 0, (hipStream_t)stream, tiles, (const Best*)dev_scratch, hm_h, hm_w,
+                           f, C, w, bias, 0, 0, post, dev_view_of, dev_slot_of, dev_boxes, max_dets, dev_det, dev_kp_xyc);
+    }
+    return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+}
+
 extern "C" int pam_preprocess_crops_ex(void* stream, int n, int n_total, const void* const* dev_frames, int frame_h, int frame_w,
                                        const int32_t* dev_view_of, const float* dev_boxes, int out_h, int out_w,
                                        int out_c, void* dev_out_bf16, int antialias) {
@@ -449,6 +550,17 @@ extern "C" int pam_preprocess_crops(void* stream, int n, const void* const* dev_
                                     const int32_t* dev_view_of, const float* dev_boxes, int out_h, int out_w,
                                     int out_c, void* dev_out_bf16) {
     return pam_preprocess_crops_ex(stream, n, n, dev_frames, frame_h, frame_w, dev_view_of, dev_boxes, out_h, out_w, out_c, dev_out_bf16, 0);
+}
+
+extern "C" int pam_preprocess_crops_flip(void* stream, int n, int n_total, const void* const* dev_frames, int frame_h, int frame_w,
+                                         const int32_t* dev_view_of, const float* dev_boxes, int out_h, int out_w,
+                                         int out_c, void* dev_out_bf16, int antialias) {
+    if (n < 0 || n_total < 2 * (long long)n || !dev_frames || !dev_view_of || !dev_boxes || !dev_out_bf16 || out_h <= 0 || out_w <= 0 || (out_c != 3 && out_c != 8)) return PAM_E_ARG;
+    if (n == 0) return PAM_OK;
+    dim3 grid((out_h * out_w + 255) / 256, n_total);
+    hipLaunchKernelGGL(k_preprocess_crops_flip, grid, dim3(256), 0, (hipStream_t)stream, n, (const uint8_t* const*)dev_frames,
+                       frame_h, frame_w, dev_view_of, dev_boxes, out_h, out_w, out_c, (uint16_t*)dev_out_bf16, antialias ? 1 : 0);
+    return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
 }
 
 extern "C" int pam_decode_heatmaps(void* stream, int n, const float* dev_heatmaps, int nchw, int hm_h, int hm_w,

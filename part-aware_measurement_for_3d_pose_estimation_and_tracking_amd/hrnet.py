@@ -295,8 +295,11 @@ class HRNetPose(object):
 
     def __init__(self, c, nof_joints, checkpoint_path, model_name='HRNet', resolution=(384, 288), hrpose_args=None,
                  device=0, dtype=torch.bfloat16, use_graph=True, seed=0, max_dets=16, backend='hip', graph_bucket=4,
-                 shard_crops=False, group=None, autotune=False, max_crops=32, antialias=False):
+                 shard_crops=False, group=None, autotune=False, max_crops=32, antialias=False, flip_test=False, shift_heatmap=True,
+                 post_process=False, soft_beta=None):
         from . import poseresnet
+        # the decode options first: a refused combination raises before anything touches a device
+        self.soft_beta, self.flip_test, self.shift_heatmap, self.post_process = soft_beta, flip_test, shift_heatmap, post_process
         if model_name in poseresnet.MODEL_NAMES:
             # simple-HRNet's second family: c is the ResNet depth (Bottleneck ResNets only; 18 / 34 are BasicBlock networks)
             if int(c) != c or int(c) not in poseresnet.DEPTHS:
@@ -613,7 +616,7 @@ class HRNetPose(object):
             # A forward beyond the arena gets a new one of TWICE its need (the captures made so far keep the old one: their kernels hold
             # its addresses, and a captured graph is never destroyed, _lib.new_graph): a crop count that creeps upwards costs at most
             # 4 x the largest forward's need in total
-            cap = self.max_crops * self._arena_bytes_per_crop
+            cap = self.forward_crops(self.max_crops) * self._arena_bytes_per_crop
             ar = ActivationArena(self.device, max(need, min(2 * need, cap)) if ar is None else 2 * need)
             self._arenas[slot] = ar
         return ar
@@ -634,7 +637,7 @@ class HRNetPose(object):
         self.max_crops = max(self.max_crops, buckets[0] if buckets else 0)
         for slot in slots:
             for n in buckets:
-                if (n, kind, slot) not in self._graphs:
+                if (self.forward_crops(n), kind, slot) not in self._graphs:
                     self._run(self.input_buffer(n, slot), kind, slot)
         torch.cuda.synchronize(self.device)
         return dict(buckets=sorted(buckets), captures=self.captures - c0, seconds=time.perf_counter() - t0, arena_bytes=self.arena_bytes())
@@ -670,9 +673,14 @@ class HRNetPose(object):
     fsum_max_crops = int(os.environ.get('PAM_FSUM_MAX', '20'))      # tuning hooks of config_for's rule
     s32_max_crops = int(os.environ.get('PAM_S32_MAX', '12'))        # up to here the deep branches' 3x3 layers run with 32-channel slabs (-8 ... -10 % at 2-6 crops, -2 % at 12)
 
+    def forward_crops(self, n):
+        """Crops in the forward that serves n boxes: 2n under the flip test (n plain rows, then their n mirrors)."""
+        return 2 * n if self.flip_test else n
+
     def input_buffer(self, n, slot=0):
-        """The (N,3,H,W) channels-last bf16 tensor the preprocessing kernel writes; the replay's own input when one
-        exists, so no copy is needed."""
+        """The (N,3,H,W) channels-last bf16 tensor the preprocessing kernel writes for n boxes (N = forward_crops(n): under the flip test
+        the mirrored crops follow the plain ones); the replay's own input when one exists, so no copy is needed."""
+        n = self.forward_crops(n)
         g = self._graphs.get((n, 'features', slot)) or self._graphs.get((n, 'heatmaps', slot))
         if g is not None:
             return g[1]
@@ -682,13 +690,15 @@ class HRNetPose(object):
     # -- HIP kernels around it -----------------------------------------------------------------------------------------
     def preprocess(self, frame_ptrs, frame_h, frame_w, view_of, boxes, out):
         """frame_ptrs: int64 device tensor of per-view frame addresses; view_of int32 (N), boxes float32 (N,4) xywh.  out may hold more
-        crops than N (a replay bucket): the extra ones repeat the last crop."""
+        crops than N (a replay bucket): the extra ones repeat the last crop.  Under the flip test out (``input_buffer``) holds at least
+        2N rows: N plain crops, their N mirrors, then repeats of the last mirror."""
         H, W = self.resolution
         st = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self.lib.pam_preprocess_crops_ex(C.c_void_p(st), int(view_of.numel()), int(out.shape[0]), C.c_void_p(frame_ptrs.data_ptr()),
-                                              int(frame_h), int(frame_w), C.c_void_p(view_of.data_ptr()),
-                                              C.c_void_p(boxes.data_ptr()), H, W, int(out.shape[1]), C.c_void_p(out.data_ptr()),
-                                              1 if self.antialias else 0)
+        fn = self.lib.pam_preprocess_crops_flip if self.flip_test else self.lib.pam_preprocess_crops_ex
+        rc = fn(C.c_void_p(st), int(view_of.numel()), int(out.shape[0]), C.c_void_p(frame_ptrs.data_ptr()),
+                int(frame_h), int(frame_w), C.c_void_p(view_of.data_ptr()),
+                C.c_void_p(boxes.data_ptr()), H, W, int(out.shape[1]), C.c_void_p(out.data_ptr()),
+                1 if self.antialias else 0)
         if rc != 0:
             raise _lib.PamError('pam_preprocess_crops failed: %d' % rc)
 
@@ -705,16 +715,48 @@ class HRNetPose(object):
         if rc != 0:
             raise _lib.PamError('pam_decode_heatmaps failed: %d' % rc)
 
-    soft_beta = None        # None: hard arg-max decode (the parity mode).  A float > 0: soft-arg-max with that inverse temperature
-                            # (sub-pixel keypoints = softmax(beta * heat-map)-weighted mean position; confidence = the maximum).
+    # Decode options, readable and writable as attributes (flip_test before the first capture: it doubles the forward).
+    #   soft_beta      None: hard arg-max decode (the parity mode).  A float > 0: soft-arg-max with that inverse temperature
+    #                  (sub-pixel keypoints = softmax(beta * heat-map)-weighted mean position; confidence = the maximum).
+    #   flip_test      the official test protocol (TEST.FLIP_TEST): every forward carries each crop and its mirror, and the decode runs on
+    #                  the average of the plain map and the mirrored-back, left/right-swapped map (pam_head_decode_flip).
+    #   shift_heatmap  (TEST.SHIFT_HEATMAP; matters under flip_test only) the mirrored-back map moves one column to the right first.
+    #   post_process   (TEST.POST_PROCESS) the arg-max moves a quarter of a cell towards the higher neighbour along each axis.
+    # soft_beta with flip_test or post_process is refused (ValueError): the soft-arg-max has no merged-map form.
+    _soft_beta, _flip_test, _post_process, shift_heatmap = None, False, False, True
+
+    def _decode_option(name):
+        def get(self):
+            return getattr(self, '_' + name)
+
+        def put(self, value):
+            value = (None if value is None else float(value)) if name == 'soft_beta' else bool(value)
+            now = dict(soft_beta=self._soft_beta, flip_test=self._flip_test, post_process=self._post_process)
+            now[name] = value
+            if now['soft_beta'] is not None and (now['flip_test'] or now['post_process']):
+                raise ValueError('HRNetPose: soft_beta cannot be combined with flip_test or post_process (got soft_beta=%r, flip_test=%r, '
+                                 'post_process=%r)' % (now['soft_beta'], now['flip_test'], now['post_process']))
+            if name == 'flip_test' and value != self._flip_test and getattr(self, '_graphs', None):
+                raise RuntimeError('HRNetPose: flip_test changes the size of every forward; set it before the first capture')
+            setattr(self, '_' + name, value)
+        return property(get, put)
+    soft_beta, flip_test, post_process = _decode_option('soft_beta'), _decode_option('flip_test'), _decode_option('post_process')
+    del _decode_option
+
+    def decode_flags(self):
+        """The flag word of pam_head_decode_flip for this object's options (0: the plain decode)."""
+        return (1 | (2 if self.shift_heatmap else 0) if self.flip_test else 0) | (4 if self.post_process else 0)
 
     def head_decode(self, f, view_of, slot_of, boxes, det, kp=None, heat=None, n=None):
         """Final 1x1 convolution + arg-max decode (soft-arg-max when ``self.soft_beta`` is set) in one pass over the features f
         (N,c,h,w channels-last bf16): det rows as ``decode``; the heat-maps are written only when ``heat`` (N,17,h,w float32
-        channels-last) is given.  n: decode only the first n crops of f."""
+        channels-last) is given.  n: decode only the first n crops of f.  Under the flip test f is the feature batch of a forward that
+        ``preprocess`` filled (n plain crops, then their n mirrors: n defaults to half of f) and the decode runs on the merged maps; with
+        ``post_process`` the arg-max carries the quarter-cell offset.  With every option off the launches are pam_head_decode's."""
         nf, c, h, w = f.shape
-        n = nf if n is None else n
-        assert f.is_contiguous(memory_format=torch.channels_last) and f.dtype == torch.bfloat16 and n <= nf
+        flags = self.decode_flags()
+        n = (nf // 2 if flags & 1 else nf) if n is None else n
+        assert f.is_contiguous(memory_format=torch.channels_last) and f.dtype == torch.bfloat16 and self.forward_crops(n) <= nf
         soft = self.soft_beta is not None
         need = int((self.lib.pam_head_decode_soft_scratch_bytes if soft else self.lib.pam_head_decode_scratch_bytes)(n, h, w))
         if getattr(self, '_hd_scratch', None) is None or self._hd_scratch.numel() < need:
@@ -728,10 +770,12 @@ class HRNetPose(object):
                 C.c_void_p(self._hd_scratch.data_ptr()))
         if soft:
             rc = self.lib.pam_head_decode_soft(*(head + (C.c_float(float(self.soft_beta)),) + tail))
+        elif flags:                                       # (same scratch size as the plain decode: pam_head_decode_flip_scratch_bytes)
+            rc = self.lib.pam_head_decode_flip(*(head[:2] + (n,) + head[2:] + (flags,) + tail))
         else:
             rc = self.lib.pam_head_decode(*(head + tail))
         if rc != 0:
-            raise _lib.PamError('pam_head_decode%s failed: %d' % ('_soft' if soft else '', rc))
+            raise _lib.PamError('pam_head_decode%s failed: %d' % ('_soft' if soft else ('_flip' if flags else ''), rc))
 
     # -- the reference-shaped entry point ------------------------------------------------------------------------------
     def predict(self, person_bbox_list, batch_size=20, conf_threshold=0.4):

@@ -116,6 +116,13 @@ class ivclabpose(object):
             sb = self.pose_detector.get('SOFT_ARGMAX_BETA') if isinstance(self.pose_detector, dict) else getattr(self.pose_detector, 'SOFT_ARGMAX_BETA', None)
             if sb:
                 self.pose_model.soft_beta = float(sb)
+            # optional keys under the official names (TEST.FLIP_TEST / SHIFT_HEATMAP / POST_PROCESS of the HRNet and Simple Baselines
+            # configs; absent from the reference's YAMLs, off when absent): the protocol the published checkpoints were evaluated under
+            opt = lambda k: self.pose_detector.get(k) if isinstance(self.pose_detector, dict) else getattr(self.pose_detector, k, None)
+            if opt('SHIFT_HEATMAP') is not None:
+                self.pose_model.shift_heatmap = bool(opt('SHIFT_HEATMAP'))
+            self.pose_model.post_process = bool(opt('POST_PROCESS'))
+            self.pose_model.flip_test = bool(opt('FLIP_TEST'))
             print("Pose Detector : ", _cfg(self.pose_detector, 'NAME'))
         if self.person_matcher is None:
             print("Person Matcher : Close.")

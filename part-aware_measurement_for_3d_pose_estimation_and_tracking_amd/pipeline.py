@@ -19,7 +19,8 @@ NUM_JOINTS = 17
 class FramePipeline(object):
     def __init__(self, calib_cameras, matcher, conf_threshold, frame_hw, max_dets=8, max_tracks=16, device=0, world=1,
                  rank=0, group=None, use_graph=True, hrnet=True, seed=0, shard='views', overlap_tracker=False, net=None, exchange='torch',
-                 pose_streams=1, autotune=True, prewarm=False, width=48, resolution=(384, 288)):
+                 pose_streams=1, autotune=True, prewarm=False, width=48, resolution=(384, 288), flip_test=False, shift_heatmap=True,
+                 post_process=False, model_name='HRNet'):
         """shard: 'views' -- rank owns whole camera views (pose_step / track_step take view-local inputs); 'crops' -- the
         frame's crops are dealt out evenly over the ranks (pose_step_crops / track_step_crops take global view indices).
         overlap_tracker (either mode): exchange + tracker kernel + fetch of frame t run on their own stream, under the conv
@@ -32,7 +33,10 @@ class FramePipeline(object):
         prewarm: capture the replay of every crop-count bucket this rank can see (its views x max_dets, in steps of the network's
         graph_bucket) at construction -- `self.warmed` says what that cost -- and pad every frame's forward to its bucket, so that no
         step() ever captures (the reference's call shape has a fixed batch_size = 20, /root/reference/src/ivclabpose.py:208-212).
-        width / resolution: the pose network FramePipeline builds when no `net` is given (HRNet-W48 at 384 x 288; 32 / (256, 192) = W32)."""
+        width / resolution: the pose network FramePipeline builds when no `net` is given (HRNet-W48 at 384 x 288; 32 / (256, 192) = W32;
+        model_name='PoseResNet' with width = the ResNet depth, as HRNetPose takes it).
+        flip_test / shift_heatmap / post_process: that network's decode options (HRNetPose: the official test protocol; the flip test
+        doubles every forward, prewarm captures the doubled counts).  A shared `net` keeps its own settings."""
         self.device = torch.device('cuda:%d' % device)
         torch.cuda.set_device(self.device)
         self.cams = calib_cameras
@@ -45,9 +49,11 @@ class FramePipeline(object):
         self.handle.set_cameras(np.stack([c.P for c in calib_cameras]), np.stack([c.F for c in calib_cameras]),
                                 np.stack([c.RK_INV for c in calib_cameras]), np.stack([c.position for c in calib_cameras]))
         # net: an existing HRNetPose to share (weights, packed images, captured graphs) between several pipelines of one process
-        self.net = net if net is not None else (HRNetPose(width, 17, None, resolution=tuple(resolution), device=device, use_graph=use_graph, seed=seed,
+        self.net = net if net is not None else (HRNetPose(width, 17, None, model_name=model_name, resolution=tuple(resolution), device=device,
+                                                          use_graph=use_graph, seed=seed,
                                                           max_dets=max_dets, autotune=autotune,
-                                                          max_crops=len(calib_cameras) * max_dets) if hrnet else None)
+                                                          max_crops=len(calib_cameras) * max_dets, flip_test=flip_test,
+                                                          shift_heatmap=shift_heatmap, post_process=post_process) if hrnet else None)
         self.shard = shard
         # exchange: 'torch' = torch.distributed (RCCL when the backend is nccl, gloo in the CPU tests); 'abi' = pam_allgather_keypoints,
         # the library's own RCCL call on the decode stream (view sharding only)

@@ -35,6 +35,7 @@ def kernels(path):
         d1 = next(i for i in range(d0, len(lines)) if ".end_amdhsa_kernel" in lines[i])
         out[k] = [norm(lines[start:end]), norm(lines[d0:d1])]
     meta = "".join(lines[next(i for i, l in enumerate(lines) if l.strip() == ".amdgpu_metadata"):])
+    meta = meta.split("\namdhsa.target:")[0]          # the file's trailer is no part of the last kernel's entry
     for entry in re.split(r"\n  - (?=\.)", meta)[1:]:
         name = re.search(r"^    \.name:\s+(\S+)", entry, re.M).group(1)
         out[name].append(norm([entry]))
