@@ -19,6 +19,9 @@ consumes the seeded synthetic keypoints so that association behaves realisticall
 
 `python bench.py --gpus N` starts its own N ranks (torch.distributed.run child; the parent never touches a GPU);
 under `python -m torch.distributed.run ... bench.py --gpus N` it is one of the ranks.  Prints ONE JSON line (rank 0).
+
+A plain run does what the headline needs and no more: set-up, warm-up, the K timed steps, --dump-outputs, the line.  `--full` adds every
+secondary measurement behind the timed steps (everything the --no-* switches name); the timed steps and `value` are the same either way.
 See DESIGN.md 'Measurement' for how roofline / families / surface / cpu_baseline are derived."""
 import argparse
 import json
@@ -45,11 +48,22 @@ def algorithmic_bytes_per_frame(C, P, T, V, L, J=17):
     return det + T * per_track + out
 
 
-def parse_args():
+# What only a --full run measures, by the switch that turns each of them off.  A plain run sets them all: it times the K steps and
+# prints what they alone give (value, ms_per_step, conv_stack_ms, the conv stack's roofline from the timed steps' own HIP events).
+SECONDARY = ('no_cpu_baseline', 'no_batched', 'no_families', 'no_surface', 'no_h2d', 'no_drift', 'no_full', 'no_driver_loop', 'no_ab',
+             'no_pair', 'no_extra', 'no_kernels')
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=10)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run every secondary measurement (CPU baseline, frames from host memory, two frames per replay, '
+                         'detector in the loop, drop-in surface, driver loop, A/B against the previous executor, bf16 drift, batched tracker, '
+                         'per-kernel and per-family rooflines; N > 1: the other partition, the single-GPU run, Panoptic-31); the --no-* switches '
+                         'below take single ones out again.  Without it none of them runs')
     ap.add_argument('--workload', default=None, choices=['S1', 'S2', 'S3', 'S4'], help='default: S2 (N > 1 adds the S4 runs as `panoptic31`)')
     ap.add_argument('--shard', default=None, choices=['views', 'crops'], help='default: crops on one GPU (= no exchange), views on several')
     ap.add_argument('--exchange', default='torch', choices=['torch', 'abi'], help="abi: the all-gather through pam_allgather_keypoints (RCCL called by the library; view sharding, real multi-GPU only)")
@@ -64,6 +78,7 @@ def parse_args():
     ap.add_argument('--no-ab', action='store_true', help="skip the interleaved A/B of this round's executor against the previous round's")
     ap.add_argument('--no-pair', action='store_true', help='skip the throughput-mode run (two frames per conv-stack replay)')
     ap.add_argument('--no-extra', action='store_true', help='N > 1: skip the crop-balanced run, the single-GPU run of the same workload and the Panoptic-31 runs')
+    ap.add_argument('--no-kernels', action='store_true', help='skip the crop kernel and the head + arg-max decode timed alone (`kernels`)')
     ap.add_argument('--batched-scenes', type=int, default=2048)
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--no-autotune', action='store_true', help="keep the conv stack in the executor's default configuration instead of the fastest per crop count")
@@ -71,7 +86,11 @@ def parse_args():
     ap.add_argument('--no-overlap', action='store_true', help='run the tracker of frame t on the pose stream instead of under frame t+1')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64, <= 64 MB in all)')
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:
+        for name in SECONDARY:
+            setattr(args, name, True)
+    return args
 
 
 def visible_gpu_count():
@@ -708,7 +727,7 @@ def main():
         vl, sl, bx = e['vl'], e['sl'], e['bx']
         n = int(vl.numel())
         kern = []
-        if n > 0 and pipe.net is not None:
+        if not args.no_kernels and n > 0 and pipe.net is not None:
             x = pipe.net.input_buffer(n)
             s = ev_time(lambda: pipe.net.preprocess(inp['ptrs'], fh, fw, vl, bx, x))
             by = float((bx[:, 2] * bx[:, 3]).sum().item()) * 3 + n * x.shape[1] * 384 * 288 * 2

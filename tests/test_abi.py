@@ -133,6 +133,25 @@ def test_bench_counts_gpus_without_touching_hip(monkeypatch):
     assert b.algorithmic_bytes_per_frame(5, 4, 4, 5, 11) == 39520      # SURVEY 8d's Shelf figure
 
 
+def test_bench_plain_run_measures_the_headline_alone_and_full_everything():
+    """A plain bench.py run switches every secondary measurement off, whatever else the command line says; --full switches them all on and
+    the --no-* options take single ones out again.  Neither form touches the arguments of the timed steps."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod3', os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'bench.py'))
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    plain = b.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '3'])
+    every = sorted(k for k in vars(plain) if k.startswith('no_') and k not in ('no_graph', 'no_autotune', 'no_overlap'))
+    assert every == sorted(b.SECONDARY)                  # a new --no-* measurement switch must be listed, or a plain run would run it
+    assert not plain.full and all(getattr(plain, k) for k in b.SECONDARY)
+    full = b.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '3', '--full'])
+    assert full.full and not any(getattr(full, k) for k in b.SECONDARY)
+    some = b.parse_args(['--full', '--no-cpu-baseline', '--no-full'])
+    assert [k for k in b.SECONDARY if getattr(some, k)] == ['no_cpu_baseline', 'no_full']
+    same = ('gpus', 'steps', 'warmup', 'workload', 'shard', 'exchange', 'no_graph', 'no_autotune', 'pose_streams', 'no_overlap', 'dump_outputs')
+    assert [getattr(plain, k) for k in same] == [getattr(full, k) for k in same]
+    assert (plain.steps, plain.warmup, plain.dump_outputs) == (7, 3, None)
+
+
 def test_one_hip_runtime_whatever_the_import_order():
     """__graft_entry__.build() loads the library before anything imported torch; the process must still end up with a
     single libamdhip64 mapped (two runtimes: the second to initialise reports 'no ROCm-capable device')."""

@@ -1,5 +1,6 @@
 #!/bin/bash
 # alternate two settings of an environment variable over bench.py runs on ONE box: tools/ab_env.sh VAR A B "<bench args>" [rounds]
+# (the `full` column is the detector-in-the-loop figure: it reads 0 unless the bench args carry --full)
 VAR=$1; A=$2; B=$3; ARGS=$4; R=${5:-2}
 for r in $(seq 1 $R); do for v in $A $B; do
 env $VAR=$v python3 bench.py $ARGS 2>/tmp/err.txt | python3 -c "

@@ -1,4 +1,4 @@
-B="--steps 200 --warmup 20 --no-cpu-baseline --no-families --no-surface --no-batched --no-drift --no-pair --no-h2d"
+B="--full --steps 200 --warmup 20 --no-cpu-baseline --no-families --no-surface --no-batched --no-drift --no-pair --no-h2d"
 for r in 1 2; do for m in 6 20; do
 PAM_FSUM_MAX=$m python3 bench.py $B 2>/tmp/err.txt | python3 -c "
 import json,sys

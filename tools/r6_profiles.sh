@@ -10,16 +10,16 @@ R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/final; mkdir -p $OUT; cd $R
 T="timeout -s KILL"
 case $STEP in
 bench)
-  $T 400 python3 bench.py > $OUT/${TAG}_bench_S2_n1.json 2> $OUT/bench.err; echo "S2 rc=$?"
+  $T 400 python3 bench.py --full > $OUT/${TAG}_bench_S2_n1.json 2> $OUT/bench.err; echo "S2 rc=$?"
   for WL in S1 S3 S4; do
-    $T 500 python3 bench.py --workload $WL --steps 40 --warmup 6 --no-pair --no-h2d --no-drift --no-driver-loop > $OUT/${TAG}_bench_${WL}_n1.json 2> $OUT/bench_$WL.err; echo "$WL rc=$?"
+    $T 500 python3 bench.py --full --workload $WL --steps 40 --warmup 6 --no-pair --no-h2d --no-drift --no-driver-loop > $OUT/${TAG}_bench_${WL}_n1.json 2> $OUT/bench_$WL.err; echo "$WL rc=$?"
   done
-  $T 500 python3 bench.py --gpus 2 --steps 20 --warmup 4 > $OUT/${TAG}_bench_n2_one_device.json 2> $OUT/bench2.err; echo "n2 rc=$?"
+  $T 500 python3 bench.py --full --gpus 2 --steps 20 --warmup 4 > $OUT/${TAG}_bench_n2_one_device.json 2> $OUT/bench2.err; echo "n2 rc=$?"
   for f in $OUT/${TAG}_bench_S*_n1.json; do python3 -c "import json,sys; j=json.loads(open('$f').read().strip().splitlines()[-1]); print('$f'.split('/')[-1], json.dumps(j['summary'])[:900])"; done
   ;;
 trace)
   cd /tmp; export TMPDIR=/tmp
-  $T 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --steps 30 --warmup 5 --no-driver-loop --no-ab > $OUT/${TAG}_bench_S2_under_rocprof.json 2> $OUT/rocprof.err; echo "rocprof rc=$?"
+  $T 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --steps 30 --warmup 5 --no-driver-loop --no-ab > $OUT/${TAG}_bench_S2_under_rocprof.json 2> $OUT/rocprof.err; echo "rocprof rc=$?"
   cp $(ls -t $OUT/stats/*/*kernel_stats.csv | head -1) $OUT/${TAG}_bench_S2_kernel_stats.csv; rm -rf $OUT/stats
   head -12 $OUT/${TAG}_bench_S2_kernel_stats.csv | cut -c1-160
   ;;
