@@ -526,6 +526,19 @@ int pam_yolo_detect_heads_ws(void* stream, int n_img, int n_heads, const void* c
  * one of the inputs (bit-exact against torch.max_pool2d on the -inf-padded tensor), so zero channels stay zero.
  * C % 8 == 0, size 2 or 3, stride 1 or 2; PAM_E_ARG otherwise (null pointer included), PAM_E_HIP on a launch error. */
 int pam_maxpool_nhwc_bf16(void* stream, const void* in, void* out, int N, int H, int W, int C, int size, int stride);
+/* YOLOv3-SPP's block in one launch: three stride-1 Darknet `maxpool`s of one layer and the `route` over them and their source.
+ * in: NHWC bf16 (N, H, W, C).  out: NHWC bf16 (N, H, W, 4C) = [pool_s3 | pool_s2 | pool_s1 | in] along the channels.  Every pool is the
+ * stride-1 `maxpool` above: the window is centred on the pixel, taps outside the image do not take part.  The copy of `in` is bitwise.  A
+ * pooled value is one of the window's inputs, bit for bit, wherever it is not zero; where it is zero either sign of zero may come out (the
+ * sign depends on the scan order, which the kernel chooses).  NaN inputs are outside the contract.
+ * PAM_E_ARG, before anything is launched, for: a null pointer; N, H or W <= 0; C % 8 != 0 (C <= 0 included); H or W above PAM_SPP_MAX_HW
+ * (the largest map the kernel holds in LDS: network inputs up to 1024 x 1024); sizes that are not odd, not in 3 .. 13 or not strictly
+ * ascending (s1 < s2 < s3).  PAM_E_HIP on a launch error.
+ * The _slab form states the channels per workgroup (8, 16, 32 or 64, PAM_E_ARG otherwise; halved until the map fits the workgroup's LDS):
+ * a measuring hook, the plain form uses the slab that measured fastest. */
+#define PAM_SPP_MAX_HW 32
+int pam_spp_concat_nhwc_bf16(void* stream, const void* in, void* out, int N, int H, int W, int C, int s1, int s2, int s3);
+int pam_spp_concat_slab_nhwc_bf16(void* stream, const void* in, void* out, int N, int H, int W, int C, int s1, int s2, int s3, int slab);
 
 #ifdef __cplusplus
 }

@@ -118,9 +118,12 @@ _SIGS = {
     'pam_yolo_detect_heads_ws': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_float, C.c_float, _I, _I, _I, _P, _P, _P, C.c_longlong]),
     'pam_yolo_detect_heads_workspace_bytes': (C.c_longlong, [_I, _I, _P, _P]),
     'pam_maxpool_nhwc_bf16': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I]),
+    'pam_spp_concat_nhwc_bf16': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
+    'pam_spp_concat_slab_nhwc_bf16': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I]),
 }
 EXPORTS = tuple(_SIGS)
 YOLO_MAX_CAND = 1024        # PAM_YOLO_MAX_CAND in include/pam.h
+SPP_MAX_HW = 32             # PAM_SPP_MAX_HW in include/pam.h
 
 _lib = None
 

@@ -2,7 +2,7 @@
 // ivclabpose.PersonDetect (/root/reference/src/ivclabpose.py:116-120,183-204; the backend itself is not in the reference
 // tree, so these follow the public Darknet YOLOv3 definition -- parity unpinned).  The Darknet-53 convolutions run on
 // pam_conv.hip; the kernels here are the HBM-bound streaming pieces: frame resize, route(upsample, skip), YOLOv3-tiny's
-// max-pool and the box decode + greedy NMS over one to three scales.
+// max-pool, YOLOv3-SPP's pooling block and the box decode + greedy NMS over one to three scales.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pam.h"
@@ -138,6 +138,127 @@ extern "C" int pam_maxpool_nhwc_bf16(void* stream, const void* in, void* out, in
     if (size == 2) hipLaunchKernelGGL(k_maxpool<2>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)in, (uint16_t*)out, N, H, W, C, Ho, Wo, stride);
     else hipLaunchKernelGGL(k_maxpool<3>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)in, (uint16_t*)out, N, H, W, C, Ho, Wo, stride);
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+}
+
+// ---- YOLOv3-SPP's block: three stride-1 [maxpool]s of one layer and the route over them, one launch ---------------------------------
+// out[n, y, x] = [pool_s3 | pool_s2 | pool_s1 | in] along the channels (4C wide).  One workgroup per (view, slab of SPP_SLAB channels): the
+// slab's H x W map lives in LDS, 16 B (8 channels) per item, as ORDER KEYS: a bf16 with its magnitude bits inverted when the sign is set
+// compares like the number as a signed 16-bit integer (-inf lowest, -0 just below +0), so a window maximum is v_pk_max_i16 on two channels at
+// once and the key of the result, turned back, is one of the inputs bit for bit (NaN is outside the contract: a key order has no place for it).
+//   phase A  in -> registers: the bitwise copy to channels [3C, 4C) and the keys to buffer 0
+//   phase B  rows:    T[y][x]  = max of buffer 0 over x - r1 .. x + r1                       (buffer 0 -> 1)
+//   phase C  columns: P1[y][x] = max of T over y - r1 .. y + r1 = the s1 pool                 (buffer 1 -> 0, channels [2C, 3C))
+//   phase D  P2 = max of P1 at the k2 x k2 taps (y + o2[j], x + o2[i]) = the s2 pool         (buffer 0 -> 1, channels [C, 2C))
+//   phase E  P3 = max of P2 at the k3 x k3 taps (y + o3[j], x + o3[i]) = the s3 pool         (buffer 1, channels [0, C))
+// A window of radius rt is the union of windows of radius rs < rt centred at offsets -(rt - rs) .. +(rt - rs) no further apart than 2 rs + 1
+// (spp_taps; for 5 / 9 / 13 that is two offsets, -2 and +2, at both levels: 4 LDS reads per output).  Every tap position is CLAMPED to the map:
+// a clamped window [0, rs] still lies inside the target window (x >= 0 > x + o means rs <= x + rt) and covers all of the unclamped window that is
+// inside the map, so the union stays exactly the target window cut to the map -- Darknet's "taps outside the image do not take part".  A skipped
+// tap instead would lose border columns (window 9 at column 1 must see column 0, which only the tap at -1, clamped to 0, brings).
+#define SPP_MAX_HW 32                    // PAM_SPP_MAX_HW: 2 buffers x 32 x 32 x 8 channels x 2 B = 32 KB at the narrowest slab
+#define SPP_LDS_BYTES 65536
+#define SPP_SLAB 32                      // channels per workgroup of the plain entry (64-byte stores; tools/bench_spp.py measures 8 .. 64,
+                                         // DESIGN.md 10e); halved until the map fits
+struct SppTaps { int r1, k2, k3; int o2[5], o3[5]; };
+
+typedef short spp_s2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t spp_key(uint32_t w) { return w ^ (((w >> 15) & 0x00010001u) * 0x7fffu); }      // its own inverse
+__device__ __forceinline__ uint32_t spp_max2(uint32_t a, uint32_t b) {
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(spp_s2, a), __builtin_bit_cast(spp_s2, b)));
+}
+__device__ __forceinline__ uint4 spp_max(uint4 a, uint4 b) {
+    return make_uint4(spp_max2(a.x, b.x), spp_max2(a.y, b.y), spp_max2(a.z, b.z), spp_max2(a.w, b.w));
+}
+__device__ __forceinline__ uint4 spp_keys(uint4 v) { return make_uint4(spp_key(v.x), spp_key(v.y), spp_key(v.z), spp_key(v.w)); }
+
+// lv = log2(vectors of 8 channels per slab); the last slab of a C that is no multiple of the slab holds fewer (nv) and its other items idle
+__global__ __launch_bounds__(256) void k_spp(const uint16_t* __restrict__ in, uint16_t* __restrict__ out, int H, int W, int C, int lv, SppTaps t) {
+    extern __shared__ uint4 spp_lds[];
+    const int n = blockIdx.y, c0 = blockIdx.x * (8 << lv);
+    const int nv = min(1 << lv, (C - c0) >> 3);
+    const int items = (H * W) << lv;
+    uint4* b0 = spp_lds;
+    uint4* b1 = spp_lds + items;
+    const uint16_t* src = in + (size_t)n * H * W * C + c0;
+    uint16_t* dst = out + (size_t)n * H * W * 4 * C + c0;
+    const int rw = 65536 / W + 1;                  // pix / W == (pix * rw) >> 16 for pix < 1024, W <= 32 (the error stays below 1 / 64)
+    const int vmask = (1 << lv) - 1;
+#define SPP_ITEM(i) const int v = (i) & vmask, pix = (i) >> lv, y = (pix * rw) >> 16, x = pix - y * W; (void)y; (void)x; if (v >= nv) continue
+    for (int i = threadIdx.x; i < items; i += 256) {                       // A
+        SPP_ITEM(i);
+        const uint4 d = *(const uint4*)(src + (size_t)pix * C + v * 8);
+        *(uint4*)(dst + (size_t)pix * 4 * C + 3 * C + v * 8) = d;
+        b0[i] = spp_keys(d);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < items; i += 256) {                       // B
+        SPP_ITEM(i);
+        const int xa = max(x - t.r1, 0), xb = min(x + t.r1, W - 1);
+        uint4 m = b0[i];
+        for (int xx = xa; xx <= xb; ++xx) m = spp_max(m, b0[((y * W + xx) << lv) + v]);
+        b1[i] = m;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < items; i += 256) {                       // C
+        SPP_ITEM(i);
+        const int ya = max(y - t.r1, 0), yb = min(y + t.r1, H - 1);
+        uint4 m = b1[i];
+        for (int yy = ya; yy <= yb; ++yy) m = spp_max(m, b1[((yy * W + x) << lv) + v]);
+        b0[i] = m;
+        *(uint4*)(dst + (size_t)pix * 4 * C + 2 * C + v * 8) = spp_keys(m);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < items; i += 256) {                       // D
+        SPP_ITEM(i);
+        uint4 m = make_uint4(0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u);      // below every key
+        for (int j = 0; j < t.k2; ++j) {
+            const int row = min(max(y + t.o2[j], 0), H - 1) * W;
+            for (int k = 0; k < t.k2; ++k) m = spp_max(m, b0[((row + min(max(x + t.o2[k], 0), W - 1)) << lv) + v]);
+        }
+        b1[i] = m;
+        *(uint4*)(dst + (size_t)pix * 4 * C + C + v * 8) = spp_keys(m);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < items; i += 256) {                       // E
+        SPP_ITEM(i);
+        uint4 m = make_uint4(0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u);
+        for (int j = 0; j < t.k3; ++j) {
+            const int row = min(max(y + t.o3[j], 0), H - 1) * W;
+            for (int k = 0; k < t.k3; ++k) m = spp_max(m, b1[((row + min(max(x + t.o3[k], 0), W - 1)) << lv) + v]);
+        }
+        *(uint4*)(dst + (size_t)pix * 4 * C + v * 8) = spp_keys(m);
+    }
+#undef SPP_ITEM
+}
+
+// offsets of the radius-rs windows whose union is the radius-rt window: k = ceil((2 rt + 1) / (2 rs + 1)) of them from -(rt - rs) to
+// +(rt - rs), neighbours at most 2 rs + 1 apart (2 (rt - rs) / (k - 1) <= 2 rs + 1 by the choice of k, and floor keeps integer steps below it)
+static int spp_taps(int rs, int rt, int* o) {
+    const int d = rt - rs, k = (2 * rt + 2 * rs + 1) / (2 * rs + 1);
+    for (int j = 0; j < k; ++j) o[j] = -d + (2 * d * j) / (k - 1);
+    return k;
+}
+
+extern "C" int pam_spp_concat_slab_nhwc_bf16(void* stream, const void* in, void* out, int N, int H, int W, int C, int s1, int s2, int s3,
+                                             int slab) {
+    if (!in || !out || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 != 0 || H > SPP_MAX_HW || W > SPP_MAX_HW) return PAM_E_ARG;
+    if (!(s1 & 1) || !(s2 & 1) || !(s3 & 1) || s1 < 3 || s3 > 13 || s1 >= s2 || s2 >= s3) return PAM_E_ARG;
+    if (slab != 8 && slab != 16 && slab != 32 && slab != 64) return PAM_E_ARG;
+    while (slab > 8 && (size_t)2 * H * W * slab * 2 > SPP_LDS_BYTES) slab >>= 1;       // 32 x 32 x 8 channels x 2 buffers = 32 KB always fits
+    int lv = 0;
+    while ((8 << lv) < slab) ++lv;
+    SppTaps t;
+    t.r1 = s1 >> 1;
+    for (int j = 0; j < 5; ++j) t.o2[j] = t.o3[j] = 0;
+    t.k2 = spp_taps(s1 >> 1, s2 >> 1, t.o2);
+    t.k3 = spp_taps(s2 >> 1, s3 >> 1, t.o3);
+    hipLaunchKernelGGL(k_spp, dim3((C + slab - 1) / slab, N), dim3(256), (size_t)2 * H * W * slab * 2, (hipStream_t)stream,
+                       (const uint16_t*)in, (uint16_t*)out, H, W, C, lv, t);
+    return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+}
+
+extern "C" int pam_spp_concat_nhwc_bf16(void* stream, const void* in, void* out, int N, int H, int W, int C, int s1, int s2, int s3) {
+    return pam_spp_concat_slab_nhwc_bf16(stream, in, out, N, H, W, C, s1, s2, s3, SPP_SLAB);
 }
 
 // ---- YOLO head decode + greedy NMS for one class --------------------------------------------------------------------

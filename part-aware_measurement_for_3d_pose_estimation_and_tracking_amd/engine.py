@@ -436,3 +436,18 @@ class ConvEngine(object):
             self._cur(x), ptr(x), ptr(y), n, h, w, c, int(size), int(stride)), nbytes, 0,
             what=(' for %s size %d stride %d', tuple(x.shape), size, stride))
         return y
+
+    def spp(self, x, sizes):
+        """YOLOv3-SPP's block, one launch: concat(pool_c(x), pool_b(x), pool_a(x), x) along channels for sizes = (a, b, c), every pool
+        Darknet's stride-1 [maxpool] (odd sizes 3 .. 13, ascending; maps up to _lib.SPP_MAX_HW a side)."""
+        n, c, h, w = x.shape
+        a, b, cc = [int(s) for s in sizes]
+        y = self._new(n, 4 * c, h, w, x.device)
+        nbytes = 2 * (x.numel() + y.numel())
+        if self._tally(x, nbytes, 0):
+            return y
+        assert x.is_contiguous(memory_format=torch.channels_last), (x.shape, x.stride())
+        self._run(x, 'pam_spp_concat_nhwc_bf16', lambda: self.lib.pam_spp_concat_nhwc_bf16(
+            self._cur(x), ptr(x), ptr(y), n, h, w, c, a, b, cc), nbytes, 0, 'k_spp', (n, h, w, c, a, b, cc),
+            what=(' for %s sizes %s', tuple(x.shape), (a, b, cc)))
+        return y

@@ -86,7 +86,7 @@ class ivclabpose(object):
             cfg, weight, names = _cfg(d, 'CFG'), _cfg(d, 'WEIGHT'), _cfg(d, 'CLASS_NAMES')
             # the reference's cfg / weight / names files are not distributed with it: a missing cfg or names file means
             # the standard YOLOv3-416 COCO layout (person = class 0), missing weights mean a seeded random network.
-            # ARCH (optional key, not in the reference): 'yolov3' | 'yolov3-tiny', the standard network built when the cfg file is missing
+            # ARCH (optional key, not in the reference): 'yolov3' | 'yolov3-tiny' | 'yolov3-spp', the standard network built when the cfg file is missing
             arch = (d.get('ARCH') if isinstance(d, dict) else getattr(d, 'ARCH', None)) or 'yolov3'
             self.bbox_detector = YOLOv3(cfg if cfg and os.path.exists(cfg) else None,
                                         weight if weight and os.path.exists(weight) else None,

@@ -6,11 +6,13 @@ The backend itself, its cfg and its weights are not part of the reference tree, 
 YOLOv3 definition (Redmon & Farhadi 2018: Darknet-53 backbone, three ``yolo`` heads, 9 anchors) -- parity unpinned, like
 HRNet.  It understands Darknet ``.cfg`` text (convolutional / shortcut / route / upsample / maxpool / yolo) and Darknet ``.weights``
 files; with no cfg it builds the standard 416 x 416, 80-class network (``arch='yolov3-tiny'``: the standard YOLOv3-tiny, 13
-convolutions, 6 max-pools, two heads), with no weights a seeded random one.
+convolutions, 6 max-pools, two heads; ``arch='yolov3-spp'``: YOLOv3-SPP, Darknet-53 with the 5 / 9 / 13 spatial-pyramid-pooling block
+in front of the first head, 76 convolutions), with no weights a seeded random one.
 
 Two executions of the same network: ``Darknet`` (plain PyTorch float32; the test reference) and ``HipDarknet`` (product
 path: every convolution on the MFMA kernels of csrc/pam_conv.hip with BN folded, leaky-ReLU and the shortcut add fused into
-the epilogue; resize, upsample+route and box decode + NMS in csrc/pam_detect.hip; one hipGraph per batch shape)."""
+the epilogue; resize, upsample+route, max-pool, the SPP block (its three pools and their route: one launch) and box decode + NMS in
+csrc/pam_detect.hip; one hipGraph per batch shape)."""
 import ctypes as C
 import os
 import struct
@@ -28,8 +30,9 @@ ANCHORS = [(10, 13), (16, 30), (33, 23), (30, 61), (62, 45), (59, 119), (116, 90
 
 
 # ---- cfg ------------------------------------------------------------------------------------------------------------
-def default_cfg(width=416, height=416, classes=80):
-    """The standard yolov3.cfg (107 layers), generated rather than shipped."""
+def _darknet53_cfg(width, height, classes, spp):
+    """yolov3.cfg, or with spp yolov3-spp.cfg: the same text with the SPP block (three stride-1 max-pools of layer 77, the route over them
+    and layer 77, a 1x1 convolution back to 512 channels) spliced in after the first head's third convolution."""
     out = ['[net]', 'width=%d' % width, 'height=%d' % height, 'channels=3', '']
 
     def conv(filters, size, stride=1, bn=1, act='leaky'):
@@ -43,9 +46,14 @@ def default_cfg(width=416, height=416, classes=80):
             conv(filters, 3)
             out.extend(['[shortcut]', 'from=-3', 'activation=linear', ''])
 
-    def head(filters, mask):
-        for _ in range(3):
+    def head(filters, mask, spp=False):
+        for k in range(3):
             conv(filters, 1)
+            if spp and k == 1:
+                for size, back in ((5, -2), (9, -4), (13, None)):
+                    out.extend(['[maxpool]', 'stride=1', 'size=%d' % size, ''])
+                    out.extend(['[route]', 'layers=%s' % (back if back is not None else '-1,-3,-5,-6'), ''])
+                conv(filters, 1)
             conv(filters * 2, 3)
         conv(3 * (5 + classes), 1, bn=0, act='linear')
         out.extend(['[yolo]', 'mask = %s' % ','.join(str(m) for m in mask),
@@ -54,13 +62,24 @@ def default_cfg(width=416, height=416, classes=80):
     conv(32, 3)
     for f, b in ((64, 1), (128, 2), (256, 8), (512, 8), (1024, 4)):
         stage(f, b)
-    head(512, (6, 7, 8))
+    head(512, (6, 7, 8), spp)
     for skip, f, mask in ((61, 256, (3, 4, 5)), (36, 128, (0, 1, 2))):
         out.extend(['[route]', 'layers = -4', ''])
         conv(f, 1)
         out.extend(['[upsample]', 'stride=2', '', '[route]', 'layers = -1, %d' % skip, ''])
         head(f, mask)
     return '\n'.join(out)
+
+
+def default_cfg(width=416, height=416, classes=80):
+    """The standard yolov3.cfg (107 layers), generated rather than shipped."""
+    return _darknet53_cfg(width, height, classes, False)
+
+
+def spp_cfg(width=416, height=416, classes=80):
+    """The standard yolov3-spp.cfg (114 layers, 76 convolutions: yolov3.cfg with the SPP block as layers 78 .. 84; heads at 89, 101, 113),
+    generated like default_cfg."""
+    return _darknet53_cfg(width, height, classes, True)
 
 
 TINY_ANCHORS = [(10, 14), (23, 27), (37, 58), (81, 82), (135, 169), (344, 319)]
@@ -93,7 +112,7 @@ def tiny_cfg(width=416, height=416, classes=80):
     return '\n'.join(out)
 
 
-ARCHS = {'yolov3': default_cfg, 'yolov3-tiny': tiny_cfg}
+ARCHS = {'yolov3': default_cfg, 'yolov3-tiny': tiny_cfg, 'yolov3-spp': spp_cfg}
 
 
 def parse_cfg(text):
@@ -282,6 +301,42 @@ def _round_channels(c):
     return c if (c % 48 == 0 or c % 64 == 0) else (c + 63) // 64 * 64
 
 
+def _layer_sizes(model):
+    """(height, width) of every layer's output for the cfg's input size."""
+    out = []
+    hw = (model.height, model.width)
+    for i, b in enumerate(model.layers):
+        t = b['type']
+        if t == 'convolutional':
+            pad = (b['size'] - 1) // 2 if b['pad'] else 0
+            hw = tuple((v + 2 * pad - b['size']) // b['stride'] + 1 for v in hw)
+        elif t == 'maxpool':
+            hw = tuple((v - 1) // b['stride'] + 1 for v in hw)
+        elif t == 'upsample':
+            hw = tuple(v * b['stride'] for v in hw)
+        elif t == 'route':
+            hw = out[b['layers'][0] if b['layers'][0] >= 0 else i + b['layers'][0]]
+        out.append(hw)
+    return out
+
+
+def _spp_block(layers, i, used_by):
+    """The pool sizes (a, b, c) when layers i .. i + 5 are YOLOv3-SPP's block on layer i - 1, else None: three stride-1 [maxpool]s of odd
+    ascending sizes <= 13, the second and third behind a one-layer [route] back to layer i - 1, then the [route] over pool c, pool b, pool a
+    and layer i - 1 in that order; nothing else reads the five inner layers."""
+    if i + 5 >= len(layers) or [b['type'] for b in layers[i:i + 6]] != ['maxpool', 'route'] * 3:
+        return None
+    pools = tuple(layers[k]['size'] for k in (i, i + 2, i + 4))
+    if any(layers[k]['stride'] != 1 for k in (i, i + 2, i + 4)) or any(s % 2 == 0 or not 3 <= s <= 13 for s in pools) or not pools[0] < pools[1] < pools[2]:
+        return None
+    routes = [[l if l >= 0 else k + l for l in layers[k]['layers']] for k in (i + 1, i + 3, i + 5)]
+    if routes != [[i - 1], [i - 1], [i + 4, i + 2, i, i - 1]]:
+        return None
+    if [used_by[k] for k in range(i, i + 5)] != [[i + 5], [], [i + 5], [], [i + 5]]:
+        return None
+    return pools
+
+
 class HipDarknet(ConvEngine):
     """The cfg's layer list compiled to kernel launches.  Channel counts the MFMA kernels cannot take (3 -> 8 on the input,
     32 / 255 -> 64 / 256 on outputs; YOLOv3-tiny's 16-filter first layer -> 32 on k_conv_stem) are zero-padded at the end of the
@@ -304,6 +359,7 @@ class HipDarknet(ConvEngine):
                 for l in b['layers']:
                     used_by[l if l >= 0 else i + l].append(i)
         self.plan, real, padded = [], [], []
+        sizes = _layer_sizes(model)
         c_real, c_pad = int(model.net.get('channels', 3)), 8
         i = 0
         while i < n:
@@ -346,6 +402,18 @@ class HipDarknet(ConvEngine):
                 real += [real[i - 1], real[i - 1] + real[skip]]; padded += [padded[i - 1], padded[i - 1] + padded[skip]]
                 i += 2
                 continue
+            elif t == 'maxpool' and _spp_block(layers, i, used_by) is not None:
+                # YOLOv3-SPP: pools a < b < c of layer i - 1 and the route (c, b, a, i - 1) over them -> layer i + 5 in ONE launch
+                src, pools = i - 1, _spp_block(layers, i, used_by)
+                if real[src] != padded[src]:
+                    raise NotImplementedError('SPP block over a channel-padded layer (%d of %d channels real)' % (real[src], padded[src]))
+                if max(sizes[src]) > _lib.SPP_MAX_HW:
+                    raise NotImplementedError('SPP block on a %d x %d map: the kernel holds maps up to %d a side (network inputs up to %d)' %
+                                              (sizes[src] + (_lib.SPP_MAX_HW, 32 * _lib.SPP_MAX_HW)))
+                self.plan.append(('spp', i + 5, src, pools))
+                real += [real[src]] * 5 + [4 * real[src]]; padded += [padded[src]] * 5 + [4 * padded[src]]
+                i += 6
+                continue
             elif t == 'maxpool':
                 if b['size'] not in (2, 3) or b['stride'] not in (1, 2):
                     raise NotImplementedError('[maxpool] size=%d stride=%d: the max-pool kernel takes size 2 or 3 and stride 1 or 2' %
@@ -383,6 +451,8 @@ class HipDarknet(ConvEngine):
             return self.upsample_concat(outs[step[2]], outs[step[3]])
         if kind == 'pool':
             return self.maxpool(outs[step[2]], step[3], step[4])
+        if kind == 'spp':
+            return self.spp(outs[step[2]], step[3])
         return outs[step[2]]                                # alias, head
 
     def unfused(self, step, x):
@@ -398,7 +468,7 @@ class YOLOv3(object):
 
     def __init__(self, cfgfile=None, weightfile=None, namesfile=None, score_thresh=0.7, nms_thresh=0.45, use_cuda=True,
                  device=0, max_det=64, seed=0, use_graph=True, arch='yolov3'):
-        """arch: 'yolov3' | 'yolov3-tiny', the standard network built when cfgfile is None (a cfg file always decides the architecture)."""
+        """arch: 'yolov3' | 'yolov3-tiny' | 'yolov3-spp', the standard network built when cfgfile is None (a cfg file always decides the architecture)."""
         if not use_cuda or not torch.cuda.is_available():
             raise RuntimeError('YOLOv3 needs a GPU (HIP kernels only; no CPU fallback)')
         self.lib = _lib.load()
