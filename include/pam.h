@@ -134,6 +134,37 @@ int pam_sync(PamHandle* h, void* stream);
  * dev_word = NULL removes the guard. */
 int pam_set_input_guard(PamHandle* h, const int32_t* dev_word);
 
+/* ---- person boxes without the detector, and box lists as crop tables (no reference counterpart: the reference runs its detector on
+ * every frame, /root/reference/src/testmodel.py:59-63) ---------------------------------------------------------------------------
+ * pam_track_boxes: person boxes of frame_id from the tracker state as the frame launches already on `stream` leave it (the state lives in
+ * global memory between frames; the kernel only reads it and does not look at the input guard).  Tracks in list order (the record's
+ * order), Tentative and Confirmed alike.  A track is eligible iff 0 <= gap <= max_gap with gap = frame_id - (time of its newest pose);
+ * its pose is moved to frame_id by the frame step's own constant-velocity expression (newest + (double)(velocity * (float)gap), a
+ * float32 product added in double) and projected into every view; a (track, view) pair gets a box iff all 17 joints lie in front of
+ * the camera.  Box, in double: centre = middle of the joints' min / max, half sizes = 0.5 * grow * (max - min) + pad_px, clamped to
+ * [0, frame_w] x [0, frame_h], dropped if the clamped width or height is < min_size_px, rounded once to float32; score 1.0f.
+ * Output in pam_yolo_detect's layout for C = n_views images: dev_boxes C * max_det rows (x1, y1, x2, y2, score) (unused rows zero),
+ * dev_count[v] = rows written for view v (at most max_det), dev_count[C + v] = boxes before that clamp, dev_ids (C * max_det, or NULL)
+ * the rows' track ids (-1 where unused), dev_info[0] = 1 if any view was clamped, dev_info[1] = eligible tracks.
+ * PAM_E_ARG, before any device call: NULL handle, max_det < 1, a NULL output (dev_ids excepted), a scene the handle does not have.
+ *
+ * pam_crop_table (csrc/pam_boxes.hip; no handle): detector-layout box lists -> the tables pam_preprocess_crops* / pam_head_decode* take,
+ * for a host that does not know the counts.  Local view i < n_views reads the list of image g = dev_views ? dev_views[i] : i (rows at
+ * dev_boxes + g * max_det_in * 5, count dev_count[g], clamped to [0, max_det_in]) and keeps its first min(count, max_dets) rows; rows are
+ * ordered by (view, slot) and only the first `cap` of them stay (dev_n_det[i] = rows view i kept).  Row r: dev_view_of[r] = i,
+ * dev_slot_of[r] = slot, dev_xywh[r] = (max(0, x1), max(0, y1), min(x2, frame_w) - x, min(y2, frame_h) - y) -- clamped and subtracted in
+ * double, one rounding to float32, nothing dropped: bit-identical to the boxes ivclabpose.PersonDetect hands HRNetPose.predict.  Rows
+ * [total, cap) repeat row total - 1 (same view, slot and box: they decode the same crop into the same slot), or (view 0, slot 0, the
+ * whole frame) when total = 0, so crop, forward and decode can be launched for cap rows.  dev_info[0] = total, [1] = rows wanted before
+ * the cap cut, [2] = 1 if a view's list was cut to max_dets | 2 if the rows were cut to cap, [3] = 0.  One workgroup; n_views <= 256.
+ * PAM_E_ARG: a NULL pointer (dev_views excepted), n_views / max_det_in / max_dets / cap < 1. */
+int pam_track_boxes(PamHandle* h, void* stream, int scene, int frame_id, int frame_w, int frame_h, float grow, float pad_px,
+                    float min_size_px, int max_gap, int max_det, float* dev_boxes, int32_t* dev_count, int32_t* dev_ids,
+                    int32_t* dev_info);
+int pam_crop_table(void* stream, int n_views, const int32_t* dev_views, const float* dev_boxes, const int32_t* dev_count,
+                   int max_det_in, int frame_w, int frame_h, int max_dets, int cap, int32_t* dev_view_of, int32_t* dev_slot_of,
+                   float* dev_xywh, int32_t* dev_n_det, int32_t* dev_info);
+
 /* ---- per-operator entry points (parity tests; host buffers, synchronous) -----------------------------------*/
 /* Camera.projectPoints_parallel, ivclabpose.py:91-98: n poses (17x3) -> (17x2) in (y, x) */
 int pam_op_project(PamHandle* h, int cid, int n, const double* poses3d, double* out_yx);

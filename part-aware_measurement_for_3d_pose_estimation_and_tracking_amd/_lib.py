@@ -97,6 +97,8 @@ _SIGS = {
     'pam_flag_signal_mask': (_I, [_P, _P, C.c_uint32]),
     'pam_flag_gate': (_I, [_P, _P, _I, _P, _P, _I, _P, _P]),
     'pam_set_input_guard': (_I, [_P, _P]),
+    'pam_track_boxes': (_I, [_P, _P, _I, _I, _I, _I, C.c_float, C.c_float, C.c_float, _I, _I, _P, _P, _P, _P]),
+    'pam_crop_table': (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     'pam_comm_unique_id': (_I, [_P]),
     'pam_comm_init': (_I, [C.POINTER(_P), _I, _I, _P, _I]),
     'pam_comm_destroy': (_I, [_P]),
@@ -124,6 +126,11 @@ _SIGS = {
 EXPORTS = tuple(_SIGS)
 YOLO_MAX_CAND = 1024        # PAM_YOLO_MAX_CAND in include/pam.h
 SPP_MAX_HW = 32             # PAM_SPP_MAX_HW in include/pam.h
+
+# the box rule of pam_track_boxes as the Python layers default it: synth.to_dump_results' growth, the pad that the oracle-tracker
+# measurement needed, the reference's 2D age filter (time_interval <= 3)
+TRACK_BOX_RULE = dict(grow=1.25, pad_px=8.0, min_size_px=8.0, max_gap=3)
+CROP_CUT_VIEW, CROP_CUT_CAP = 1, 2         # pam_crop_table's info[2]
 
 _lib = None
 
@@ -316,6 +323,19 @@ class Handle(object):
         untouched): the word is raised by the producer of the keypoints (HRNetPose.void_word).  None / 0 removes the guard."""
         self._chk(self.lib.pam_set_input_guard(self._h, C.c_void_p(dev_word_ptr or None)))
 
+    def track_boxes(self, stream, frame_id, frame_w, frame_h, boxes, count, ids=None, info=None, scene=0, grow=1.25, pad_px=8.0,
+                    min_size_px=8.0, max_gap=3):
+        """Person boxes of ``frame_id`` from the tracker state behind whatever is queued on ``stream`` (pam_track_boxes).  boxes
+        (C, max_det, 5) float32, count (2C,) int32, ids (C, max_det) int32 or None, info (2,) int32: contiguous device tensors, written
+        in the detector's layout (``YOLOv3.detect_dev``)."""
+        max_det = int(boxes.shape[1])
+        assert tuple(boxes.shape) == (self.C, max_det, 5) and boxes.is_contiguous() and count.numel() == 2 * self.C and info.numel() >= 2
+        assert ids is None or (ids.numel() == self.C * max_det and ids.is_contiguous())
+        self._chk(self.lib.pam_track_boxes(self._h, C.c_void_p(stream), int(scene), int(frame_id), int(frame_w), int(frame_h), float(grow),
+                                           float(pad_px), float(min_size_px), int(max_gap), max_det, C.c_void_p(boxes.data_ptr()),
+                                           C.c_void_p(count.data_ptr()), C.c_void_p(ids.data_ptr()) if ids is not None else None,
+                                           C.c_void_p(info.data_ptr())))
+
     def pinned_record(self):
         """(keep, out_i, out_d): ONE pinned host buffer laid out like the device record (int32 section padded to 8 bytes, float64 section
         behind it) and NumPy views of its two sections -- ``fetch`` into them is a single device -> host copy."""
@@ -445,3 +465,19 @@ class Handle(object):
         cost = C.c_double(0); veto = C.c_int32(0)
         self._chk(self.lib.pam_op_hyp_cost(self._h, len(c), _ptr(c), _ptr(ps), int(o_cid), _ptr(po), C.byref(cost), C.byref(veto)))
         return cost.value, bool(veto.value)
+
+
+def crop_table(stream, boxes, count, frame_w, frame_h, max_dets, view_of, slot_of, xywh, n_det, info, views=None):
+    """Detector-layout box lists -> crop table (pam_crop_table).  boxes (V, max_det_in, 5) float32 and count (>= V,) int32 as
+    ``YOLOv3.detect_dev`` / ``Handle.track_boxes`` leave them; views: int32 device tensor of the images to take, in order (None = the
+    first ``n_det.numel()``); view_of / slot_of (cap,) int32, xywh (cap, 4) float32, n_det (n_views,) int32, info (4,) int32 are written.
+    All contiguous device tensors; asynchronous on ``stream``."""
+    cap, n_views = int(view_of.numel()), int(n_det.numel())
+    assert boxes.dim() == 3 and boxes.shape[2] == 5 and boxes.is_contiguous() and xywh.numel() == 4 * cap and slot_of.numel() == cap
+    assert info.numel() >= 4 and (views is None or views.numel() == n_views) and (views is not None or n_views <= boxes.shape[0])
+    rc = load().pam_crop_table(C.c_void_p(stream), n_views, C.c_void_p(views.data_ptr()) if views is not None else None,
+                               C.c_void_p(boxes.data_ptr()), C.c_void_p(count.data_ptr()), int(boxes.shape[1]), int(frame_w), int(frame_h),
+                               int(max_dets), cap, C.c_void_p(view_of.data_ptr()), C.c_void_p(slot_of.data_ptr()),
+                               C.c_void_p(xywh.data_ptr()), C.c_void_p(n_det.data_ptr()), C.c_void_p(info.data_ptr()))
+    if rc != 0:
+        raise PamError('pam_crop_table failed (%d)' % rc)

@@ -77,6 +77,18 @@ class ivclabpose(object):
         self.device = device
         self.cameras = None
         self.pose_model = None
+        # optional keys of the detector's block (not in the reference's YAMLs; absent = the detector on every frame): DETECT_EVERY = K runs
+        # the detector on every K-th frame and takes the boxes of the frames in between from the tracks (PersonBoxesFromTracks);
+        # TRACK_BOX_GROW / TRACK_BOX_PAD = that box rule's growth and pad in pixels
+        from . import _lib
+        dopt = lambda k: (person_detector.get(k) if isinstance(person_detector, dict) else getattr(person_detector, k, None)) if person_detector is not None else None
+        self.detect_every = int(dopt('DETECT_EVERY') or 1)
+        self.track_box_rule = dict(_lib.TRACK_BOX_RULE)
+        if dopt('TRACK_BOX_GROW') is not None:
+            self.track_box_rule['grow'] = float(dopt('TRACK_BOX_GROW'))
+        if dopt('TRACK_BOX_PAD') is not None:
+            self.track_box_rule['pad_px'] = float(dopt('TRACK_BOX_PAD'))
+        self.frames_scheduled = 0
         if self.person_detector is None:
             print("Person Detector : Close.")
         elif _cfg(self.person_detector, 'NAME') == 'YOLOv3':                        # ivclabpose.py:116-120
@@ -175,6 +187,32 @@ class ivclabpose(object):
             return None
         imglist, image_id, ticket = ahead
         return self._person_dicts(imglist, image_id, self.bbox_detector.collect(ticket))
+
+    def box_source(self, ahead=0):
+        """'detector' | 'tracks' for the frame `ahead` frames after the next one ``schedule_frame`` hands out (pipeline.box_source on
+        DETECT_EVERY); always 'detector' without a detector block's DETECT_EVERY."""
+        from .pipeline import box_source
+        return box_source(self.frames_scheduled + ahead, self.detect_every, self.person_detector is not None)
+
+    def schedule_frame(self):
+        """The source of the next frame's boxes; counts the frame."""
+        src = self.box_source()
+        self.frames_scheduled += 1
+        return src
+
+    def PersonBoxesFromTracks(self, imglist, image_id):
+        """Not in the reference: a person_bbox_list in PersonDetect's format (plus a ``track_id`` key) whose boxes are drawn round the
+        tracks' predicted poses for frame image_id instead of coming from the detector (IterativeTracker.predict_boxes; rule:
+        ``self.track_box_rule``).  Tentative and Confirmed tracks, in the tracker's list order; empty lists before the first frame."""
+        if self.tracker is None or self.tracker.handle is None:
+            return [[] for _ in imglist]
+        h, w = imglist[0].shape[:2]
+        rows = self.tracker.predict_boxes(image_id, (h, w), **self.track_box_rule)
+        out = self._person_dicts(imglist, image_id, [r[:, :5] for r in rows])
+        for persons, r in zip(out, rows):
+            for p, row in zip(persons, r):
+                p['track_id'] = int(row[5])
+        return out
 
     def _person_dicts(self, imglist, image_id, results):
         person_bbox_list = []

@@ -16,11 +16,26 @@ from .hrnet import HRNetPose
 NUM_JOINTS = 17
 
 
+def box_source(frame_no, detect_every=1, have_detector=True):
+    """Where the person boxes of a frame come from: 'detector' on every detect_every-th frame, counted from the last reset (frame_no %
+    detect_every == 0: the detector finds who enters), 'tracks' in between (boxes round the tracks' predicted poses, pam_track_boxes).
+    Pure: the schedule is the same on every rank.  A schedule that asks for a detector nobody attached is an error, never a silent
+    frame of track boxes."""
+    detect_every = int(detect_every)
+    if detect_every < 1:
+        raise ValueError('detect_every must be >= 1')
+    if int(frame_no) % detect_every == 0:
+        if not have_detector:
+            raise ValueError('frame %d is a detector frame and no detector is attached' % frame_no)
+        return 'detector'
+    return 'tracks'
+
+
 class FramePipeline(object):
     def __init__(self, calib_cameras, matcher, conf_threshold, frame_hw, max_dets=8, max_tracks=16, device=0, world=1,
                  rank=0, group=None, use_graph=True, hrnet=True, seed=0, shard='views', overlap_tracker=False, net=None, exchange='torch',
                  pose_streams=1, autotune=True, prewarm=False, width=48, resolution=(384, 288), flip_test=False, shift_heatmap=True,
-                 post_process=False, model_name='HRNet'):
+                 post_process=False, model_name='HRNet', crop_cap=None, detect_every=1):
         """shard: 'views' -- rank owns whole camera views (pose_step / track_step take view-local inputs); 'crops' -- the
         frame's crops are dealt out evenly over the ranks (pose_step_crops / track_step_crops take global view indices).
         overlap_tracker (either mode): exchange + tracker kernel + fetch of frame t run on their own stream, under the conv
@@ -36,7 +51,11 @@ class FramePipeline(object):
         width / resolution: the pose network FramePipeline builds when no `net` is given (HRNet-W48 at 384 x 288; 32 / (256, 192) = W32;
         model_name='PoseResNet' with width = the ResNet depth, as HRNetPose takes it).
         flip_test / shift_heatmap / post_process: that network's decode options (HRNetPose: the official test protocol; the flip test
-        doubles every forward, prewarm captures the doubled counts).  A shared `net` keeps its own settings."""
+        doubles every forward, prewarm captures the doubled counts).  A shared `net` keeps its own settings.
+        crop_cap: rows of the device-built crop table (pose_step_boxes): crop, forward and decode of such a frame run for this many rows
+        whatever the boxes' count.  None = this rank's views x max_dets; under prewarm rounded up to the network's bucket.
+        detect_every: the schedule of pose_step_auto (box_source): the detector on every detect_every-th frame since the last reset(),
+        boxes round the tracks' predictions in between."""
         self.device = torch.device('cuda:%d' % device)
         torch.cuda.set_device(self.device)
         self.cams = calib_cameras
@@ -96,6 +115,18 @@ class FramePipeline(object):
             if shard == 'crops' and world > 1:
                 most = (most + world - 1) // world
             self.warmed = self.net.warm(most, slots=(0, 1) if pose_streams > 1 else (0,))
+        self.detect_every, self._auto_no, self._det_ahead = int(detect_every), 0, None
+        if self.detect_every < 1:
+            raise ValueError('detect_every must be >= 1')
+        self.crop_cap = int(crop_cap) if crop_cap is not None else max(1, len(self.mine) * max_dets)
+        if self.crop_cap < 1:
+            raise ValueError('crop_cap must be >= 1')
+        if self.bucketed and self.net is not None:
+            self.crop_cap = self.net.bucket(self.crop_cap)
+        self._tables, self._tb, self._table_info, self.table_n_det = None, None, None, None
+        self._ct_host = torch.zeros(4, dtype=torch.int32).pin_memory()
+        self._ct_fetched = False
+        self._ev_slot_read, self._table_no, self._table_slot = [None, None], 0, 0
 
     def _pick_track_stream(self, tries=8, spin_us=400, avoid=None):
         """A stream for the exchange + tracker that REALLY runs beside the caller's (pose) stream.  HIP streams are multiplexed onto a few
@@ -234,6 +265,7 @@ class FramePipeline(object):
 
     def pose_step(self, frame_ptrs, view_local, slot_of, boxes, time_events=None, after_crop=None):
         """HRNet side for this rank's crops.  view_local: int32 (N,) index into self.mine; writes self.det_local."""
+        self._table_info = None
         if int(view_local.numel()) == 0 or self.net is None:
             if after_crop is not None:
                 after_crop()
@@ -257,6 +289,9 @@ class FramePipeline(object):
             self.handle.frame_dev_views(st, frame_id, recv.data_ptr(), self.gather.rows.data_ptr())
             if fetch:
                 self.handle.fetch(st, self.out_i.numpy(), self.out_d.numpy())
+                self._ct_fetched = self._table_info is not None
+                if self._ct_fetched:                     # the crop table's info words travel with the record (results())
+                    self._ct_host.copy_(self._table_info, non_blocking=True)
         if self.track_stream is None:
             issue(self.stream_ptr())
             return
@@ -265,7 +300,107 @@ class FramePipeline(object):
             self.track_stream.wait_event(self.ev_pose)
             issue(self.track_stream.cuda_stream)
             self.ev_track.record(self.track_stream)
+            if self._table_info is not None:             # this frame's table set (its n_det) has been read: pose_step_boxes may refill it
+                k = self._table_slot
+                self._ev_slot_read[k] = self._ev_slot_read[k] or torch.cuda.Event()
+                self._ev_slot_read[k].record(self.track_stream)
         self._track_pending = True
+
+    # -- person boxes that never visit the host ------------------------------------------------------------------------------
+    def reset(self):
+        """Forget every track (handle.reset()) and restart the schedule of pose_step_auto: the next frame is a detector frame."""
+        self.handle.reset()
+        self._auto_no, self._det_ahead = 0, None
+
+    def _box_buffers(self):
+        if self._tables is None:
+            dev, cap, nv = self.device, self.crop_cap, max(1, len(self.mine))
+            self._tables = [dict(view_of=torch.zeros(cap, dtype=torch.int32, device=dev), slot_of=torch.zeros(cap, dtype=torch.int32, device=dev),
+                                 xywh=torch.zeros((cap, 4), dtype=torch.float32, device=dev),
+                                 n_det=torch.zeros(nv, dtype=torch.int32, device=dev), info=torch.zeros(4, dtype=torch.int32, device=dev))
+                            for _ in range(2)]
+            self._tb = dict(boxes=torch.zeros((self.C, self.max_dets, 5), dtype=torch.float32, device=dev),
+                            count=torch.zeros(2 * self.C, dtype=torch.int32, device=dev),
+                            ids=torch.zeros((self.C, self.max_dets), dtype=torch.int32, device=dev),
+                            info=torch.zeros(2, dtype=torch.int32, device=dev))
+            self._mine_dev = torch.tensor(list(self.mine) or [0], dtype=torch.int32, device=dev)
+            self.ev_boxes = torch.cuda.Event()
+
+    def track_boxes(self, frame_id, **rule):
+        """Person boxes of frame_id round the tracks' constant-velocity predictions (pam_track_boxes; rule: grow, pad_px, min_size_px,
+        max_gap, defaults _lib.TRACK_BOX_RULE) -> (boxes (C, max_dets, 5), count (2C,), ids (C, max_dets)) device tensors for ALL C
+        views, in the detector's layout; pipeline-owned, valid until the next call.
+        Ordering: the kernel is issued behind the last tracker step that was issued -- on the track stream when there is one, with an
+        event the current (pose) stream then waits on.  So the boxes always come from the state after the previous track_step, whatever
+        overlap_tracker says: a frame whose boxes come from here cannot start its crops before the previous frame's k_frame has ended,
+        which costs the overlap of k_frame under this frame's forward (the record's fetch still overlaps)."""
+        self._box_buffers()
+        b = self._tb
+        kw = dict(_lib.TRACK_BOX_RULE); kw.update(rule)
+        if self.track_stream is not None and self._track_pending:
+            with torch.cuda.stream(self.track_stream):
+                self.handle.track_boxes(self.track_stream.cuda_stream, frame_id, self.frame_w, self.frame_h, b['boxes'], b['count'], b['ids'],
+                                        b['info'], **kw)
+                self.ev_boxes.record(self.track_stream)
+            torch.cuda.current_stream(self.device).wait_event(self.ev_boxes)
+        else:
+            self.handle.track_boxes(self.stream_ptr(), frame_id, self.frame_w, self.frame_h, b['boxes'], b['count'], b['ids'], b['info'], **kw)
+        return b['boxes'], b['count'], b['ids']
+
+    def pose_step_boxes(self, frame_ptrs, boxes, count, views=None, time_events=None, after_crop=None):
+        """pose_step on boxes that are on the device in the detector's layout (YOLOv3.detect_dev, track_boxes): boxes (G, max_det, 5)
+        float32, count (>= G,) int32; views: int32 device tensor, for each of this rank's views the image of `boxes` that holds its list
+        (None: image i is view mine[i]).  pam_crop_table turns them into a crop table of crop_cap rows (spare rows repeat the last real
+        one), and crop, forward and decode run for crop_cap rows through the kernels pose_step uses.  ``self.table_n_det`` (device, one
+        count per view of this rank) is the n_det_local for track_step."""
+        if self.shard != 'views':
+            raise ValueError("pose_step_boxes needs shard='views': crop sharding builds its select index from a host box list")
+        if not len(self.mine) or self.net is None:
+            if after_crop is not None:
+                after_crop()
+            return
+        self._box_buffers()
+        k = self._table_slot = self._table_no & 1       # two sets: the track step of the frame before may still be reading the other one
+        self._table_no += 1
+        T = self._tables[k]
+        cur = torch.cuda.current_stream(self.device)
+        if self._ev_slot_read[k] is not None:
+            cur.wait_event(self._ev_slot_read[k])       # the track step of two frames ago has read this set's counts
+        _lib.crop_table(cur.cuda_stream, boxes, count, self.frame_w, self.frame_h, self.max_dets, T['view_of'], T['slot_of'], T['xywh'],
+                        T['n_det'], T['info'], views=views)
+        self.table_n_det, self._table_info = T['n_det'], T['info']
+        self._pose(frame_ptrs, T['view_of'], T['slot_of'], T['xywh'], self.det_local, time_events, after_crop)
+
+    def pose_step_auto(self, frame_id, frame_ptrs, frames, next_frames=None, time_events=None, after_crop=None, **rule):
+        """pose_step_boxes with the boxes the schedule names (box_source(frames since reset(), detect_every)): the detector's -- the
+        result of the detect_ahead this method issued during the frame before when `next_frames` was given, else detect_dev(frames) in
+        line -- or track_boxes(frame_id).  frames: this rank's (views, H, W, 3) uint8 device tensor; next_frames: the next frame's, to
+        run its detection under this frame's forward when the next frame is a detector frame.  -> 'detector' | 'tracks'."""
+        det = getattr(self, 'detector', None)
+        src = box_source(self._auto_no, self.detect_every, det is not None)
+        views = None
+        if src == 'detector':
+            if self._det_ahead is not None:
+                boxes, count = self._det_ahead
+                self._det_ahead = None
+                self.wait_detection()
+            else:
+                boxes, count = det.detect_dev(frames)
+        else:
+            boxes, count, _ = self.track_boxes(frame_id, **rule)
+            self._box_buffers()
+            views = self._mine_dev
+        ahead = next_frames is not None and det is not None and hasattr(self, 'det_stream') and \
+            box_source(self._auto_no + 1, self.detect_every, True) == 'detector'
+
+        def crop_done():
+            if after_crop is not None:
+                after_crop()
+            if ahead:
+                self._det_ahead = self.detect_ahead(next_frames)
+        self.pose_step_boxes(frame_ptrs, boxes, count, views=views, time_events=time_events, after_crop=crop_done)
+        self._auto_no += 1
+        return src
 
     # -- crop-balanced sharding ----------------------------------------------------------------------------------------------
     def wait_track(self):
@@ -331,4 +466,7 @@ class FramePipeline(object):
         if strict and (rec['status'] | rec['status_sticky']) != 0:
             raise _lib.PamError('tracker status 0x%x on frame %d, 0x%x over the run (1 track slots, 2 hypothesis slots, 4 infeasible '
                                 'assignment, 8 clamped detection count)' % (rec['status'], rec['frame_id'], rec['status_sticky']))
+        if self._ct_fetched:
+            w = self._ct_host.numpy()
+            rec['crop_table'] = dict(rows=int(w[0]), wanted=int(w[1]), status=int(w[2]))
         return rec

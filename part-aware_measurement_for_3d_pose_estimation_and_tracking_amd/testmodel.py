@@ -39,8 +39,12 @@ def frame_inputs(model, precomputed, frame_id, imagelist, ahead=None, next_frame
     nxt = None
     if model.person_detector is not None:                    # testmodel.py:56-58
         t0 = time.time()
-        pbl = model.PersonDetectResult(ahead) if ahead is not None else model.PersonDetect(imagelist, frame_id)
-        if next_frame is not None:
+        # DETECT_EVERY (optional key): the detector on every K-th frame, boxes round the tracks' predictions in between
+        if model.schedule_frame() == 'detector':
+            pbl = model.PersonDetectResult(ahead) if ahead is not None else model.PersonDetect(imagelist, frame_id)
+        else:
+            pbl = model.PersonBoxesFromTracks(imagelist, frame_id)
+        if next_frame is not None and model.box_source() == 'detector':      # (the next frame's source: schedule_frame has counted this one)
             nxt = model.PersonDetectAhead(next_frame[1], next_frame[0])
         dt_det = time.time() - t0
     else:

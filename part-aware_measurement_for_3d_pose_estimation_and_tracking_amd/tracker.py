@@ -104,6 +104,25 @@ class IterativeTracker(object):
         self.handle.reset()
         self.tracks = []
 
+    def predict_boxes(self, frame_id, frame_hw, **rule):
+        """Person boxes of frame_id round the tracks' constant-velocity predictions, from the device-resident state (pam_track_boxes;
+        not in the reference, whose boxes always come from its detector).  frame_hw = (height, width) the boxes are clamped to; rule:
+        grow, pad_px, min_size_px, max_gap (_lib.TRACK_BOX_RULE).  -> per view a host (k, 6) float64 array of rows (x1, y1, x2, y2,
+        score, track_id), tracks in list order; the coordinates are the device's float32 values."""
+        import torch
+        if self.handle is None:
+            raise _lib.PamError('predict_boxes before set_cameras')
+        dev, C, md = torch.device('cuda:%d' % self.device), self.cam_num, self.max_tracks
+        if getattr(self, '_tb', None) is None or self._tb[0].shape[0] != C:
+            self._tb = (torch.zeros((C, md, 5), dtype=torch.float32, device=dev), torch.zeros(2 * C, dtype=torch.int32, device=dev),
+                        torch.zeros((C, md), dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev))
+        boxes, count, ids, info = self._tb
+        kw = dict(_lib.TRACK_BOX_RULE); kw.update(rule)
+        st = torch.cuda.current_stream(dev)
+        self.handle.track_boxes(st.cuda_stream, frame_id, int(frame_hw[1]), int(frame_hw[0]), boxes, count, ids, info, **kw)
+        b, n, i = boxes.cpu().numpy(), count.cpu().numpy(), ids.cpu().numpy()          # (the copies wait for the kernel)
+        return [np.concatenate([b[v, :n[v]].astype(np.float64), i[v, :n[v], None].astype(np.float64)], axis=1) for v in range(C)]
+
     def tracking(self, frame_id, camera_list, frame_list, boxes_list, detections_list, build3D='SVD'):
         assert build3D == 'SVD', "Please modify BUILD3D to SVD when PERSON_MATCHER == Iterative"
         if self.cameras is None or self.cameras is not camera_list:     # the reference uses the camera_list of every call
