@@ -270,6 +270,34 @@ int pam_head_decode_flip(void* stream, int n, int flip_row0, int hm_h, int hm_w,
                          const float* bias, int J, int flags, float* dev_heatmaps_or_null, const int32_t* dev_view_of,
                          const int32_t* dev_slot_of, const float* dev_boxes, int max_dets, double* dev_det, float* dev_kp_xyc,
                          void* dev_scratch);
+/* pam_head_decode_dark: the DARK decode (Zhang et al., "Distribution-Aware Coordinate Representation for Human Pose Estimation", CVPR
+ * 2020; the test protocol of the DARK-trained HRNet / Simple Baselines checkpoints) in the head pass: Gaussian blur, logarithm, one
+ * Newton step of the log map's second-order Taylor expansion at the arg-max.  Arguments as pam_head_decode_flip; flags takes
+ * PAM_FLIP_MERGE and PAM_FLIP_SHIFT under the rules there, and M is the map they define (M = P without MERGE).  blur_kernel = k, odd,
+ * 9 <= k <= 17 (below 9 OpenCV uses fixed tap tables): R = (k - 1) / 2, sigma = 0.3 * ((k - 1) * 0.5 - 1) + 0.8 (OpenCV's rule for
+ * GaussianBlur(.., (k, k), 0): 2.0 at 11, 2.9 at 17), taps g[i] = exp(-(i - R)^2 / (2 sigma^2)) normalised to sum 1, in float64.
+ *   1. (py, px) = arg-max of M, NOT of the blurred map (first maximum; nothing above -inf: cell 0); the score is M[py][px].
+ *   2. The offset applies only where 1 < px < hm_w - 2 and 1 < py < hm_h - 2 (one cell tighter than PAM_FLIP_QUARTER: the second
+ *      derivatives read +- 2); elsewhere the keypoint is the plain arg-max.
+ *   3. B = blur(M): separable, rows first, then columns, float64 sums in ascending tap order, cells outside the map count as 0 (the
+ *      official code frames the map with R zeros before cv2.GaussianBlur, so no reflected sample is ever read).
+ *   4. L = log(max(B, 1e-10)) in float64 (a NaN is clamped as well).
+ *   5. dx = 0.5 (L[py][px+1] - L[py][px-1]), dy alike; dxx = 0.25 (L[py][px+2] - 2 L[py][px] + L[py][px-2]), dyy alike;
+ *      dxy = 0.25 (L[py+1][px+1] - L[py-1][px+1] - L[py+1][px-1] + L[py-1][px-1]).
+ *   6. If dxx dyy - dxy^2 != 0: (ox, oy) = -H^-1 (dx, dy), keypoint (py + oy, px + ox).  Otherwise no offset.  Nothing clamps the offset.
+ *   7. The box mapping of pam_decode_heatmaps (float64 arithmetic, one float32 rounding).
+ * One deviation from the official code, which rescales B by max(M) / max(B) before the clamp: under the logarithm a positive scale is
+ * an additive constant and drops out of every derivative, so it is left out (no whole-map maximum is needed and the maps stay out of
+ * memory).  The results are equal whenever max(M) > 0, max(B) > 0 and no sampled B lies in (0, 1e-10 max(B) / max(M)] -- every map that
+ * shows a joint (float64 check on planted blobs: 2e-14 cell).  On an all-negative map the official scale is negative and un-clamps the
+ * map, an artefact; this entry point's definition is the scale-free one above.
+ * dev_heatmaps_or_null receives M, as in pam_head_decode_flip.  dev_scratch: pam_head_decode_dark_scratch_bytes(n, hm_h, hm_w) bytes.
+ * PAM_E_ARG: PAM_FLIP_QUARTER or unknown bits, an even or out-of-range blur_kernel, and what pam_head_decode_flip refuses.  n == 0: PAM_OK. */
+long long pam_head_decode_dark_scratch_bytes(int n, int hm_h, int hm_w);
+int pam_head_decode_dark(void* stream, int n, int flip_row0, int hm_h, int hm_w, const void* feat_bf16, int C, const float* w,
+                         const float* bias, int J, int flags, int blur_kernel, float* dev_heatmaps_or_null, const int32_t* dev_view_of,
+                         const int32_t* dev_slot_of, const float* dev_boxes, int max_dets, double* dev_det, float* dev_kp_xyc,
+                         void* dev_scratch);
 int pam_decode_heatmaps(void* stream, int n, const float* dev_heatmaps, int nchw, int hm_h, int hm_w,
                         const int32_t* dev_view_of, const int32_t* dev_slot_of, const float* dev_boxes,
                         int max_dets, double* dev_det, float* dev_kp_xyc /*optional n*17*3 (x,y,conf) or NULL*/);

@@ -536,6 +536,135 @@ extern "C" int pam_head_decode_flip(void* stream, int n, int flip_row0, int hm_h
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
 }
 
+// ---- DARK decode (Zhang et al., CVPR 2020): Gaussian blur, logarithm, one Newton step at the arg-max -- contract in include/pam.h --------
+// The winner is known only after the fold, and the step needs the blurred map at 13 cells round it: the cross px +- 2 / py +- 2 and the four
+// diagonal neighbours.  Those depend on the (2R + 5)^2 window of M round the winner (R = (k - 1) / 2; 21 x 21 at k = 17), which is recomputed
+// from the features with head_chain -- the map's own bits, as in k_argmax_finish_flip -- so the maps still never reach memory.
+// One workgroup per (crop, joint): the joint is uniform, so the weight row of every chain comes through scalar loads.
+//   1. every thread folds the tile candidates (the same loads); a winner outside 1 < px < w - 2, 1 < py < h - 2 is written as it is
+//   2. window -> LDS as float32, 0 outside the map: one chain per thread and step (MERGE: the mirrored crop's chains of joint pair(j) are
+//      further steps of the same loop, then one pass forms 0.5f * (p + f), the sum k_head_argmax_flip forms)
+//   3. horizontal pass, float64, ascending taps: the 5 columns px - 2 .. px + 2 of all 2R + 5 rows
+//   4. vertical pass over those: the 13 cells
+//   5. thread 0: clamp at 1e-10, 13 logarithms, the 2 x 2 solve, write_keypoint_at
+// The taps are the host's doubles, passed by value; t is wave-uniform in both passes, so they too are scalar operands.
+struct DarkTaps { double g[17]; };
+#define DARK_T 256
+#define DARK_W 21             // 2 R + 5 at the largest blur, k = 17
+template <bool MERGE>
+__global__ __launch_bounds__(DARK_T) void k_dark_finish(int tiles, const Best* __restrict__ cand, int hm_h, int hm_w,
+                                                        const uint16_t* __restrict__ feat, int C, const float* __restrict__ w,
+                                                        const float* __restrict__ bias, int flip_row0, int shift, int R, DarkTaps taps,
+                                                        const int* __restrict__ view_of, const int* __restrict__ slot_of,
+                                                        const float* __restrict__ boxes, int max_dets, double* __restrict__ det,
+                                                        float* __restrict__ kp) {
+    __shared__ float win[MERGE ? 2 : 1][DARK_W * DARK_W];
+    __shared__ double bh[DARK_W * 5];
+    __shared__ double bv[13];
+    const int crop = blockIdx.x / J, j = blockIdx.x - crop * J, tid = threadIdx.x;
+    Best b; b.v = -__builtin_huge_valf(); b.i = 0x7fffffff;
+    for (int t0 = 0; t0 < tiles; t0 += 8) {
+        Best c[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int t = min(t0 + q, tiles - 1);
+            c[q] = cand[((size_t)crop * tiles + t) * J + j];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if (t0 + q < tiles && c[q].v > b.v) b = c[q];
+    }
+    if (b.i == 0x7fffffff) b.i = 0;        // no value above -inf: cell 0 (never inside: no offset)
+    const int py = b.i / hm_w, px = b.i - py * hm_w, HW = hm_h * hm_w;
+    double* row = det + ((size_t)view_of[crop] * max_dets + slot_of[crop]) * J * 3;
+    float* kp_row = kp ? kp + (size_t)crop * J * 3 : nullptr;
+    if (!(1 < px && px < hm_w - 2 && 1 < py && py < hm_h - 2)) {       // the same for the whole workgroup: nobody waits at a barrier below
+        if (tid == 0) write_keypoint_at(j, (double)py, (double)px, b.v, hm_h, hm_w, boxes + crop * 4, row, kp_row);
+        return;
+    }
+    const int W = 2 * R + 5, cells = W * W, y0 = py - R - 2, x0 = px - R - 2, k = 2 * R + 1;
+    for (int i = tid; i < (MERGE ? 2 : 1) * cells; i += DARK_T) {
+        const int part = i >= cells, c = i - part * cells;
+        const int wy = c / W, wx = c - wy * W, y = y0 + wy, x = x0 + wx;
+        float v = 0.0f;
+        if (y >= 0 && y < hm_h && x >= 0 && x < hm_w)
+            v = part ? head_chain(feat + ((size_t)(flip_row0 + crop) * HW + y * hm_w + flip_column(x, hm_w, shift)) * C, C, w, bias, flip_pair(j))
+                     : head_chain(feat + ((size_t)crop * HW + y * hm_w + x) * C, C, w, bias, j);
+        win[part][c] = v;
+    }
+    __syncthreads();
+    if constexpr (MERGE) {
+        for (int c = tid; c < cells; c += DARK_T) win[0][c] = 0.5f * (win[0][c] + win[1][c]);      // (outside the map: 0.5f * (0 + 0))
+        __syncthreads();
+    }
+    for (int i = tid; i < W * 5; i += DARK_T) {                        // B_h[row][px - 2 + d]: window columns d .. d + 2R
+        const int r = i / 5, d = i - r * 5;
+        double s = 0.0;
+        for (int t = 0; t < k; ++t) s += taps.g[t] * (double)win[0][r * W + d + t];
+        bh[i] = s;
+    }
+    __syncthreads();
+    if (tid < 13) {                                                    // (dy, dx) of cell tid: 0 | x+1 x-1 x+2 x-2 | y+1 y-1 y+2 y-2 | ++ -+ +- --
+        const int dy = tid < 5 ? 0 : (tid < 9 ? ((tid & 1) ? 1 : -1) * (tid < 7 ? 1 : 2) : ((tid & 1) ? 1 : -1));
+        const int dx = tid == 0 || (tid >= 5 && tid < 9) ? 0 : (tid < 5 ? ((tid & 1) ? 1 : -1) * (tid < 3 ? 1 : 2) : (tid < 11 ? 1 : -1));
+        double s = 0.0;
+        for (int t = 0; t < k; ++t) s += taps.g[t] * bh[(2 + dy + t) * 5 + 2 + dx];     // window rows 2 + dy .. 2 + dy + 2R
+        bv[tid] = s;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    double L[13];
+#pragma unroll
+    for (int q = 0; q < 13; ++q) L[q] = log(bv[q] > 1e-10 ? bv[q] : 1e-10);                // (a NaN clamps too)
+    const double gx = 0.5 * (L[1] - L[2]), gy = 0.5 * (L[5] - L[6]);
+    const double dxx = 0.25 * (L[3] - 2.0 * L[0] + L[4]), dyy = 0.25 * (L[7] - 2.0 * L[0] + L[8]);
+    const double dxy = 0.25 * (L[9] - L[10] - L[11] + L[12]);
+    const double dt = dxx * dyy - dxy * dxy;
+    double ox = 0.0, oy = 0.0;
+    if (dt != 0.0) {                                                   // -H^-1 g; nothing clamps the step, as in the official code
+        ox = -(dyy * gx - dxy * gy) / dt;
+        oy = -(dxx * gy - dxy * gx) / dt;
+    }
+    write_keypoint_at(j, (double)py + oy, (double)px + ox, b.v, hm_h, hm_w, boxes + crop * 4, row, kp_row);
+}
+
+extern "C" long long pam_head_decode_dark_scratch_bytes(int n, int hm_h, int hm_w) { return pam_head_decode_scratch_bytes(n, hm_h, hm_w); }
+
+extern "C" int pam_head_decode_dark(void* stream, int n, int flip_row0, int hm_h, int hm_w, const void* feat_bf16, int C, const float* w,
+                                    const float* bias, int J_, int flags, int blur_kernel, float* dev_heatmaps_or_null,
+                                    const int32_t* dev_view_of, const int32_t* dev_slot_of, const float* dev_boxes, int max_dets,
+                                    double* dev_det, float* dev_kp_xyc, void* dev_scratch) {
+    const int merge = flags & PAM_FLIP_MERGE, shift = (flags & PAM_FLIP_SHIFT) ? 1 : 0;
+    if (n < 0 || !feat_bf16 || !w || !dev_view_of || !dev_slot_of || !dev_boxes || !dev_det || !dev_scratch || hm_h <= 0 || hm_w <= 0 ||
+        C <= 0 || C % 8 != 0 || J_ != PAM_J || (flags & ~(PAM_FLIP_MERGE | PAM_FLIP_SHIFT)) || (shift && !merge) ||
+        (merge && flip_row0 < n) || blur_kernel < 9 || blur_kernel > 17 || blur_kernel % 2 == 0)
+        return PAM_E_ARG;
+    if (n == 0) return PAM_OK;
+    const int HW = hm_h * hm_w, tiles = (HW + HEAD_T - 1) / HEAD_T, R = (blur_kernel - 1) / 2;
+    DarkTaps taps;                                                     // OpenCV's getGaussianKernel(k, 0): sigma from k, taps normalised to 1
+    const double sigma = 0.3 * ((blur_kernel - 1) * 0.5 - 1.0) + 0.8;
+    double sum = 0.0;
+    for (int i = 0; i < 17; ++i) {
+        taps.g[i] = i < blur_kernel ? exp(-(double)((i - R) * (i - R)) / (2.0 * sigma * sigma)) : 0.0;
+        sum += taps.g[i];
+    }
+    for (int i = 0; i < 17; ++i) taps.g[i] /= sum;
+    const uint16_t* f = (const uint16_t*)feat_bf16;
+    if (merge) {
+        hipLaunchKernelGGL((k_head_argmax_flip<PAM_J>), dim3(n * tiles), dim3(HEAD_T), (size_t)HEAD_T * (J_ + 1) * sizeof(float),
+                           (hipStream_t)stream, HW, tiles, f, C, w, bias, dev_heatmaps_or_null, (Best*)dev_scratch, hm_w, flip_row0, shift);
+        hipLaunchKernelGGL((k_dark_finish<true>), dim3(n * J_), dim3(DARK_T), 0, (hipStream_t)stream, tiles, (const Best*)dev_scratch, hm_h, hm_w,
+                           f, C, w, bias, flip_row0, shift, R, taps, dev_view_of, dev_slot_of, dev_boxes, max_dets, dev_det, dev_kp_xyc);
+    } else {
+        const size_t lds = (size_t)J_ * C * sizeof(float) + (size_t)(HEAD_T / 64) * J_ * sizeof(Best) + (size_t)HEAD_T * (J_ + 1) * sizeof(float);
+        hipLaunchKernelGGL((k_head_argmax<PAM_J, false>), dim3(n * tiles), dim3(HEAD_T), lds, (hipStream_t)stream, HW, tiles, f, C, w, bias,
+                           dev_heatmaps_or_null, (Best*)dev_scratch, hm_w, 0.0f, (Soft*)nullptr);
+        hipLaunchKernelGGL((k_dark_finish<false>), dim3(n * J_), dim3(DARK_T), 0, (hipStream_t)stream, tiles, (const Best*)dev_scratch, hm_h, hm_w,
+                           f, C, w, bias, 0, 0, R, taps, dev_view_of, dev_slot_of, dev_boxes, max_dets, dev_det, dev_kp_xyc);
+    }
+    return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+}
+
 extern "C" int pam_preprocess_crops_ex(void* stream, int n, int n_total, const void* const* dev_frames, int frame_h, int frame_w,
                                        const int32_t* dev_view_of, const float* dev_boxes, int out_h, int out_w,
                                        int out_c, void* dev_out_bf16, int antialias) {

@@ -296,10 +296,11 @@ class HRNetPose(object):
     def __init__(self, c, nof_joints, checkpoint_path, model_name='HRNet', resolution=(384, 288), hrpose_args=None,
                  device=0, dtype=torch.bfloat16, use_graph=True, seed=0, max_dets=16, backend='hip', graph_bucket=4,
                  shard_crops=False, group=None, autotune=False, max_crops=32, antialias=False, flip_test=False, shift_heatmap=True,
-                 post_process=False, soft_beta=None):
+                 post_process=False, soft_beta=None, dark=False, blur_kernel=None):
         from . import poseresnet
         # the decode options first: a refused combination raises before anything touches a device
         self.soft_beta, self.flip_test, self.shift_heatmap, self.post_process = soft_beta, flip_test, shift_heatmap, post_process
+        self.dark, self.blur_kernel = dark, blur_kernel
         if model_name in poseresnet.MODEL_NAMES:
             # simple-HRNet's second family: c is the ResNet depth (Bottleneck ResNets only; 18 / 34 are BasicBlock networks)
             if int(c) != c or int(c) not in poseresnet.DEPTHS:
@@ -722,8 +723,13 @@ class HRNetPose(object):
     #                  the average of the plain map and the mirrored-back, left/right-swapped map (pam_head_decode_flip).
     #   shift_heatmap  (TEST.SHIFT_HEATMAP; matters under flip_test only) the mirrored-back map moves one column to the right first.
     #   post_process   (TEST.POST_PROCESS) the arg-max moves a quarter of a cell towards the higher neighbour along each axis.
-    # soft_beta with flip_test or post_process is refused (ValueError): the soft-arg-max has no merged-map form.
-    _soft_beta, _flip_test, _post_process, shift_heatmap = None, False, False, True
+    #   dark           the DARK decode (Zhang et al., CVPR 2020; pam_head_decode_dark): the arg-max of the (merged) map moves by one Newton
+    #                  step of the Gaussian-blurred map's logarithm.  Settable before or after capture: the forward keeps its size.
+    #   blur_kernel    DARK's blur size, odd, 9 .. 17.  None: 17 for maps of 96 rows or more, otherwise 11 (the published DARK configs'
+    #                  values for 384 x 288 and 256 x 192).
+    # soft_beta with flip_test or post_process is refused (ValueError): the soft-arg-max has no merged-map form.  dark with post_process
+    # or soft_beta is refused alike: each of the three is a sub-cell decode of its own.
+    _soft_beta, _flip_test, _post_process, _dark, _blur_kernel, shift_heatmap = None, False, False, False, None, True
 
     def _decode_option(name):
         def get(self):
@@ -731,8 +737,11 @@ class HRNetPose(object):
 
         def put(self, value):
             value = (None if value is None else float(value)) if name == 'soft_beta' else bool(value)
-            now = dict(soft_beta=self._soft_beta, flip_test=self._flip_test, post_process=self._post_process)
+            now = dict(soft_beta=self._soft_beta, flip_test=self._flip_test, post_process=self._post_process, dark=self._dark)
             now[name] = value
+            if now['dark'] and (now['post_process'] or now['soft_beta'] is not None):
+                raise ValueError('HRNetPose: dark cannot be combined with post_process or soft_beta (got dark=%r, post_process=%r, '
+                                 'soft_beta=%r)' % (now['dark'], now['post_process'], now['soft_beta']))
             if now['soft_beta'] is not None and (now['flip_test'] or now['post_process']):
                 raise ValueError('HRNetPose: soft_beta cannot be combined with flip_test or post_process (got soft_beta=%r, flip_test=%r, '
                                  'post_process=%r)' % (now['soft_beta'], now['flip_test'], now['post_process']))
@@ -741,7 +750,22 @@ class HRNetPose(object):
             setattr(self, '_' + name, value)
         return property(get, put)
     soft_beta, flip_test, post_process = _decode_option('soft_beta'), _decode_option('flip_test'), _decode_option('post_process')
+    dark = _decode_option('dark')
     del _decode_option
+
+    @property
+    def blur_kernel(self):
+        return self._blur_kernel
+
+    @blur_kernel.setter
+    def blur_kernel(self, value):
+        if value is not None and (int(value) != value or int(value) % 2 == 0 or not 9 <= int(value) <= 17):
+            raise ValueError('HRNetPose: blur_kernel must be None or odd with 9 <= blur_kernel <= 17 (got %r)' % (value,))
+        self._blur_kernel = None if value is None else int(value)
+
+    def dark_blur_kernel(self, hm_h):
+        """The blur size the DARK decode uses on a heat-map of hm_h rows: ``blur_kernel``, or by default 17 from 96 rows on, else 11."""
+        return self._blur_kernel if self._blur_kernel is not None else (17 if hm_h >= 96 else 11)
 
     def decode_flags(self):
         """The flag word of pam_head_decode_flip for this object's options (0: the plain decode)."""
@@ -752,7 +776,8 @@ class HRNetPose(object):
         (N,c,h,w channels-last bf16): det rows as ``decode``; the heat-maps are written only when ``heat`` (N,17,h,w float32
         channels-last) is given.  n: decode only the first n crops of f.  Under the flip test f is the feature batch of a forward that
         ``preprocess`` filled (n plain crops, then their n mirrors: n defaults to half of f) and the decode runs on the merged maps; with
-        ``post_process`` the arg-max carries the quarter-cell offset.  With every option off the launches are pam_head_decode's."""
+        ``post_process`` the arg-max carries the quarter-cell offset; with ``dark`` the DARK offset (pam_head_decode_dark, on the merged
+        map under the flip test).  With every option off the launches are pam_head_decode's."""
         nf, c, h, w = f.shape
         flags = self.decode_flags()
         n = (nf // 2 if flags & 1 else nf) if n is None else n
@@ -770,12 +795,14 @@ class HRNetPose(object):
                 C.c_void_p(self._hd_scratch.data_ptr()))
         if soft:
             rc = self.lib.pam_head_decode_soft(*(head + (C.c_float(float(self.soft_beta)),) + tail))
+        elif self.dark:                                   # (same scratch size as well: pam_head_decode_dark_scratch_bytes)
+            rc = self.lib.pam_head_decode_dark(*(head[:2] + (n,) + head[2:] + (flags & 3, self.dark_blur_kernel(h)) + tail))
         elif flags:                                       # (same scratch size as the plain decode: pam_head_decode_flip_scratch_bytes)
             rc = self.lib.pam_head_decode_flip(*(head[:2] + (n,) + head[2:] + (flags,) + tail))
         else:
             rc = self.lib.pam_head_decode(*(head + tail))
         if rc != 0:
-            raise _lib.PamError('pam_head_decode%s failed: %d' % ('_soft' if soft else ('_flip' if flags else ''), rc))
+            raise _lib.PamError('pam_head_decode%s failed: %d' % ('_soft' if soft else ('_dark' if self.dark else ('_flip' if flags else '')), rc))
 
     # -- the reference-shaped entry point ------------------------------------------------------------------------------
     def predict(self, person_bbox_list, batch_size=20, conf_threshold=0.4):

@@ -134,6 +134,11 @@ class ivclabpose(object):
             if opt('SHIFT_HEATMAP') is not None:
                 self.pose_model.shift_heatmap = bool(opt('SHIFT_HEATMAP'))
             self.pose_model.post_process = bool(opt('POST_PROCESS'))
+            # optional keys DARK / BLUR_KERNEL: the DARK decode (Zhang et al., CVPR 2020), the test protocol of the DARK-trained checkpoints;
+            # BLUR_KERNEL absent: 17 for maps of 96 rows or more, otherwise 11
+            if opt('BLUR_KERNEL') is not None:
+                self.pose_model.blur_kernel = int(opt('BLUR_KERNEL'))
+            self.pose_model.dark = bool(opt('DARK'))
             self.pose_model.flip_test = bool(opt('FLIP_TEST'))
             print("Pose Detector : ", _cfg(self.pose_detector, 'NAME'))
         if self.person_matcher is None:

@@ -35,7 +35,7 @@ class FramePipeline(object):
     def __init__(self, calib_cameras, matcher, conf_threshold, frame_hw, max_dets=8, max_tracks=16, device=0, world=1,
                  rank=0, group=None, use_graph=True, hrnet=True, seed=0, shard='views', overlap_tracker=False, net=None, exchange='torch',
                  pose_streams=1, autotune=True, prewarm=False, width=48, resolution=(384, 288), flip_test=False, shift_heatmap=True,
-                 post_process=False, model_name='HRNet', crop_cap=None, detect_every=1):
+                 post_process=False, model_name='HRNet', crop_cap=None, detect_every=1, dark=False, blur_kernel=None):
         """shard: 'views' -- rank owns whole camera views (pose_step / track_step take view-local inputs); 'crops' -- the
         frame's crops are dealt out evenly over the ranks (pose_step_crops / track_step_crops take global view indices).
         overlap_tracker (either mode): exchange + tracker kernel + fetch of frame t run on their own stream, under the conv
@@ -52,6 +52,7 @@ class FramePipeline(object):
         model_name='PoseResNet' with width = the ResNet depth, as HRNetPose takes it).
         flip_test / shift_heatmap / post_process: that network's decode options (HRNetPose: the official test protocol; the flip test
         doubles every forward, prewarm captures the doubled counts).  A shared `net` keeps its own settings.
+        dark / blur_kernel: that network's DARK decode (HRNetPose; the forwards keep their size).
         crop_cap: rows of the device-built crop table (pose_step_boxes): crop, forward and decode of such a frame run for this many rows
         whatever the boxes' count.  None = this rank's views x max_dets; under prewarm rounded up to the network's bucket.
         detect_every: the schedule of pose_step_auto (box_source): the detector on every detect_every-th frame since the last reset(),
@@ -72,7 +73,8 @@ class FramePipeline(object):
                                                           use_graph=use_graph, seed=seed,
                                                           max_dets=max_dets, autotune=autotune,
                                                           max_crops=len(calib_cameras) * max_dets, flip_test=flip_test,
-                                                          shift_heatmap=shift_heatmap, post_process=post_process) if hrnet else None)
+                                                          shift_heatmap=shift_heatmap, post_process=post_process, dark=dark,
+                                                          blur_kernel=blur_kernel) if hrnet else None)
         self.shard = shard
         # exchange: 'torch' = torch.distributed (RCCL when the backend is nccl, gloo in the CPU tests); 'abi' = pam_allgather_keypoints,
         # the library's own RCCL call on the decode stream (view sharding only)
