@@ -370,6 +370,12 @@ int pam_conv_last_kernel(void);
  *   PAM_CONV_KERNEL_STEM   S*100 + Cout                   stride 1 / 2, 32 or 64 output channels
  * Kernel and form are recorded together, by the launcher, from the launched kernel's own template parameters. */
 int pam_conv_last_form(void);
+/* Which kernel and form (the two codes above) pam_conv2d_nhwc_bf16_ex would launch for these integer arguments and pointers (has_* = 1
+ * where the call passes a non-NULL in / w_packed / w_img / residual / out): the library's own choice, asked without launching.  Returns
+ * what the call would return before it launches: PAM_OK with *kernel and *form written, or PAM_E_ARG (a refused call, or a NULL output)
+ * with both left alone.  Pure integer arithmetic: touches no device and works on a machine without a GPU. */
+int pam_conv_plan(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu, int tile_cfg, int in_cstride,
+                  int relu_from, int has_in, int has_w_packed, int has_w_img, int has_residual, int has_out, int32_t* kernel, int32_t* form);
 /* diagnostic builds only: device buffer (64 x uint64 per workgroup) for k_conv3x3's s_memtime stamps, used when tile_cfg = 100 + 64 */
 int pam_conv_debug_stamps(void* dev_buf);
 int pam_upsample_add_nhwc_bf16(void* stream, const void* base, int n_terms, const void* const* terms,

@@ -73,6 +73,7 @@ _SIGS = {
     'pam_conv3x3_layout': (_I, [_I, _I, _I, _I]),
     'pam_conv_last_kernel': (_I, []),
     'pam_conv_last_form': (_I, []),
+    'pam_conv_plan': (_I, [_I] * 18 + [_P, _P]),
     'pam_conv3x3_layout_ex': (_I, [_I, _I, _I, _I, _I]),
     'pam_conv3x3_layout_gen': (_I, [_I, _I, _I, _I]),
     'pam_conv3x3_layout_small': (_I, [_I, _I, _I, _I]),

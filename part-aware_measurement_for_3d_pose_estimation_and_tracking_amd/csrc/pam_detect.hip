@@ -1,7 +1,7 @@
 // libpam_hip.so, person-detector side: what `backend.YOLOv3` does around its conv stack for
 // ivclabpose.PersonDetect (/root/reference/src/ivclabpose.py:116-120,183-204; the backend itself is not in the reference
 // tree, so these follow the public Darknet YOLOv3 definition -- parity unpinned).  The Darknet-53 convolutions run on
-// pam_conv.hip; the kernels here are the HBM-bound streaming pieces: frame resize, route(upsample, skip), YOLOv3-tiny's
+// the kernels behind pam_conv.hip (pam_conv_*.hip); the kernels here are the HBM-bound streaming pieces: frame resize, route(upsample, skip), YOLOv3-tiny's
 // max-pool, YOLOv3-SPP's pooling block and the box decode + greedy NMS over one to three scales.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -257,7 +257,7 @@ bool d48_pick(int N, int Ho, int Wo, int nslab, int& TR, int& TC, int& G) {
 
 
 // ====================================================================================================================================
-// k_down_s (Cin = 96 / 192: the other 12 strided layers): the streamed 3x3 kernel of csrc/pam_conv.hip (k_conv3x3s: loader waves 4-7 move
+// k_down_s (Cin = 96 / 192: the other 12 strided layers): the streamed 3x3 kernel of csrc/pam_conv3x3s.hip (k_conv3x3s: loader waves 4-7 move
 // 32-channel chunks -- patch rows + the chunk's [9 taps][BN rows] weight image -- by LDS-DMA into a ring of chunk buffers, multiplier
 // waves 0-3 read fragments and multiply) with a STRIDE-2 patch: tile = TH output rows x the full output width, patch = (2 TH + 1) rows of
 // PWp = 2 Wo + 2 slots of 64 B, the columns of a row stored by parity (even patch columns in slots 0 .. Wo, odd ones in Wo + 1 .. 2 Wo), so

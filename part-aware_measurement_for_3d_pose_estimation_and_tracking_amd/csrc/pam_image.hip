@@ -1,5 +1,5 @@
 // libpam_hip.so, image part of a1 (HRNetPose.predict pre/post-processing; call site /root/reference/src/ivclabpose.py:210).
-// Crop / resize / normalise in front of the conv stack (csrc/pam_conv.hip, csrc/pam_block.hip), the network's final 1x1
+// Crop / resize / normalise in front of the conv stack (csrc/pam_conv.hip and its pam_conv_*.hip kernel families, csrc/pam_block.hip), the network's final 1x1
 // convolution and the arg-max decode behind it.  All HBM-bound streaming kernels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>

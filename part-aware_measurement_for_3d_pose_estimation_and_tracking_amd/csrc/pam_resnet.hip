@@ -1,6 +1,6 @@
 // PoseResNet's own layers (poseresnet.py, hrnet_hip.HipPoseResNet): the stem -- 7x7 stride-2 convolution + bias + ReLU + 3x3 stride-2
 // max-pool in one launch -- and the 4x4 stride-2 transposed convolutions of the deconvolution head.  The backbone's other layers
-// are the shared conv stack's (pam_conv.hip, pam_pw.hip, pam_bneck.hip).
+// are the shared conv stack's (pam_conv.hip and its pam_conv_*.hip kernel families, pam_pw.hip, pam_bneck.hip).
 //
 // k_resnet_stem: one workgroup per pooled output row (n, py).  Pooled row py reads conv rows 2 py - 1 .. 2 py + 1 (one halo row shared with
 // each neighbour, recomputed): they are computed into LDS as bf16 after bias + ReLU ([3 rows][Wc][64]), then pooled.  The H/2 map never

@@ -10,7 +10,7 @@ convolutions, 6 max-pools, two heads; ``arch='yolov3-spp'``: YOLOv3-SPP, Darknet
 in front of the first head, 76 convolutions), with no weights a seeded random one.
 
 Two executions of the same network: ``Darknet`` (plain PyTorch float32; the test reference) and ``HipDarknet`` (product
-path: every convolution on the MFMA kernels of csrc/pam_conv.hip with BN folded, leaky-ReLU and the shortcut add fused into
+path: every convolution on the MFMA kernels of csrc/pam_conv_*.hip (chosen by csrc/pam_conv_plan.hpp) with BN folded, leaky-ReLU and the shortcut add fused into
 the epilogue; resize, upsample+route, max-pool, the SPP block (its three pools and their route: one launch) and box decode + NMS in
 csrc/pam_detect.hip; one hipGraph per batch shape)."""
 import ctypes as C

@@ -66,6 +66,25 @@ def test_conv_form_query_is_bound_and_documented():
         assert fn() == 0, name
 
 
+def test_conv_plan_query_is_bound_and_rejects_a_null_output():
+    """pam_conv_plan (which kernel and form pam_conv2d_nhwc_bf16_ex would launch) is declared, bound with 18 integers and two output
+    pointers, and answers without touching a device: PAM_E_ARG with the outputs left alone when one is missing or the call would be
+    refused, else the codes pam_conv_last_kernel / pam_conv_last_form document."""
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    assert _lib._SIGS['pam_conv_plan'] == (ctypes.c_int, [ctypes.c_int] * 18 + [ctypes.c_void_p] * 2)
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    fn = lib.pam_conv_plan
+    fn.restype, fn.argtypes = _lib._SIGS['pam_conv_plan']
+    k, f = ctypes.c_int32(-7), ctypes.c_int32(-7)
+    layer = [2, 24, 18, 192, 192, 3, 3, 1, 1, 1, -3, 192, 0, 1, 1, 1, 0, 1]      # a streamed 3x3 layer of HRNet-W48's third branch
+    assert fn(*layer, None, ctypes.byref(f)) == -1 and fn(*layer, ctypes.byref(k), None) == -1
+    assert fn(*(layer[:13] + [0] + layer[14:]), ctypes.byref(k), ctypes.byref(f)) == -1          # no input pointer: the call is refused
+    assert (k.value, f.value) == (-7, -7)
+    assert fn(*layer, ctypes.byref(k), ctypes.byref(f)) == 0 and (k.value, f.value) == (2, 19244)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(_lib, '_lib', None)
     monkeypatch.setattr(_lib, 'LIB_PATH', '/nonexistent/libpam_hip.so')

@@ -1,4 +1,4 @@
-"""GPU: the hand-written MFMA convolution (csrc/pam_conv.hip) against a plain PyTorch fp32 reference of the same op on the
+"""GPU: the hand-written MFMA convolutions (csrc/pam_conv.hip and its pam_conv_*.hip kernel families) against a plain PyTorch fp32 reference of the same op on the
 same bf16-rounded inputs, over every (Cin, Cout, kernel, stride, tile) family HRNet-W48 uses, incl. ragged M / K tails."""
 import ctypes as C
 

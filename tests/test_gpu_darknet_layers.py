@@ -112,7 +112,7 @@ def form_name(kind, form):
     raise AssertionError('unknown conv kernel %d (form %d)' % (kind, form))
 
 
-# Forms the detector's dispatch can select (from csrc/pam_conv.hip and ConvEngine.conv), each of which the cases above must reach:
+# Forms the detector's dispatch can select (from csrc/pam_conv_plan.hpp and ConvEngine.conv), each of which the cases above must reach:
 REQUIRED = {
     'k_conv_stem s1 Cout=32',                                                  # layer 0
     'k_conv_gs tile=64 slab=64 nbuf=3', 'k_conv_gs tile=128 slab=64 nbuf=3',   # leaky 1x1 / stride-2 / unfused 3x3 layers: the pixel tile

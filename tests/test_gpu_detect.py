@@ -1,4 +1,4 @@
-"""GPU: the person-detector side (csrc/pam_detect.hip + the Darknet activation codes of csrc/pam_conv.hip) through the C ABI,
+"""GPU: the person-detector side (csrc/pam_detect.hip + the Darknet activation codes of the csrc/pam_conv_*.hip kernels) through the C ABI,
 against oracle/yolo_ref.py (NumPy) for the streaming kernels and a plain PyTorch fp32 Darknet for the conv stack."""
 import ctypes as C
 

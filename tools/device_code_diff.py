@@ -5,6 +5,8 @@ Each directory holds the `.s` files of `hipcc $(CXXFLAGS) --cuda-device-only -S 
 with -DPAM_DIAG for the diagnostic build).  Per kernel the body (symbol to .Lfunc_end), the .amdhsa_kernel descriptor and the
 kernel's .amdgpu_metadata entry must be equal after three normalisations: assembler comments dropped, the random __hip_cuid_* symbol, and local labels
 (.LBB / .Lfunc_end / .Ltmp), renumbered in order of appearance because their function index moves with definition order.
+Kernels are pooled by symbol over all files of a directory, so a kernel that moved to another source file is still compared; the
+report names the file(s) it sits in.
 usage: device_code_diff.py OLD_DIR NEW_DIR      exit status 1 when a kernel differs or exists on one side only
 """
 import pathlib
@@ -42,19 +44,29 @@ def kernels(path):
     return out
 
 
+def pool(directory):
+    """symbol -> (file name, [body, descriptor, metadata]) over every .s file of the directory; a symbol defined in two files is an error."""
+    out = {}
+    for path in sorted(pathlib.Path(directory).glob("*.s")):
+        for k, parts in kernels(path).items():
+            if k in out:
+                sys.exit("%s: %s is defined in %s and %s" % (directory, k, out[k][0], path.name))
+            out[k] = (path.name, parts)
+    return out
+
+
 def main(old_dir, new_dir):
-    total = bad = 0
-    for old in sorted(pathlib.Path(old_dir).glob("*.s")):
-        a, b = kernels(old), kernels(pathlib.Path(new_dir) / old.name)
-        for k in sorted(a.keys() | b.keys()):
-            total += 1
-            if k not in a or k not in b:
-                bad += 1
-                print("%s: %s only in %s" % (old.name, k, "old" if k in a else "new"))
-            elif a[k] != b[k]:
-                bad += 1
-                print("%s: %s differs (%s)" % (old.name, k, ", ".join(p for p, x, y in zip(("body", "descriptor", "metadata"), a[k], b[k]) if x != y)))
-    print("%d kernels compared, %d differ" % (total, bad))
+    a, b = pool(old_dir), pool(new_dir)
+    bad = 0
+    for k in sorted(a.keys() | b.keys()):
+        where = " / ".join(sorted({d[k][0] for d in (a, b) if k in d}))
+        if k not in a or k not in b:
+            bad += 1
+            print("%s: %s only in %s" % (where, k, "old" if k in a else "new"))
+        elif a[k][1] != b[k][1]:
+            bad += 1
+            print("%s: %s differs (%s)" % (where, k, ", ".join(p for p, x, y in zip(("body", "descriptor", "metadata"), a[k][1], b[k][1]) if x != y)))
+    print("%d kernels in old, %d in new, %d compared, %d differ" % (len(a), len(b), len(a.keys() | b.keys()), bad))
     return 1 if bad else 0
 
 
