@@ -165,6 +165,36 @@ int pam_crop_table(void* stream, int n_views, const int32_t* dev_views, const fl
                    int max_det_in, int frame_w, int frame_h, int max_dets, int cap, int32_t* dev_view_of, int32_t* dev_slot_of,
                    float* dev_xywh, int32_t* dev_n_det, int32_t* dev_info);
 
+/* ---- duplicate 2D poses out of each view (csrc/pam_pose_nms.hip; no handle, asynchronous on `stream`; no reference counterpart: the
+ * rescoring + greedy OKS-NMS of the HRNet / Simple Baselines test protocol, TEST.OKS_THRE / TEST.IN_VIS_THRE) ------------------------
+ * pam_pose_nms filters the decode's buffer in place, one workgroup per view, all in float64.  View v < n_views holds
+ * n = clamp(dev_n_det_in[v], 0, max_dets) rows (y, x, s)[17] at dev_det + v * det_slots * 51 (det_slots >= max_dets: max_dets for
+ * HRNetPose.predict's buffer, max_dets + 1 for ViewGather's view records).  The crop rows that produced the buffer (n_rows of
+ * dev_view_of / dev_slot_of / dev_xywh, the tables pam_preprocess_crops* took; rows that repeat a (view, slot) carry the same box) give
+ * each row its area = (double)w * (double)h (0 for a slot no crop row names).  Box score b of (v, slot) = dev_score[g * view_stride +
+ * slot * slot_stride] with g = dev_views ? dev_views[v] : v (strides in floats: a detector-layout list (G, max_det, 5) is read in place
+ * as dev_boxes + 4 with strides (5 * max_det, 5)); dev_score = NULL means 1.0.
+ *   score   = (double)b * mean{ s_j : s_j > in_vis_thre }   (summed over j = 0..16 in order; 0.0 when no joint passes)
+ *   oks(p,q) = (1/17) sum_j exp(-e_j),  e_j = ((dx_j)^2 + (dy_j)^2) / vars[j] / ((area_p + area_q) / 2 + 2.220446049250313e-16) / 2
+ *             (all 17 joints always count; vars: 17 host doubles, (2 sigma_j)^2, copied into the launch)
+ *   order   = descending score, equal scores by lower slot (a NaN score goes last)
+ *   greedy  = the first row of the order that is alive is kept and kills every alive row q with oks(kept, q) > oks_thre (a NaN OKS
+ *             kills nothing; NOT transitive: what a killed row would have killed stays unless a kept row kills it); repeat.
+ * Output: the kept rows in their original slot order, compacted to slots 0 .. kept - 1 (a view without duplicates is left bit-identical),
+ * rows [kept, n) set to 0.0, rows >= n untouched; dev_n_det_out[v] = kept; dev_keep_from[v * max_dets + slot] = the original slot of the
+ * row now at `slot` (-1 from kept on); dev_pose_score[v * max_dets + slot] = its score (0.0 from kept on).  dev_n_det_out must not be
+ * dev_n_det_in: a forward that is issued again decodes and filters again from the original counts.
+ * Counts and crop rows are clamped or skipped (no row index leaves its view).  The score grid is the caller's to guarantee, as the box list
+ * of pam_crop_table is: dev_views[v] and every (g, slot < max_dets) address must lie inside dev_score -- the kernel cannot know its extent.
+ * The library is built with -ffp-contract=off, so e_j is computed as written (no fused multiply-add); exp is the device library's and may
+ * differ from another implementation's in the last bits.
+ * PAM_E_ARG, before any device call: a NULL pointer (dev_score and dev_views excepted), n_views < 1, max_dets outside 1..32,
+ * det_slots < max_dets, n_rows < 0, dev_n_det_out == dev_n_det_in. */
+int pam_pose_nms(void* stream, int n_views, int max_dets, int det_slots, double* dev_det, const int32_t* dev_n_det_in, int n_rows,
+                 const int32_t* dev_view_of, const int32_t* dev_slot_of, const float* dev_xywh, const float* dev_score,
+                 long long view_stride, long long slot_stride, const int32_t* dev_views, const double* vars, double oks_thre,
+                 double in_vis_thre, int32_t* dev_n_det_out, int32_t* dev_keep_from, double* dev_pose_score);
+
 /* ---- per-operator entry points (parity tests; host buffers, synchronous) -----------------------------------*/
 /* Camera.projectPoints_parallel, ivclabpose.py:91-98: n poses (17x3) -> (17x2) in (y, x) */
 int pam_op_project(PamHandle* h, int cid, int n, const double* poses3d, double* out_yx);

@@ -100,6 +100,7 @@ _SIGS = {
     'pam_set_input_guard': (_I, [_P, _P]),
     'pam_track_boxes': (_I, [_P, _P, _I, _I, _I, _I, C.c_float, C.c_float, C.c_float, _I, _I, _P, _P, _P, _P]),
     'pam_crop_table': (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'pam_pose_nms': (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, C.c_longlong, C.c_longlong, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
     'pam_comm_unique_id': (_I, [_P]),
     'pam_comm_init': (_I, [C.POINTER(_P), _I, _I, _P, _I]),
     'pam_comm_destroy': (_I, [_P]),
@@ -134,6 +135,11 @@ SPP_MAX_HW = 32             # PAM_SPP_MAX_HW in include/pam.h
 # measurement needed, the reference's 2D age filter (time_interval <= 3)
 TRACK_BOX_RULE = dict(grow=1.25, pad_px=8.0, min_size_px=8.0, max_gap=3)
 CROP_CUT_VIEW, CROP_CUT_CAP = 1, 2         # pam_crop_table's info[2]
+POSE_NMS_MAX = 32                          # rows per view pam_pose_nms takes (one bit each)
+# pam_pose_nms' per-joint constants: (2 sigma_j)^2 of the COCO keypoint sigmas, by the expression of the official oks_nms (the kernel
+# gets these 17 doubles, whatever produced them: a caller with other joints passes its own)
+COCO_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
+OKS_VARS = (COCO_SIGMAS * 2) ** 2
 
 _lib = None
 
@@ -484,3 +490,31 @@ def crop_table(stream, boxes, count, frame_w, frame_h, max_dets, view_of, slot_o
                                C.c_void_p(xywh.data_ptr()), C.c_void_p(n_det.data_ptr()), C.c_void_p(info.data_ptr()))
     if rc != 0:
         raise PamError('pam_crop_table failed (%d)' % rc)
+
+
+def pose_nms(stream, det, n_det_in, view_of, slot_of, xywh, n_det_out, keep_from, pose_score, max_dets=None, score=None,
+             score_strides=(0, 0), views=None, oks_thre=0.9, in_vis_thre=0.2, oks_vars=None):
+    """Rescoring + greedy OKS-NMS of every view's decoded poses, in place (pam_pose_nms; the rule: include/pam.h).  det (V, det_slots,
+    17, 3) float64 rows (y, x, score), the first max_dets (None: det_slots; at most 32) rows of a view are its slots; n_det_in (V,) int32;
+    view_of / slot_of (n_rows,) int32 and xywh (n_rows, 4) float32: the crop rows that produced det; score: float32 device tensor or
+    data pointer of the box scores, read at [g * score_strides[0] + slot * score_strides[1]] with g = views[v] (views: int32 device
+    tensor) or v -- None = 1.0; oks_vars: 17 doubles (None: OKS_VARS).  Written: n_det_out (V,) int32 (not n_det_in), keep_from (V,
+    max_dets) int32, pose_score (V, max_dets) float64.  All contiguous device tensors; asynchronous on ``stream``."""
+    V, det_slots = int(det.shape[0]), int(det.shape[1])
+    max_dets = det_slots if max_dets is None else int(max_dets)
+    if max_dets > POSE_NMS_MAX:
+        raise ValueError('pose_nms: %d slots per view, at most %d' % (max_dets, POSE_NMS_MAX))
+    n_rows = int(view_of.numel())
+    assert det.is_contiguous() and tuple(det.shape[2:]) == (PAM_J, 3) and n_det_in.numel() >= V and n_det_out.numel() >= V
+    assert slot_of.numel() == n_rows and xywh.numel() == 4 * n_rows and keep_from.numel() >= V * max_dets and pose_score.numel() >= V * max_dets
+    assert views is None or views.numel() >= V
+    vs = np.ascontiguousarray(OKS_VARS if oks_vars is None else oks_vars, dtype=np.float64)
+    assert vs.shape == (PAM_J,)
+    sp = None if score is None else C.c_void_p(score if isinstance(score, int) else score.data_ptr())
+    rc = load().pam_pose_nms(C.c_void_p(stream), V, max_dets, det_slots, C.c_void_p(det.data_ptr()), C.c_void_p(n_det_in.data_ptr()), n_rows,
+                             C.c_void_p(view_of.data_ptr()), C.c_void_p(slot_of.data_ptr()), C.c_void_p(xywh.data_ptr()), sp,
+                             int(score_strides[0]), int(score_strides[1]), C.c_void_p(views.data_ptr()) if views is not None else None,
+                             _ptr(vs), float(oks_thre), float(in_vis_thre), C.c_void_p(n_det_out.data_ptr()),
+                             C.c_void_p(keep_from.data_ptr()), C.c_void_p(pose_score.data_ptr()))
+    if rc != 0:
+        raise PamError('pam_pose_nms failed (%d)' % rc)

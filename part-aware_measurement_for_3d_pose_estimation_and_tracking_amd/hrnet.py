@@ -296,11 +296,12 @@ class HRNetPose(object):
     def __init__(self, c, nof_joints, checkpoint_path, model_name='HRNet', resolution=(384, 288), hrpose_args=None,
                  device=0, dtype=torch.bfloat16, use_graph=True, seed=0, max_dets=16, backend='hip', graph_bucket=4,
                  shard_crops=False, group=None, autotune=False, max_crops=32, antialias=False, flip_test=False, shift_heatmap=True,
-                 post_process=False, soft_beta=None, dark=False, blur_kernel=None):
+                 post_process=False, soft_beta=None, dark=False, blur_kernel=None, pose_nms=False, oks_thre=0.9, in_vis_thre=0.2):
         from . import poseresnet
         # the decode options first: a refused combination raises before anything touches a device
         self.soft_beta, self.flip_test, self.shift_heatmap, self.post_process = soft_beta, flip_test, shift_heatmap, post_process
         self.dark, self.blur_kernel = dark, blur_kernel
+        self.pose_nms, self.oks_thre, self.in_vis_thre = bool(pose_nms), float(oks_thre), float(in_vis_thre)
         if model_name in poseresnet.MODEL_NAMES:
             # simple-HRNet's second family: c is the ResNet depth (Bottleneck ResNets only; 18 / 34 are BasicBlock networks)
             if int(c) != c or int(c) not in poseresnet.DEPTHS:
@@ -729,7 +730,12 @@ class HRNetPose(object):
     #                  values for 384 x 288 and 256 x 192).
     # soft_beta with flip_test or post_process is refused (ValueError): the soft-arg-max has no merged-map form.  dark with post_process
     # or soft_beta is refused alike: each of the three is a sub-cell decode of its own.
+    #   pose_nms       the protocol's last step (TEST.OKS_THRE / TEST.IN_VIS_THRE): behind the decode every pose is rescored (box score x
+    #                  mean of its joint scores above in_vis_thre) and each view's duplicates are removed by greedy OKS-NMS at oks_thre, on
+    #                  the device (pam_pose_nms; the rule: include/pam.h).  Plain attributes, settable at any time; composes with every
+    #                  decode above (it runs after whichever ran).  Off: predict() issues exactly the launches it issued without it.
     _soft_beta, _flip_test, _post_process, _dark, _blur_kernel, shift_heatmap = None, False, False, False, None, True
+    pose_nms, oks_thre, in_vis_thre = False, 0.9, 0.2
 
     def _decode_option(name):
         def get(self):
@@ -816,10 +822,12 @@ class HRNetPose(object):
         V = len(person_bbox_list)
         if not self._arenas:
             self.max_crops = max(self.max_crops, int(batch_size))
-        views, slots, boxes, frames, cnt = [], [], [], {}, [0] * V
+        views, slots, boxes, frames, cnt, bscore = [], [], [], {}, [0] * V, []
         for v, persons in enumerate(person_bbox_list):
             for p in persons:
                 views.append(v); slots.append(cnt[v]); cnt[v] += 1; boxes.append(list(p['bbox']))     # copied: the dump is built lazily
+                sc = p.get('score')
+                bscore.append(1.0 if sc is None else float(sc))       # (absent or None: 1.0)
                 if v not in frames:
                     d = p['data']
                     if not torch.is_tensor(d):
@@ -832,12 +840,21 @@ class HRNetPose(object):
         any_frame = next(iter(frames.values()))
         fh, fw = any_frame.shape[0], any_frame.shape[1]
         # one upload for all the small per-call tables: [view_of n | slot_of n | boxes 4n (f32 bits) | n_det V | frame ptrs V (i64)]
-        meta = np.empty(6 * n + V + (V & 1) + 2 * V, dtype=np.int32)
+        S = max(self.max_dets, max(cnt))                   # slots per view of this call's buffer
+        nms = bool(self.pose_nms)
+        if nms and S > _lib.POSE_NMS_MAX:
+            raise ValueError('HRNetPose.predict: pose_nms takes at most %d persons per view (got a buffer of %d slots)' % (_lib.POSE_NMS_MAX, S))
+        # (pose_nms: the box scores travel in the same upload, as a (V, S) float32 table behind the frame pointers)
+        meta = np.empty(6 * n + V + (V & 1) + 2 * V + (V * S if nms else 0), dtype=np.int32)
         meta[:n] = views; meta[n:2 * n] = slots
         meta[2 * n:6 * n].view(np.float32)[:] = np.asarray(boxes, dtype=np.float32).reshape(-1)
         meta[6 * n:6 * n + V] = cnt
         o_ptr = 6 * n + V + (V & 1)
-        meta[o_ptr:].view(np.int64)[:] = [frames[v].data_ptr() if v in frames else 0 for v in range(V)]
+        meta[o_ptr:o_ptr + 2 * V].view(np.int64)[:] = [frames[v].data_ptr() if v in frames else 0 for v in range(V)]
+        if nms:
+            tab = np.ones((V, S), dtype=np.float32)
+            tab[views, slots] = bscore
+            meta[o_ptr + 2 * V:].view(np.float32)[:] = tab.reshape(-1)
         # staged through a pinned buffer of its own (two per size, alternating): the upload is asynchronous and the host goes on issuing
         # (each buffer carries the event recorded behind its last upload: a host that runs more than two calls ahead of the GPU -- device
         # frames, dumps dropped unread -- must not overwrite a table whose copy has not been issued to the device yet)
@@ -854,8 +871,8 @@ class HRNetPose(object):
         view_of, slot_of = m[:n], m[n:2 * n]
         bx = m[2 * n:6 * n].view(torch.float32).reshape(n, 4)
         n_det = m[6 * n:6 * n + V]
-        ptrs = m[o_ptr:].view(torch.int64)
-        det = torch.empty((V, max(self.max_dets, max(cnt)), 17, 3), dtype=torch.float64, device=self.device)
+        ptrs = m[o_ptr:o_ptr + 2 * V].view(torch.int64)
+        det = torch.empty((V, S, 17, 3), dtype=torch.float64, device=self.device)
         kp = torch.empty((n, 17, 3), dtype=torch.float32, device=self.device)
         lo, hi = 0, n
         if self.world > 1:                                # this rank's share of the call's crops (ordered by view, then person)
@@ -864,6 +881,16 @@ class HRNetPose(object):
                 check_same_call(n, V, self.device, self.group)
             lo, hi = crop_partition(n, self.world)[self.rank]
         host = self._pinned_kp(n)
+        nms_dev = nms_host = None
+        if nms:
+            # the filter's outputs: [n_det_out V | keep_from V * S] int32 and pose_score (V, S) float64, with pinned host copies that
+            # travel behind the keypoints' copy (they share its ring entry: a dump still pending on them is materialised first)
+            nms_dev = (torch.empty(V + V * S, dtype=torch.int32, device=self.device), torch.empty((V, S), dtype=torch.float64, device=self.device),
+                       m[o_ptr + 2 * V:].view(torch.float32))
+            side = self._kp_last[2]
+            if (V, S) not in side:
+                side[(V, S)] = (torch.empty(V + V * S, dtype=torch.int32).pin_memory(), torch.empty((V, S), dtype=torch.float64).pin_memory())
+            nms_host = side[(V, S)]
 
         def issue():
             """The device side of this call (crop -> conv stack -> head + arg-max per batch, the exchange, the copy of the keypoints to
@@ -881,6 +908,14 @@ class HRNetPose(object):
                 kpl = gather_crop_keypoints(kp[lo:hi].contiguous(), n, self.world, self.rank, self.group)
                 # the tracker's device-side input, rebuilt from the gathered rows: (view, slot) <- (y, x, score) as float64
                 det[view_of.long(), slot_of.long()] = kpl[:, :, [1, 0, 2]].double()
+            if nms:
+                # behind the last decode of the call (the assembled buffer on every rank when the crops are sharded), from the ORIGINAL
+                # counts: a redo after a void forward decodes and filters again
+                _lib.pose_nms(torch.cuda.current_stream(self.device).cuda_stream, det, n_det, view_of, slot_of, bx, nms_dev[0][:V],
+                              nms_dev[0][V:], nms_dev[1], score=nms_dev[2], score_strides=(S, 1), oks_thre=self.oks_thre,
+                              in_vis_thre=self.in_vis_thre)
+                nms_host[0].copy_(nms_dev[0], non_blocking=True)
+                nms_host[1].copy_(nms_dev[1], non_blocking=True)
             # The reference's contract is host lists -- but nothing needs them before the caller looks: the device -> host copy of the
             # keypoints is only ENQUEUED here (pinned buffer, this stream) and the per-person dicts are built at the first access of the
             # dump (DumpResults).  A loop that passes the dump straight on to PersonTrack_Project3DPose waits for the GPU once per frame
@@ -890,7 +925,9 @@ class HRNetPose(object):
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(self.device))
             return done
-        out.attach_pending(det, n_det, host, issue(), views, boxes, cnt)
+        out.attach_pending(det, nms_dev[0][:V] if nms else n_det, host, issue(), views, boxes, cnt)
+        if nms:
+            out._nms = (nms_host[0], nms_host[1], V, S)
         out._net, out._issue = self, issue
         import weakref
         self._kp_last[1] = weakref.ref(out)
@@ -898,10 +935,12 @@ class HRNetPose(object):
 
     def _pinned_kp(self, n):
         """A pinned (n, 17, 3) float32 host buffer for the keypoints of one call; two per crop count, used alternately (a dump that is
-        still pending when its buffer comes round again is materialised first)."""
+        still pending when its buffer comes round again is materialised first).  An entry is [buffer, weak reference to the dump that
+        uses it, side buffers]: the side buffers ((views, slots) -> pinned outputs of the call's pose_nms) belong to the same dump as the
+        keypoints and are protected by the same rule; the dict stays empty while pose_nms is off."""
         ring = self._kp_pinned.setdefault(n, [])
         if len(ring) < 2:
-            ring.append([torch.empty((n, 17, 3), dtype=torch.float32).pin_memory(), None])
+            ring.append([torch.empty((n, 17, 3), dtype=torch.float32).pin_memory(), None, {}])
             ent = ring[-1]
         else:
             ent = ring[0]; ring.reverse()
@@ -922,6 +961,7 @@ class DumpResults(list):
     device_n_det = None      # (views,) int32
     _poses_host = None       # per view (n, 17, 3) float64 (y, x, score): what ivclabpose._unpack would rebuild from the dicts
     _pending = None          # (pinned host keypoints, event, views, boxes, per-view counts) until the first access
+    _nms = None              # HRNetPose(pose_nms=True): (pinned [n_det_out | keep_from], pinned pose_score, views, slots) of the call's filter
     _witness = None
 
     def attach(self, det, n_det, poses_host):
@@ -965,8 +1005,19 @@ class DumpResults(list):
             kp_h, cnt = self._host_rows(), self._pending[4]
             yxs = kp_h[:, :, [1, 0, 2]]
             first = np.concatenate([[0], np.cumsum(cnt)])
-            self._poses_host = [yxs[first[v]:first[v + 1]] for v in range(len(cnt))]
+            kept = self._kept()
+            # (filtered: compacted like the device buffer, so that the record's matched_det indices index it)
+            self._poses_host = [yxs[first[v]:first[v + 1]] if kept is None else yxs[[first[v] + s for s in kept[v]]].reshape(-1, 17, 3)
+                                for v in range(len(cnt))]
         return self._poses_host
+
+    def _kept(self):
+        """Per view the original slots the call's OKS-NMS kept, ascending (None without the filter); valid once _host_rows has waited."""
+        if self._nms is None:
+            return None
+        ki, _, V, S = self._nms
+        a = ki.numpy() if torch.is_tensor(ki) else ki
+        return [[int(s) for s in a[V + v * S:V + v * S + int(a[v])]] for v in range(V)]
 
     @poses_host.setter
     def poses_host(self, value):
@@ -983,8 +1034,19 @@ class DumpResults(list):
         n = len(views)
         flat = kp_h.reshape(n, 51).tolist()
         score = kp_h[:, :, 2].tolist()
-        for i in range(n):
-            list.__getitem__(self, views[i]).append(dict(bbox=list(boxes[i]), keypoints=flat[i], keypoints_score=score[i], feature=[]))
+        kept = self._kept()
+        if kept is None:
+            for i in range(n):
+                list.__getitem__(self, views[i]).append(dict(bbox=list(boxes[i]), keypoints=flat[i], keypoints_score=score[i], feature=[]))
+        else:                                              # the kept persons only, in slot order, each with its own box and its new score
+            first = np.concatenate([[0], np.cumsum(cnt)])
+            ps = self._nms[1].numpy()
+            for v, slots in enumerate(kept):
+                for k, s in enumerate(slots):
+                    i = int(first[v]) + s
+                    list.__getitem__(self, v).append(dict(bbox=list(boxes[i]), keypoints=flat[i], keypoints_score=score[i], feature=[],
+                                                          pose_score=float(ps[v, k])))
+            self._nms = (self._nms[0].numpy().copy(), ps.copy()) + tuple(self._nms[2:])       # (the pinned buffers go back to the ring)
         self._seal()
 
     def device_valid(self):

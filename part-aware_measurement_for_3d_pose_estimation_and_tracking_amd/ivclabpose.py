@@ -140,6 +140,13 @@ class ivclabpose(object):
                 self.pose_model.blur_kernel = int(opt('BLUR_KERNEL'))
             self.pose_model.dark = bool(opt('DARK'))
             self.pose_model.flip_test = bool(opt('FLIP_TEST'))
+            # optional keys OKS_NMS / OKS_THRE / IN_VIS_THRE (TEST.OKS_THRE / TEST.IN_VIS_THRE of the official configs; OKS_NMS switches the
+            # step on): every pose rescored and each view's duplicates removed on the device before the tracker (pam_pose_nms)
+            self.pose_model.pose_nms = bool(opt('OKS_NMS'))
+            if opt('OKS_THRE') is not None:
+                self.pose_model.oks_thre = float(opt('OKS_THRE'))
+            if opt('IN_VIS_THRE') is not None:
+                self.pose_model.in_vis_thre = float(opt('IN_VIS_THRE'))
             print("Pose Detector : ", _cfg(self.pose_detector, 'NAME'))
         if self.person_matcher is None:
             print("Person Matcher : Close.")

@@ -35,7 +35,8 @@ class FramePipeline(object):
     def __init__(self, calib_cameras, matcher, conf_threshold, frame_hw, max_dets=8, max_tracks=16, device=0, world=1,
                  rank=0, group=None, use_graph=True, hrnet=True, seed=0, shard='views', overlap_tracker=False, net=None, exchange='torch',
                  pose_streams=1, autotune=True, prewarm=False, width=48, resolution=(384, 288), flip_test=False, shift_heatmap=True,
-                 post_process=False, model_name='HRNet', crop_cap=None, detect_every=1, dark=False, blur_kernel=None):
+                 post_process=False, model_name='HRNet', crop_cap=None, detect_every=1, dark=False, blur_kernel=None, pose_nms=False,
+                 oks_thre=0.9, in_vis_thre=0.2):
         """shard: 'views' -- rank owns whole camera views (pose_step / track_step take view-local inputs); 'crops' -- the
         frame's crops are dealt out evenly over the ranks (pose_step_crops / track_step_crops take global view indices).
         overlap_tracker (either mode): exchange + tracker kernel + fetch of frame t run on their own stream, under the conv
@@ -56,7 +57,17 @@ class FramePipeline(object):
         crop_cap: rows of the device-built crop table (pose_step_boxes): crop, forward and decode of such a frame run for this many rows
         whatever the boxes' count.  None = this rank's views x max_dets; under prewarm rounded up to the network's bucket.
         detect_every: the schedule of pose_step_auto (box_source): the detector on every detect_every-th frame since the last reset(),
-        boxes round the tracks' predictions in between."""
+        boxes round the tracks' predictions in between.
+        pose_nms / oks_thre / in_vis_thre: behind the decode of every frame (pose_step, pose_step_boxes, pose_step_auto) each view's poses
+        are rescored and its duplicates removed by greedy OKS-NMS on the device (pam_pose_nms, the rule: include/pam.h; at most 32 slots
+        per view).  ``self.nms_n_det`` (device, one count per view of this rank) is then the n_det_local for track_step -- it replaces
+        ``table_n_det`` -- and results() adds rec['pose_nms'] = dict(n_det, keep_from).  Box scores: the detector's, read in place from
+        its list, on detector frames; 1.0 on track-box frames; pose_step takes a table.  The pipeline's own setting: a shared `net`
+        keeps its own (HRNetPose.predict's).  Off: every step issues exactly the launches it issued without the option."""
+        if pose_nms and shard == 'crops':
+            raise ValueError("pose_nms needs shard='views': crop sharding builds its select index from the host box list, before the filter")
+        if pose_nms and max_dets > _lib.POSE_NMS_MAX:
+            raise ValueError('pose_nms takes at most %d slots per view (max_dets=%d)' % (_lib.POSE_NMS_MAX, max_dets))
         self.device = torch.device('cuda:%d' % device)
         torch.cuda.set_device(self.device)
         self.cams = calib_cameras
@@ -74,7 +85,8 @@ class FramePipeline(object):
                                                           max_dets=max_dets, autotune=autotune,
                                                           max_crops=len(calib_cameras) * max_dets, flip_test=flip_test,
                                                           shift_heatmap=shift_heatmap, post_process=post_process, dark=dark,
-                                                          blur_kernel=blur_kernel) if hrnet else None)
+                                                          blur_kernel=blur_kernel, pose_nms=pose_nms, oks_thre=oks_thre,
+                                                          in_vis_thre=in_vis_thre) if hrnet else None)
         self.shard = shard
         # exchange: 'torch' = torch.distributed (RCCL when the backend is nccl, gloo in the CPU tests); 'abi' = pam_allgather_keypoints,
         # the library's own RCCL call on the decode stream (view sharding only)
@@ -129,6 +141,17 @@ class FramePipeline(object):
         self._ct_host = torch.zeros(4, dtype=torch.int32).pin_memory()
         self._ct_fetched = False
         self._ev_slot_read, self._table_no, self._table_slot = [None, None], 0, 0
+        # the OKS-NMS behind the decode: [n_det | keep_from] int32 and the new scores, one set (the launch sits behind wait_track, so the
+        # track step of the frame before has read its counts), and a pinned copy of the int32 part that travels with the record's fetch
+        self.pose_nms, self.oks_thre, self.in_vis_thre = bool(pose_nms), float(oks_thre), float(in_vis_thre)
+        self.nms_n_det, self.nms_keep_from, self.nms_pose_score, self._nms_live, self._nms_fetched = None, None, None, False, False
+        if self.pose_nms:
+            nv = max(1, len(self.mine))
+            self._nms_i = torch.zeros(nv + nv * max_dets, dtype=torch.int32, device=self.device)
+            self._nms_i[nv:].fill_(-1)
+            self.nms_n_det, self.nms_keep_from = self._nms_i[:nv], self._nms_i[nv:].view(nv, max_dets)
+            self.nms_pose_score = torch.zeros((nv, max_dets), dtype=torch.float64, device=self.device)
+            self._nms_host = torch.zeros(nv + nv * max_dets, dtype=torch.int32).pin_memory()
 
     def _pick_track_stream(self, tries=8, spin_us=400, avoid=None):
         """A stream for the exchange + tracker that REALLY runs beside the caller's (pose) stream.  HIP streams are multiplexed onto a few
@@ -234,8 +257,9 @@ class FramePipeline(object):
     def stream_ptr(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def _pose(self, frame_ptrs, views, slot_of, boxes, det, time_events, after_crop=None):
-        """crop -> conv stack -> head + arg-max for one frame on the current stream, replay slot = frame parity when two pose streams run."""
+    def _pose(self, frame_ptrs, views, slot_of, boxes, det, time_events, after_crop=None, n_det=None, score=(None, (0, 0), None)):
+        """crop -> conv stack -> head + arg-max for one frame on the current stream, replay slot = frame parity when two pose streams run.
+        pose_nms: + the filter, from the counts n_det and the box scores score = (tensor or address, strides, view map)."""
         k = (self._frame_no & 1) if self.pose_streams is not None else 0
         n = int(views.numel())
         x = self.net.input_buffer(self.net.bucket(n) if self.bucketed else n, k)     # a bucket's spare rows repeat the last crop, undecoded
@@ -249,6 +273,11 @@ class FramePipeline(object):
             time_events[1].record(torch.cuda.current_stream(self.device))
         self.wait_track()                               # the previous frame's exchange / tracker read the buffer decode writes
         self.net.head_decode(f, views, slot_of, boxes, det, n=n)
+        if self.pose_nms:
+            _lib.pose_nms(torch.cuda.current_stream(self.device).cuda_stream, det, n_det, views, slot_of, boxes, self.nms_n_det,
+                          self.nms_keep_from, self.nms_pose_score, max_dets=self.max_dets, score=score[0], score_strides=score[1],
+                          views=score[2], oks_thre=self.oks_thre, in_vis_thre=self.in_vis_thre)
+            self._nms_live = True
 
     @contextlib.contextmanager
     def frame(self):
@@ -265,14 +294,23 @@ class FramePipeline(object):
             yield
         self._frame_no += 1
 
-    def pose_step(self, frame_ptrs, view_local, slot_of, boxes, time_events=None, after_crop=None):
-        """HRNet side for this rank's crops.  view_local: int32 (N,) index into self.mine; writes self.det_local."""
-        self._table_info = None
+    def pose_step(self, frame_ptrs, view_local, slot_of, boxes, time_events=None, after_crop=None, n_det=None, scores=None):
+        """HRNet side for this rank's crops.  view_local: int32 (N,) index into self.mine; writes self.det_local.
+        pose_nms: n_det (one int32 device count per view of this rank, what track_step would have been given) is required and
+        ``self.nms_n_det`` is what track_step takes instead; scores: (len(mine), max_dets) float32 device table of box scores (None: 1.0)."""
+        self._table_info, self._nms_live = None, False
+        if self.pose_nms and self.net is not None and n_det is None:
+            raise ValueError('pose_step with pose_nms needs n_det: the filter starts from the per-view counts')
         if int(view_local.numel()) == 0 or self.net is None:
             if after_crop is not None:
                 after_crop()
+            if self.pose_nms and self.net is not None:  # nothing decoded, nothing kept
+                self.wait_track()
+                self.nms_n_det.zero_(); self.nms_keep_from.fill_(-1)
+                self._nms_live = True
             return
-        self._pose(frame_ptrs, view_local, slot_of, boxes, self.det_local, time_events, after_crop)
+        self._pose(frame_ptrs, view_local, slot_of, boxes, self.det_local, time_events, after_crop, n_det=n_det,
+                   score=(scores, (self.max_dets, 1), None))
 
     def write_local(self, rows):
         """Copy keypoint rows (len(mine), max_dets, 17, 3) into this rank's records, ordered behind the previous frame's readers."""
@@ -294,6 +332,9 @@ class FramePipeline(object):
                 self._ct_fetched = self._table_info is not None
                 if self._ct_fetched:                     # the crop table's info words travel with the record (results())
                     self._ct_host.copy_(self._table_info, non_blocking=True)
+                self._nms_fetched = self._nms_live
+                if self._nms_fetched:                    # ... and so do the filter's counts and keep table
+                    self._nms_host.copy_(self._nms_i, non_blocking=True)
         if self.track_stream is None:
             issue(self.stream_ptr())
             return
@@ -349,12 +390,14 @@ class FramePipeline(object):
             self.handle.track_boxes(self.stream_ptr(), frame_id, self.frame_w, self.frame_h, b['boxes'], b['count'], b['ids'], b['info'], **kw)
         return b['boxes'], b['count'], b['ids']
 
-    def pose_step_boxes(self, frame_ptrs, boxes, count, views=None, time_events=None, after_crop=None):
+    def pose_step_boxes(self, frame_ptrs, boxes, count, views=None, time_events=None, after_crop=None, use_scores=True):
         """pose_step on boxes that are on the device in the detector's layout (YOLOv3.detect_dev, track_boxes): boxes (G, max_det, 5)
         float32, count (>= G,) int32; views: int32 device tensor, for each of this rank's views the image of `boxes` that holds its list
         (None: image i is view mine[i]).  pam_crop_table turns them into a crop table of crop_cap rows (spare rows repeat the last real
         one), and crop, forward and decode run for crop_cap rows through the kernels pose_step uses.  ``self.table_n_det`` (device, one
-        count per view of this rank) is the n_det_local for track_step."""
+        count per view of this rank) is the n_det_local for track_step -- ``self.nms_n_det`` under pose_nms, whose box scores are column 4
+        of `boxes`, read in place (use_scores=False: 1.0)."""
+        self._nms_live = False
         if self.shard != 'views':
             raise ValueError("pose_step_boxes needs shard='views': crop sharding builds its select index from a host box list")
         if not len(self.mine) or self.net is None:
@@ -371,7 +414,8 @@ class FramePipeline(object):
         _lib.crop_table(cur.cuda_stream, boxes, count, self.frame_w, self.frame_h, self.max_dets, T['view_of'], T['slot_of'], T['xywh'],
                         T['n_det'], T['info'], views=views)
         self.table_n_det, self._table_info = T['n_det'], T['info']
-        self._pose(frame_ptrs, T['view_of'], T['slot_of'], T['xywh'], self.det_local, time_events, after_crop)
+        score = (boxes.data_ptr() + 16, (5 * int(boxes.shape[1]), 5), views) if (self.pose_nms and use_scores) else (None, (0, 0), None)
+        self._pose(frame_ptrs, T['view_of'], T['slot_of'], T['xywh'], self.det_local, time_events, after_crop, n_det=T['n_det'], score=score)
 
     def pose_step_auto(self, frame_id, frame_ptrs, frames, next_frames=None, time_events=None, after_crop=None, **rule):
         """pose_step_boxes with the boxes the schedule names (box_source(frames since reset(), detect_every)): the detector's -- the
@@ -400,7 +444,8 @@ class FramePipeline(object):
                 after_crop()
             if ahead:
                 self._det_ahead = self.detect_ahead(next_frames)
-        self.pose_step_boxes(frame_ptrs, boxes, count, views=views, time_events=time_events, after_crop=crop_done)
+        self.pose_step_boxes(frame_ptrs, boxes, count, views=views, time_events=time_events, after_crop=crop_done,
+                             use_scores=src == 'detector')
         self._auto_no += 1
         return src
 
@@ -471,4 +516,7 @@ class FramePipeline(object):
         if self._ct_fetched:
             w = self._ct_host.numpy()
             rec['crop_table'] = dict(rows=int(w[0]), wanted=int(w[1]), status=int(w[2]))
+        if self._nms_fetched:
+            a, nv = self._nms_host.numpy(), int(self.nms_n_det.numel())
+            rec['pose_nms'] = dict(n_det=[int(x) for x in a[:nv]], keep_from=a[nv:].reshape(nv, self.max_dets).copy())
         return rec
