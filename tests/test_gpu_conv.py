@@ -8,6 +8,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import pam
+import guarded_mem as G
 
 pytestmark = pytest.mark.gpu
 
@@ -148,6 +149,7 @@ def test_upsample_add_vs_torch():
     g = torch.Generator().manual_seed(5)
     e = hrnet_hip.HipHRNet.__new__(hrnet_hip.HipHRNet)
     e.lib = _lib.load(); e.device = dev; e.tile_cfg = -1
+    e.arena = G.GuardArena(dev, 4 << 20)                         # the outputs between sentinel bands (tests/guarded_mem.py)
     base = torch.randn((2, 48, 24, 16), generator=g).to(torch.bfloat16).to(dev).contiguous(memory_format=torch.channels_last)
     terms = [torch.randn((2, 48, 24 >> s, 16 >> s), generator=g).to(torch.bfloat16).to(dev).contiguous(memory_format=torch.channels_last) for s in (1, 2, 3)]
     for nt in (1, 2, 3):
@@ -160,6 +162,7 @@ def test_upsample_add_vs_torch():
                 ref = torch.relu(ref)
             torch.cuda.synchronize()
             assert torch.equal(y, ref.to(torch.bfloat16))
+            assert e.arena.report() == ''                        # no write outside y, nothing of y left unwritten
 
 
 def test_channel_sliced_operands_and_partial_relu():
@@ -184,10 +187,12 @@ def test_channel_sliced_operands_and_partial_relu():
         assert bool((err <= 2.0 ** -7 * ref.abs() + 2e-2).all()), ((off, cin, cout, k, stride, relu_from), err.max().item())
     base = torch.randn((2, 48, 24, 18), generator=g).to(torch.bfloat16).to(dev).contiguous(memory_format=torch.channels_last)
     coarse = torch.randn((2, 96, 12, 9), generator=g).to(torch.bfloat16).to(dev).contiguous(memory_format=torch.channels_last)
+    e.arena = G.GuardArena(dev, 1 << 20)                         # the sum's output between sentinel bands (tests/guarded_mem.py)
     out = e.upsample_add(base, [wide[:, 48:96], coarse[:, 48:96]], [0, 1], True)
     ref = torch.relu(base.float() + wide[:, 48:96].float() + F.interpolate(coarse[:, 48:96].float(), scale_factor=2, mode='nearest'))
     torch.cuda.synchronize()
     assert torch.equal(out, ref.to(torch.bfloat16))
+    assert e.arena.report() == ''
 
 
 @pytest.mark.gpu

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 import pam
 from oracle import yolo_ref as Y
+import guarded_mem as G
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -95,6 +96,7 @@ def test_resize_frames_vs_oracle(shape):
 
 def test_upsample_concat_vs_oracle():
     e = _engine()
+    e.arena = G.GuardArena(e.device, 8 << 20)                    # the outputs between sentinel bands (tests/guarded_mem.py)
     g = torch.Generator().manual_seed(4)
     for (n, h, w, ca, cb) in [(2, 13, 13, 256, 512), (1, 7, 5, 8, 16), (3, 26, 26, 128, 256)]:
         a = torch.randn((n, ca, h, w), generator=g).to(torch.bfloat16).to(DEV).contiguous(memory_format=torch.channels_last)
@@ -102,6 +104,7 @@ def test_upsample_concat_vs_oracle():
         y = e.upsample_concat(a, b)
         exp = Y.upsample_concat(a.permute(0, 2, 3, 1).float().cpu().numpy(), b.permute(0, 2, 3, 1).float().cpu().numpy())
         assert np.array_equal(y.permute(0, 2, 3, 1).float().cpu().numpy(), exp)
+        assert e.arena.report() == ''                            # no write outside y, nothing of y left unwritten
     rc = e.lib.pam_upsample_concat_nhwc_bf16(None, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), C.c_void_p(y.data_ptr()), 1, 7, 6, 8, 8)
     assert rc == -1                                              # odd output height: PAM_E_ARG
 

@@ -8,6 +8,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import pam
+import guarded_mem as G
 
 pytestmark = pytest.mark.gpu
 
@@ -189,11 +190,16 @@ def test_fuse_sum_vs_torch_and_the_launches_it_replaces(eng, case):
     plain = [wide[:, 8:8 + c], wide[:, 8 + c:8 + 2 * c]][:nplain]              # channel slices, as the merged strided heads hand them over
     srcs = [_cl((n, c << sh, h >> sh, w >> sh), 5 + sh, dev) for sh in shifts]
     eng._keep = []
-    y = eng.fuse_sum(op, base, plain, srcs, relu=True, tile=tile or (0, 0))
-    # the launches it replaces: one 1x1 convolution per source, then the up-sampling sum with the terms in branch order
-    packed = [hrnet_hip.PackedConv(cv, dev) for cv in convs]
-    terms = [eng.conv(pk, s) for pk, s in zip(packed, srcs)]
-    y0 = eng.upsample_add(base, plain + terms, [0] * nplain + list(shifts), relu=True)
+    # every output of the three kinds of launch between sentinel bands (tests/guarded_mem.py): y, the terms (less than y together), y0
+    eng.arena = arena = G.GuardArena(dev, 3 * 2 * base.numel() + (1 << 20))
+    try:
+        y = eng.fuse_sum(op, base, plain, srcs, relu=True, tile=tile or (0, 0))
+        # the launches it replaces: one 1x1 convolution per source, then the up-sampling sum with the terms in branch order
+        packed = [hrnet_hip.PackedConv(cv, dev) for cv in convs]
+        terms = [eng.conv(pk, s) for pk, s in zip(packed, srcs)]
+        y0 = eng.upsample_add(base, plain + terms, [0] * nplain + list(shifts), relu=True)
+    finally:
+        eng.arena = None
     ref = base.float()
     for t in plain:
         ref = ref + t.float()
@@ -202,6 +208,7 @@ def test_fuse_sum_vs_torch_and_the_launches_it_replaces(eng, case):
         ref = ref + F.interpolate(t.to(torch.bfloat16).float(), scale_factor=2 ** sh, mode='nearest')
     ref = torch.relu(ref)
     torch.cuda.synchronize()
+    assert arena.report() == '', case                          # no write outside an output, nothing of an output left unwritten
     err = (y.float() - ref).abs()
     assert bool((err <= 2.0 ** -6 * ref.abs() + 6e-2).all()), (case, err.max().item())      # a product rounded one bf16 step apart moves the sum by that step
     assert torch.equal(y0, y), (case, (y0.float() - y.float()).abs().max().item())

@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 import darknet_tiny_calibrated as TC
 from oracle import yolo_ref as Y
+import guarded_mem as G
 from test_gpu_darknet_layers import HEAD_FLOOR_RATIO, Checker, Spy, family_of, input_x8, padded_bf16, rel
 
 pytestmark = pytest.mark.gpu
@@ -45,10 +46,13 @@ def test_maxpool_bit_exact_vs_torch(shape, size, stride):
     real = c - c // 2 if c >= 16 else c
     x = torch.randn((n, real, h, w), generator=g)
     x = torch.cat([x, torch.zeros((n, c - real, h, w))], 1).to(torch.bfloat16).to(DEV).contiguous(memory_format=torch.channels_last)
-    y = _engine().maxpool(x, size, stride)
+    e = _engine()
+    e.arena = G.GuardArena(e.device, 2 * x.numel() + (1 << 20))  # the output between sentinel bands (tests/guarded_mem.py)
+    y = e.maxpool(x, size, stride)
     lo, hi = (size - 1) // 2, (size - 1) - (size - 1) // 2
     want = F.max_pool2d(F.pad(x.float(), (lo, hi, lo, hi), value=float('-inf')), size, stride)
     torch.cuda.synchronize()
+    assert e.arena.report() == ''                                # no write outside y, nothing of y left unwritten
     assert tuple(y.shape) == tuple(want.shape) == (n, c, (h - 1) // stride + 1, (w - 1) // stride + 1)
     if shape == (1, 31, 23, 8):
         assert tuple(y.shape[2:]) == (16, 12)
