@@ -217,6 +217,14 @@ int pam_op_greedy(PamHandle* h, int mode, int V, const int32_t* cids, const void
 /* SVD_pose_kernel_jf, construction.py:89-114: keep_mask[17] view sets, Ts[V] ages -> 17*3 */
 int pam_op_dlt(PamHandle* h, int V, const int32_t* cids, const int32_t* Ts, const double* pose_mat,
                const uint32_t* keep_mask, const double* next_pose, double* out);
+/* pam_op_dlt with the solver's paths selectable and reported.  nsplit 1: every joint's rows folded by one lane, as pam_op_dlt does;
+ * nsplit 4: the form the frame step takes on tracks of more than 8 views -- lane q folds the kept views q, q + 4, ... into a triangular
+ * factor of its own, the four factors are packed to device memory, merged in the order 0..3 and solved.  solver 0: inverse iteration, then
+ * one-sided Jacobi if it did not converge (what the frame step runs); solver 1: Jacobi alone.  path[17]: 0 = fewer than two kept views,
+ * next_pose copied; 1 = inverse iteration converged; 2 = Jacobi.  PAM_E_ARG: V outside 1..32, nsplit not 1 or 4, solver not 0 or 1, a
+ * NULL argument, a camera id outside the handle's views. */
+int pam_op_dlt_paths(PamHandle* h, int V, const int32_t* cids, const int32_t* Ts, const double* pose_mat,
+                     const uint32_t* keep_mask, const double* next_pose, int nsplit, int solver, double* out, int32_t* path);
 /* IterTrack.smooth_3dpose, IterativeTracker.py:371-383: hist L*17*3 + raw 17*3 -> 17*3 */
 int pam_op_smooth(PamHandle* h, int L, const double* hist, const double* raw, double* out);
 /* IterTrack.update_motion, IterativeTracker.py:385-395: hist L*17*3 (L>=2) -> float32 17*3 */

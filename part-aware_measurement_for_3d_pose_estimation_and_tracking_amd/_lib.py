@@ -59,6 +59,7 @@ _SIGS = {
     'pam_op_epi_dist_init': (_I, [_P, _I, _P, _P, _P]),
     'pam_op_greedy': (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
     'pam_op_dlt': (_I, [_P, _I, _P, _P, _P, _P, _P, _P]),
+    'pam_op_dlt_paths': (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
     'pam_op_smooth': (_I, [_P, _I, _P, _P, _P]),
     'pam_op_velocity': (_I, [_P, _I, _P, _P]),
     'pam_op_hyp_cost': (_I, [_P, _I, _P, _P, _I, _P, _P, _P]),
@@ -452,6 +453,18 @@ class Handle(object):
         nx = np.ascontiguousarray(next_pose, dtype=np.float64); out = np.zeros((PAM_J, 3))
         self._chk(self.lib.pam_op_dlt(self._h, len(c), _ptr(c), _ptr(t), _ptr(pm), _ptr(k), _ptr(nx), _ptr(out)))
         return out
+
+    def op_dlt_paths(self, cids, Ts, pose_mat, keep_masks, next_pose, nsplit=1, solver=0):
+        """op_dlt with the solver's paths selectable (nsplit 1 / 4: unsplit or the four-way fold / pack / merge of the wide rigs; solver 0 /
+        1: inverse iteration with the Jacobi fall-back, or Jacobi alone) -> (out (17, 3), path (17,) int32: 0 copied, 1 inverse iteration,
+        2 Jacobi)."""
+        c = np.ascontiguousarray(cids, dtype=np.int32); t = np.ascontiguousarray(Ts, dtype=np.int32)
+        pm = np.ascontiguousarray(pose_mat, dtype=np.float64); k = np.ascontiguousarray(keep_masks, dtype=np.uint32)
+        nx = np.ascontiguousarray(next_pose, dtype=np.float64); out = np.zeros((PAM_J, 3)); path = np.full(PAM_J, -1, dtype=np.int32)
+        assert len(t) == len(c) and pm.shape == (len(c), PAM_J, 3) and k.shape == (PAM_J,) and nx.shape == (PAM_J, 3)
+        self._chk(self.lib.pam_op_dlt_paths(self._h, len(c), _ptr(c), _ptr(t), _ptr(pm), _ptr(k), _ptr(nx), int(nsplit), int(solver),
+                                            _ptr(out), _ptr(path)))
+        return out, path
 
     def op_smooth(self, hist, raw):
         hs = np.ascontiguousarray(hist, dtype=np.float64).reshape(-1, PAM_J, 3)

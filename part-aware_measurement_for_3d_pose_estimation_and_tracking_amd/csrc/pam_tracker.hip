@@ -90,7 +90,7 @@ struct Scratch {
     uint32_t* keep; int* nview; int* ok;   // [MAXT][17], [MAXT][17], [MAXT]
     uint32_t* h_conf; float* h_sum;        // [MAXH][17][C]
     uint32_t* h_keep; double* h_pose; int* h_slot;   // [MAXH][17], [MAXH][51], [MAXH]
-    double* rpart;                  // [MAXT][17][4][10] partial triangular factors of the split DLT
+    double* rpart;                  // [MAXT][17][DLT_SPLIT][DLT_PACK] partial triangular factors of the split DLT
 };
 // small, latency-critical arrays first (they are carved out of LDS when they fit: the serial LSAP walks, atomically built
 // conflict masks and every index-chasing read then cost an LDS access instead of an L2 round trip), bulk arrays after
@@ -122,7 +122,7 @@ __host__ __device__ inline char* carve_ws_bulk(char* base, const Dims& d, Scratc
     w.h_conf = c.take<uint32_t>((size_t)d.MAXH * J * d.C); w.h_sum = c.take<float>((size_t)d.MAXH * J * d.C);
     w.h_keep = c.take<uint32_t>((size_t)d.MAXH * J); w.h_pose = c.take<double>((size_t)d.MAXH * J3);
     w.h_slot = c.take<int>(d.MAXH);
-    w.rpart = c.take<double>((size_t)d.MAXT * J * 4 * 10);
+    w.rpart = c.take<double>((size_t)d.MAXT * J * DLT_SPLIT * DLT_PACK);
     return c.bytes(0);
 }
 __host__ __device__ inline size_t hot_bytes(const Dims& d) {
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(NTHREADS, 4) void k_frame(FrameArgs A) {      // 4 
     if (tid == 0) out_d[5] = now_s();
     // ---- P4c: greedy filter (matching.py:243-285) + weighted DLT (construction.py:89-114) per (track, joint); tracks that
     //           see many views split each joint's row folding over 4 lanes and merge the triangular factors ------------
-    const int nsplit = maxV > 8 ? 4 : 1;
+    const int nsplit = maxV > 8 ? DLT_SPLIT : 1;
     for (int it = tid; it < nT * J * nsplit; it += NT) {
         const int ij = it / nsplit, q = it % nsplit, i = ij / J, j = ij % J;
         const int V = ws.sel_n[i];
@@ -458,11 +458,8 @@ __global__ __launch_bounds__(NTHREADS, 4) void k_frame(FrameArgs A) {      // 4 
             if (V == 0) continue;
             const int s = st.order[i];
             const int* scid = ws.sel_cid + i * C;
-            double R[4][4];
-            dlt_zero(R);
-            dlt_fold(cs, V, q, nsplit, scid, ws.sel_T + i * C, prm.w_lambda_t, prm.lambda_t, ws.keep[i * J + j],
-                     [&](int v) { return st.p2d_pose + ((size_t)s * C + scid[v]) * J3 + j * 3; }, R);
-            dlt_pack(R, ws.rpart + ((size_t)ij * 4 + q) * 10);
+            dlt_joint_part(cs, V, q, scid, ws.sel_T + i * C, prm.w_lambda_t, prm.lambda_t, ws.keep[i * J + j],
+                           [&](int v) { return st.p2d_pose + ((size_t)s * C + scid[v]) * J3 + j * 3; }, ws.rpart + (size_t)ij * DLT_SPLIT * DLT_PACK);
         }
         __syncthreads();
         for (int it = tid; it < nT * J; it += NT) {
@@ -470,10 +467,7 @@ __global__ __launch_bounds__(NTHREADS, 4) void k_frame(FrameArgs A) {      // 4 
             if (ws.sel_n[i] == 0) continue;
             double X[3];
             if (ws.nview[i * J + j] >= 2) {
-                double R[4][4];
-                dlt_zero(R);
-                for (int q = 0; q < 4; ++q) dlt_merge(R, ws.rpart + ((size_t)it * 4 + q) * 10);
-                dlt_solve(R, X);
+                dlt_joint_merge(ws.rpart + (size_t)it * DLT_SPLIT * DLT_PACK, X);
             } else {
                 X[0] = ws.pred[i * J3 + j * 3]; X[1] = ws.pred[i * J3 + j * 3 + 1]; X[2] = ws.pred[i * J3 + j * 3 + 2];
             }
@@ -835,6 +829,32 @@ __global__ void k_op_dlt(CamSet cs, const PamParams* prm, int V, const int* cids
                       [&](int v) { return pm + ((size_t)v * J + j) * 3; }, X);
         else { X[0] = next_pose[j * 3]; X[1] = next_pose[j * 3 + 1]; X[2] = next_pose[j * 3 + 2]; }
         out[j * 3] = X[0]; out[j * 3 + 1] = X[1]; out[j * 3 + 2] = X[2];
+    }
+}
+// the same joints with the paths of P4c selectable: nsplit 1 = dlt_joint, nsplit DLT_SPLIT = the fold / pack / merge / solve sequence of the
+// wide rigs (part: 17 x DLT_SPLIT x DLT_PACK doubles); jacobi_only = the fall-back alone; path[j] = DLT_PATH_* of joint j.  One workgroup.
+__global__ void k_op_dlt_paths(CamSet cs, const PamParams* prm, int V, const int* cids, const int* Ts, const double* pm,
+                               const uint32_t* keep, const double* next_pose, int nsplit, int jacobi_only, double* part, double* out,
+                               int* path) {
+    const int tid = threadIdx.x;
+    if (nsplit > 1) {
+        for (int it = tid; it < J * DLT_SPLIT; it += blockDim.x) {
+            const int j = it / DLT_SPLIT, q = it % DLT_SPLIT;
+            dlt_joint_part(cs, V, q, cids, Ts, prm->w_lambda_t, prm->lambda_t, keep[j],
+                           [&](int v) { return pm + ((size_t)v * J + j) * 3; }, part + (size_t)j * DLT_SPLIT * DLT_PACK);
+        }
+        __syncthreads();
+    }
+    const int j = tid;
+    if (j < J) {
+        double X[3];
+        int p = DLT_PATH_COPIED;
+        if (__popc(keep[j]) < 2) { X[0] = next_pose[j * 3]; X[1] = next_pose[j * 3 + 1]; X[2] = next_pose[j * 3 + 2]; }
+        else if (nsplit > 1) p = dlt_joint_merge(part + (size_t)j * DLT_SPLIT * DLT_PACK, X, jacobi_only != 0);
+        else p = dlt_joint(cs, V, cids, Ts, prm->w_lambda_t, prm->lambda_t, keep[j],
+                           [&](int v) { return pm + ((size_t)v * J + j) * 3; }, X, jacobi_only != 0);
+        out[j * 3] = X[0]; out[j * 3 + 1] = X[1]; out[j * 3 + 2] = X[2];
+        path[j] = p;
     }
 }
 __global__ void k_op_smooth(const PamParams* prm, int L, const double* hist, const double* raw, double* out) {
@@ -1362,6 +1382,23 @@ extern "C" int pam_op_dlt(PamHandle* h, int V, const int32_t* cids, const int32_
     hipLaunchKernelGGL(k_op_dlt, dim3(1), dim3(64), 0, 0, camset(h), h->d_prm, V, c, t, pm, k, np, o);
     int rc = S.done("pam_op_dlt"); if (rc) return rc;
     S.back(out, o, J3);
+    return S.ok ? PAM_OK : PAM_E_HIP;
+}
+
+extern "C" int pam_op_dlt_paths(PamHandle* h, int V, const int32_t* cids, const int32_t* Ts, const double* pose_mat,
+                                const uint32_t* keep_mask, const double* next_pose, int nsplit, int solver, double* out, int32_t* path) {
+    OP_PROLOG(h);
+    ARGCHK(h, V >= 1 && V <= PAM_MAX_VIEWS, "bad V");
+    ARGCHK(h, (nsplit == 1 || nsplit == DLT_SPLIT) && (solver == 0 || solver == 1), "bad nsplit / solver");
+    ARGCHK(h, cids && Ts && pose_mat && keep_mask && next_pose && out && path, "null argument");
+    for (int v = 0; v < V; ++v) ARGCHK(h, cids[v] >= 0 && cids[v] < h->d.C, "camera id out of range");
+    const int* c = S.in(cids, V); const int* t = S.in(Ts, V); const double* pm = S.in(pose_mat, (size_t)V * J3);
+    const uint32_t* k = S.in(keep_mask, J); const double* np = S.in(next_pose, J3);
+    double* part = S.out<double>((size_t)J * DLT_SPLIT * DLT_PACK); double* o = S.out<double>(J3); int* pp = S.out<int>(J);
+    OP_CHECK_STAGE("pam_op_dlt_paths");
+    hipLaunchKernelGGL(k_op_dlt_paths, dim3(1), dim3(64), 0, 0, camset(h), h->d_prm, V, c, t, pm, k, np, nsplit, solver, part, o, pp);
+    int rc = S.done("pam_op_dlt_paths"); if (rc) return rc;
+    S.back(out, o, J3); S.back(path, pp, J);
     return S.ok ? PAM_OK : PAM_E_HIP;
 }
 

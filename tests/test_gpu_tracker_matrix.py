@@ -64,6 +64,36 @@ def test_single_scene_form_vs_oracle(monkeypatch, form, C, P, max_dets, max_trac
     assert run.n_out > n_frames * P // 2
 
 
+# One sequence gross enough that k_frame's DLT certainly leaves the inverse iteration for the Jacobi fall-back: 12 views (form C, tracks of
+# more than 8 views fold their rows four ways), 40 px of keypoint noise, every second pose with an outlier joint.  Chosen on the CPU from the
+# systems the oracle solves (O.dlt_solve wrapped), each against mpmath's 50-digit SVD: seed 6 has 8 278 solved joints, 77 of them with
+# s4 / s3 > 0.3 -- eight steps shrink the iteration's error by no more than 0.3^14 ~ 5e-8, so the device took Jacobi for them (tests/
+# test_gpu_dlt_paths.py pins that rule on the operator; the kept view sets are asserted identical here) -- and LAPACK's worst error against
+# the truth is 3.9e-9 m over all of them, so the 1e-6 m bar of `step` is a fair one.
+FALLBACK = dict(C=12, P=4, max_dets=8, max_tracks=32, n_frames=60, seed=6, noise_px=40.0, outlier_p=0.5)
+
+
+def test_gross_noise_drives_the_frame_step_into_the_jacobi_fall_back(monkeypatch):
+    f = FALLBACK
+    size = M.add_rig(monkeypatch, f['C'], f['P'])
+    seq = synth.make_sequence(size, n_frames=f['n_frames'], seed=f['seed'], noise_px=f['noise_px'], outlier_p=f['outlier_p'], **M.STRESS)
+    rho, solve = [], O.dlt_solve
+
+    def spy(A, mask, nviews, next_pose=None):
+        for j in np.nonzero(np.asarray(nviews) >= 2)[0]:
+            s = np.linalg.svd(A[j][np.asarray(mask[j]) == 1], compute_uv=False)
+            rho.append(s[3] / s[2])
+        return solve(A, mask, nviews, next_pose)
+    monkeypatch.setattr(O, 'dlt_solve', spy)
+    run = M.FacadeVsOracle(seq, f['max_dets'], f['max_tracks'])
+    assert run.handle.plan() == PLANS['C']
+    for t, views in enumerate(seq['frames']):
+        run.step(t, views)
+    rho = np.array(rho)
+    assert len(rho) > 5000 and (rho > 0.3).sum() >= 50, (len(rho), (rho > 0.3).sum())
+    assert run.max_views > 8 and run.n_out > f['n_frames'] * f['P'] // 2
+
+
 BATCHED = [('E', 31, 8, 8, 16), ('F', 31, 16, 16, 32), ('E', 32, 8, 8, 16), ('F', 32, 16, 16, 32)]
 
 
