@@ -195,6 +195,47 @@ int pam_pose_nms(void* stream, int n_views, int max_dets, int det_slots, double*
                  long long view_stride, long long slot_stride, const int32_t* dev_views, const double* vars, double oks_thre,
                  double in_vis_thre, int32_t* dev_n_det_out, int32_t* dev_keep_from, double* dev_pose_score);
 
+/* ---- lens distortion out of the decoded keypoints (csrc/pam_lens.hip, csrc/pam_lens.hpp; no reference counterpart: the reference's
+ * Camera.undistort / undistort_points are identity stubs and its matching path takes every camera for an ideal pin-hole) -----------------
+ * The model is Brown-Conrady in the OpenCV / Panoptic order (k1, k2, p1, p2, k3) on normalised coordinates, K upper-triangular.  A camera
+ * is a row of 10 doubles: fx, fy, cx, cy, skew, k1, k2, p1, p2, k3.  All float64.  With u the column and w the row of a pixel:
+ *   normalise   y = (w - cy) / fy;  x = (u - cx - skew * y) / fx            pixels   u = fx * x + skew * y + cx;  w = fy * y + cy
+ *   forward     r2 = x * x + y * y;  rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))
+ *               xd = x * rad + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+ *               yd = y * rad + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+ *   inverse     of (dx, dy): (x, y) = (dx, dy), then 8 times, always 8 (no data-dependent exit):
+ *               r2, rad as above;  drad = k1 + r2 * (2.0 * k2 + 3.0 * r2 * k3)
+ *               ex = xd(x, y) - dx;  ey = yd(x, y) - dy
+ *               a = rad + 2.0 * x * x * drad + 2.0 * p1 * y + 6.0 * p2 * x
+ *               b = 2.0 * x * y * drad + 2.0 * p1 * x + 2.0 * p2 * y
+ *               d = rad + 2.0 * y * y * drad + 6.0 * p1 * y + 2.0 * p2 * x
+ *               det = a * d - b * b;  x = x - (d * ex - b * ey) / det;  y = y - (a * ey - b * ex) / det
+ *               The point CANNOT BE INVERTED when det > 0.0 is false at any of the 8 iterates (a point beyond the fold of the model, or
+ *               NaN), or when |xd(x, y) - dx| <= 1e-9 or |yd(x, y) - dy| <= 1e-9 is false at the end (normalised units).
+ * The library is built with -ffp-contract=off, so these are computed as written (no fused multiply-add); the division is the device's.
+ *
+ * pam_undistort_keypoints works in place on the decode's buffer, in pam_pose_nms' layout: view v < n_views holds
+ * n = clamp(dev_n_det[v], 0, max_dets) rows (y, x, s)[17] at dev_det + v * det_slots * 51 (det_slots = max_dets, or max_dets + 1 for
+ * ViewGather's view records).  One lane per keypoint, n_views * max_dets * 17 of them.  The camera of view v is row
+ * g = dev_views ? dev_views[v] : v of dev_lens (the caller guarantees that the row exists, as with pam_pose_nms' score grid).  Each (y, x)
+ * of a row below its view's count is normalised (u = x, w = y), inverted and taken back to pixels.  Never touched: the score column; rows
+ * at or beyond the view's count; every row of a camera whose five coefficients are all exactly 0.0 (a rig without distortion stays
+ * bit-identical).  A point that is not finite or cannot be inverted keeps its input coordinates and adds 1 to dev_info[0] (an ordinary
+ * global atomic add; the entry point zeroes dev_info[0..1] on `stream` in front of the launch).  dev_info[1] = the sum of 17 * n over the
+ * views: the points below the counts, pin-hole cameras' and kept ones included.
+ * PAM_E_ARG, before any device call: a NULL pointer (dev_views excepted), n_views < 1, max_dets outside 1..32, det_slots < max_dets.
+ *
+ * pam_set_lens stores a host table of C rows (C = the handle's views) in the handle, on the device, for pam_track_boxes: while a table is
+ * set, each joint's projection (u, w) is normalised with its camera's K, pushed through the forward model and taken back to pixels before
+ * the min / max, so the box lies round the person in the RAW image (a camera of the table whose coefficients are all 0.0 is skipped).
+ * NULL, or a table whose coefficients are all 0.0, removes the table: pam_track_boxes then runs the expressions and gives the bits it
+ * gave before.  The frame step never reads the table: its keypoints are undistorted before they reach it.  Synchronises the device,
+ * except when there is no table to set and none to remove (then no device call is made).
+ * PAM_E_ARG: NULL handle, a value that is not finite, a zero fx or fy in a table that has a non-zero coefficient. */
+int pam_undistort_keypoints(void* stream, int n_views, int max_dets, int det_slots, double* dev_det, const int32_t* dev_n_det,
+                            const int32_t* dev_views, const double* dev_lens, int32_t* dev_info);
+int pam_set_lens(PamHandle* h, const double* lens /* host, C * 10, or NULL */);
+
 /* ---- per-operator entry points (parity tests; host buffers, synchronous) -----------------------------------*/
 /* Camera.projectPoints_parallel, ivclabpose.py:91-98: n poses (17x3) -> (17x2) in (y, x) */
 int pam_op_project(PamHandle* h, int cid, int n, const double* poses3d, double* out_yx);

@@ -102,6 +102,8 @@ _SIGS = {
     'pam_track_boxes': (_I, [_P, _P, _I, _I, _I, _I, C.c_float, C.c_float, C.c_float, _I, _I, _P, _P, _P, _P]),
     'pam_crop_table': (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     'pam_pose_nms': (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, C.c_longlong, C.c_longlong, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
+    'pam_undistort_keypoints': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'pam_set_lens': (_I, [_P, _P]),
     'pam_comm_unique_id': (_I, [_P]),
     'pam_comm_init': (_I, [C.POINTER(_P), _I, _I, _P, _I]),
     'pam_comm_destroy': (_I, [_P]),
@@ -141,6 +143,38 @@ POSE_NMS_MAX = 32                          # rows per view pam_pose_nms takes (o
 # gets these 17 doubles, whatever produced them: a caller with other joints passes its own)
 COCO_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
 OKS_VARS = (COCO_SIGMAS * 2) ** 2
+LENS_WORDS = 10                            # doubles of a camera's row in a lens table: fx, fy, cx, cy, skew, k1, k2, p1, p2, k3
+LENS_ITERS, LENS_TOL = 8, 1e-9             # Newton steps of the inverse and its residual bound, normalised units (include/pam.h)
+
+
+def lens_table(K, dist, always=False):
+    """K (C, 3, 3) upper-triangular, dist (C, 5) (k1, k2, p1, p2, k3) or None -> the (C, 10) float64 table of pam_undistort_keypoints /
+    pam_set_lens, or None when there is nothing to undo (dist None or all zero; always=True: the table of pin-holes then)."""
+    if dist is None and always:
+        dist = np.zeros((len(K), 5))
+    if dist is None:
+        return None
+    K, dist = np.asarray(K, dtype=np.float64), np.asarray(dist, dtype=np.float64)
+    if dist.ndim != 2 or dist.shape != (len(K), 5):
+        raise ValueError('distCoef must be (%d, 5): k1, k2, p1, p2, k3 per camera (got %s)' % (len(K), dist.shape))
+    if not np.any(dist) and not always:
+        return None
+    K = K / K[:, 2:3, 2:3]
+    return np.ascontiguousarray(np.concatenate([np.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2], K[:, 0, 1]], axis=1), dist], axis=1))
+
+
+def check_lens(lens, n_cameras):
+    """A caller's lens table as a contiguous (n_cameras, 10) float64 array; None when it is None or holds no non-zero coefficient."""
+    if lens is None:
+        return None
+    lens = np.ascontiguousarray(lens, dtype=np.float64)
+    if lens.shape != (n_cameras, LENS_WORDS) or not np.all(np.isfinite(lens)):
+        raise ValueError('lens table must be (%d, %d) finite doubles (got %s)' % (n_cameras, LENS_WORDS, lens.shape))
+    if not np.any(lens[:, 5:]):
+        return None
+    if np.any(lens[:, :2] == 0):
+        raise ValueError('lens table: zero focal length')
+    return lens
 
 _lib = None
 
@@ -332,6 +366,12 @@ class Handle(object):
         """While the device int32 at dev_word_ptr is non-zero the frame step skips its frame (record status ``ST_INPUT_VOID``, state
         untouched): the word is raised by the producer of the keypoints (HRNetPose.void_word).  None / 0 removes the guard."""
         self._chk(self.lib.pam_set_input_guard(self._h, C.c_void_p(dev_word_ptr or None)))
+
+    def set_lens(self, lens):
+        """lens: (C, 10) host table (lens_table) or None.  While one is set, track_boxes draws its boxes in the RAW image: every joint's
+        projection goes through its camera's forward model before the min / max (pam_set_lens).  None or all-zero coefficients remove it."""
+        lens = check_lens(lens, self.C)
+        self._chk(self.lib.pam_set_lens(self._h, _ptr(lens)))
 
     def track_boxes(self, stream, frame_id, frame_w, frame_h, boxes, count, ids=None, info=None, scene=0, grow=1.25, pad_px=8.0,
                     min_size_px=8.0, max_gap=3):
@@ -531,3 +571,23 @@ def pose_nms(stream, det, n_det_in, view_of, slot_of, xywh, n_det_out, keep_from
                              C.c_void_p(keep_from.data_ptr()), C.c_void_p(pose_score.data_ptr()))
     if rc != 0:
         raise PamError('pam_pose_nms failed (%d)' % rc)
+
+
+def undistort_keypoints(stream, det, n_det, lens, info, max_dets=None, views=None):
+    """Lens distortion out of every view's decoded poses, in place (pam_undistort_keypoints; the model: include/pam.h).  det (V, det_slots,
+    17, 3) float64 rows (y, x, score), the first max_dets (None: det_slots; at most 32) rows of a view are its slots; n_det (V,) int32;
+    lens (G, 10) float64 device table, read at row views[v] (views: int32 device tensor) or v; info (2,) int32 is written: [0] points left
+    as they were because they could not be inverted, [1] points below the counts.  All contiguous device tensors; asynchronous on
+    ``stream``."""
+    V, det_slots = int(det.shape[0]), int(det.shape[1])
+    max_dets = det_slots if max_dets is None else int(max_dets)
+    if max_dets > POSE_NMS_MAX:
+        raise ValueError('undistort_keypoints: %d slots per view, at most %d' % (max_dets, POSE_NMS_MAX))
+    assert det.is_contiguous() and tuple(det.shape[2:]) == (PAM_J, 3) and str(det.dtype) == 'torch.float64' and n_det.numel() >= V
+    assert lens.is_contiguous() and str(lens.dtype) == 'torch.float64' and lens.dim() == 2 and lens.shape[1] == LENS_WORDS and info.numel() >= 2
+    assert (views is None and lens.shape[0] >= V) or (views is not None and views.numel() >= V)
+    rc = load().pam_undistort_keypoints(C.c_void_p(stream), V, max_dets, det_slots, C.c_void_p(det.data_ptr()), C.c_void_p(n_det.data_ptr()),
+                                        C.c_void_p(views.data_ptr()) if views is not None else None, C.c_void_p(lens.data_ptr()),
+                                        C.c_void_p(info.data_ptr()))
+    if rc != 0:
+        raise PamError('pam_undistort_keypoints failed (%d)' % rc)

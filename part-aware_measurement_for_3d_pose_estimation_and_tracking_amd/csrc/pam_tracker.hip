@@ -7,7 +7,9 @@
 #include <stdlib.h>
 #include <limits.h>
 #include <string>
+#include <cmath>
 #include "pam_device.hpp"
+#include "pam_lens.hpp"
 
 using namespace pam;
 
@@ -899,6 +901,7 @@ struct TrackBoxArgs {
     float grow, pad_px, min_size_px;
     int max_gap, max_det;
     float* boxes; int* count; int* ids; int* info;
+    const double* lens;    // pam_set_lens: C rows of PAM_LENS_WORDS doubles, or nullptr (the pin-hole rig: the boxes of before, bit for bit)
 };
 __global__ __launch_bounds__(TB_BLOCK) void k_track_boxes(TrackBoxArgs A) {
     __shared__ float s_box[64 * PAM_MAX_VIEWS][4];          // pam_create: at most 64 tracks x 32 views
@@ -934,6 +937,15 @@ __global__ __launch_bounds__(TB_BLOCK) void k_track_boxes(TrackBoxArgs A) {
                 if (!(h2 > 0.0)) { ok = false; break; }                              // a joint behind the camera (or NaN): no box in this view
                 double u, w;
                 project_point(P, X[0], X[1], X[2], u, w);
+                if (A.lens) {                                                        // where the joint lies in the RAW image of this camera
+                    const Lens L = lens_row(A.lens, v);
+                    if (!lens_is_pinhole(L)) {
+                        double x, y, xd, yd;
+                        lens_normalise(L, u, w, x, y);
+                        lens_forward(L, x, y, xd, yd);
+                        lens_pixels(L, xd, yd, u, w);
+                    }
+                }
                 if (j == 0) { x0 = x1 = u; y0 = y1 = w; }
                 else { x0 = u < x0 ? u : x0; x1 = u > x1 ? u : x1; y0 = w < y0 ? w : y0; y1 = w > y1 ? w : y1; }
             }
@@ -994,6 +1006,7 @@ struct PamHandle {
     hipStream_t stream = nullptr;
     char* d_op = nullptr; size_t op_bytes = 0;     // staging for the per-operator entry points
     const int* d_guard = nullptr;                  // pam_set_input_guard
+    double* d_lens = nullptr;                      // pam_set_lens: C * PAM_LENS_WORDS doubles while a table is set
     std::string err;
 };
 static std::string g_create_err;
@@ -1075,6 +1088,7 @@ extern "C" int pam_destroy(PamHandle* h) {
     hipSetDevice(h->device);
     hipFree(h->d_prm); hipFree(h->d_P); hipFree(h->d_F); hipFree(h->d_RK); hipFree(h->d_pos);
     hipFree(h->d_state); hipFree(h->d_ws); hipFree(h->d_ndet); hipFree(h->d_det);
+    hipFree(h->d_lens);
     hipFree(h->d_out_i); hipFree(h->d_op);                  // (d_out_d lives in d_out_i's allocation)
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -1113,6 +1127,30 @@ extern "C" int pam_out_layout(const PamHandle* h, PamOutLayout* out) {
 extern "C" int pam_set_input_guard(PamHandle* h, const int32_t* dev_word) {
     if (!h) return PAM_E_ARG;
     h->d_guard = dev_word;
+    return PAM_OK;
+}
+
+// The rig's lens table (pam_lens.hpp), read by k_track_boxes only: NULL, or a table whose every coefficient is exactly zero, removes it.
+extern "C" int pam_set_lens(PamHandle* h, const double* lens) {
+    if (!h) return PAM_E_ARG;
+    const int C = h->d.C;
+    bool any = false;
+    for (int i = 0; lens && i < C * PAM_LENS_WORDS; ++i) {
+        ARGCHK(h, std::isfinite(lens[i]), "non-finite lens table");
+        if (i % PAM_LENS_WORDS >= 5 && lens[i] != 0.0) any = true;
+    }
+    for (int v = 0; lens && any && v < C; ++v)
+        ARGCHK(h, lens[v * PAM_LENS_WORDS] != 0.0 && lens[v * PAM_LENS_WORDS + 1] != 0.0, "zero focal length in the lens table");
+    if (!any && !h->d_lens) return PAM_OK;             // nothing set, nothing to remove: no device call
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipDeviceSynchronize());                 // a k_track_boxes in flight still reads the table of before
+    if (!any) {
+        HIPCHK(h, hipFree(h->d_lens));
+        h->d_lens = nullptr;
+        return PAM_OK;
+    }
+    if (!h->d_lens) HIPCHK(h, hipMalloc(&h->d_lens, sizeof(double) * C * PAM_LENS_WORDS));
+    HIPCHK(h, hipMemcpy(h->d_lens, lens, sizeof(double) * C * PAM_LENS_WORDS, hipMemcpyHostToDevice));
     return PAM_OK;
 }
 
@@ -1155,6 +1193,7 @@ extern "C" int pam_track_boxes(PamHandle* h, void* stream, int scene, int frame_
     A.frame_id = frame_id; A.frame_w = frame_w; A.frame_h = frame_h;
     A.grow = grow; A.pad_px = pad_px; A.min_size_px = min_size_px; A.max_gap = max_gap; A.max_det = max_det;
     A.boxes = dev_boxes; A.count = dev_count; A.ids = dev_ids; A.info = dev_info;
+    A.lens = h->d_lens;
     hipLaunchKernelGGL(k_track_boxes, dim3(1), dim3(TB_BLOCK), 0, (hipStream_t)stream, A);
     HIPCHK(h, hipGetLastError());
     return PAM_OK;

@@ -736,6 +736,22 @@ class HRNetPose(object):
     #                  decode above (it runs after whichever ran).  Off: predict() issues exactly the launches it issued without it.
     _soft_beta, _flip_test, _post_process, _dark, _blur_kernel, shift_heatmap = None, False, False, False, None, True
     pose_nms, oks_thre, in_vis_thre = False, 0.9, 0.2
+    #   lens           (set_lens) the rig's lens table: behind the last decode of a predict() call -- and behind pose_nms, whose OKS areas
+    #                  come from raw-image boxes -- the TRACKER's float64 copy of the keypoints is undistorted in place on the device
+    #                  (pam_undistort_keypoints).  The host keypoints and the dump's dicts stay in raw-image pixels.  None: predict()
+    #                  issues exactly the launches it issued without it.
+    lens, lens_info = None, None
+
+    def set_lens(self, table):
+        """table: (cameras, 10) float64 host rows (_lib.lens_table), view v of a predict() call is camera v; None or all-zero
+        coefficients switch the step off.  ``lens_info`` (device, 2 int32) then holds the last call's [points that could not be
+        inverted and were left as they were, points looked at]."""
+        table = None if table is None else _lib.check_lens(table, len(table))
+        if table is None:
+            self.lens, self.lens_info = None, None
+            return
+        self.lens = torch.from_numpy(table).to(self.device)
+        self.lens_info = torch.zeros(2, dtype=torch.int32, device=self.device)
 
     def _decode_option(name):
         def get(self):
@@ -844,6 +860,10 @@ class HRNetPose(object):
         nms = bool(self.pose_nms)
         if nms and S > _lib.POSE_NMS_MAX:
             raise ValueError('HRNetPose.predict: pose_nms takes at most %d persons per view (got a buffer of %d slots)' % (_lib.POSE_NMS_MAX, S))
+        lens = self.lens
+        if lens is not None and (S > _lib.POSE_NMS_MAX or V != int(lens.shape[0])):
+            raise ValueError('HRNetPose.predict: the lens table is for %d cameras and at most %d persons per view (got %d views, a buffer of '
+                             '%d slots)' % (int(lens.shape[0]), _lib.POSE_NMS_MAX, V, S))
         # (pose_nms: the box scores travel in the same upload, as a (V, S) float32 table behind the frame pointers)
         meta = np.empty(6 * n + V + (V & 1) + 2 * V + (V * S if nms else 0), dtype=np.int32)
         meta[:n] = views; meta[n:2 * n] = slots
@@ -916,6 +936,11 @@ class HRNetPose(object):
                               in_vis_thre=self.in_vis_thre)
                 nms_host[0].copy_(nms_dev[0], non_blocking=True)
                 nms_host[1].copy_(nms_dev[1], non_blocking=True)
+            if lens is not None:
+                # last of all, on the tracker's buffer only (kp, the host's rows, stays raw): the filter above wanted raw-image coordinates,
+                # and a redo decodes again before it comes here, so the in-place step never meets its own output
+                _lib.undistort_keypoints(torch.cuda.current_stream(self.device).cuda_stream, det, nms_dev[0][:V] if nms else n_det, lens,
+                                         self.lens_info)
             # The reference's contract is host lists -- but nothing needs them before the caller looks: the device -> host copy of the
             # keypoints is only ENQUEUED here (pinned buffer, this stream) and the per-person dicts are built at the first access of the
             # dump (DumpResults).  A loop that passes the dump straight on to PersonTrack_Project3DPose waits for the GPU once per frame

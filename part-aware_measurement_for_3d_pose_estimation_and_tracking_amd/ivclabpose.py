@@ -20,18 +20,44 @@ def _cfg(obj, key):
 
 
 class Camera(object):
-    """Calibrated view: P, K, RT (float32), F[other] (float32), RK_INV (float32), position (float64)."""
+    """Calibrated view: P, K, RT (float32), F[other] (float32), RK_INV (float32), position (float64).
+    distCoef (not in the reference, whose lens methods are identity stubs): (k1, k2, p1, p2, k3) of the camera's lens, OpenCV / Panoptic
+    order; None or all zeros = an ideal pin-hole.  P, F and RK_INV describe the IDEAL camera either way: points of the raw image go
+    through ``undistort_points`` before they meet them (on the product path the device does that, pam_undistort_keypoints)."""
 
-    def __init__(self, cid, P, K, RT, F, w=640, h=480):
+    def __init__(self, cid, P, K, RT, F, w=640, h=480, distCoef=None):
         self.cid, self.P, self.K, self.RT, self.F, self.w, self.h = cid, P, K, RT, F, w, h
         self.RK_INV = np.linalg.inv(RT[:, :3]) @ np.linalg.inv(K)
         self.position = np.linalg.inv(np.vstack([RT, [0, 0, 0, 1]]))[:3, 3]
+        self.distCoef, self.lens = None, None
+        if distCoef is not None:
+            from . import _lib
+            self.distCoef = np.asarray(distCoef, dtype=np.float64).reshape(5)
+            table = _lib.lens_table(np.asarray(K)[None], self.distCoef[None])
+            self.lens = table[0] if table is not None else None            # the row of the device table, None for a pin-hole
 
     def undistort(self, im):
-        return im
+        return im                    # images are not resampled: the keypoints are moved instead
+
+    def _rows_xy(self, points2d, fn):
+        pts = np.asarray(points2d, dtype=np.float64)
+        if self.lens is None or pts.size == 0:
+            return points2d
+        out = pts.copy()
+        res = fn(self.lens, pts[..., 0], pts[..., 1])
+        out[..., 0], out[..., 1] = res[0], res[1]
+        return out
 
     def undistort_points(self, points2d):
-        return points2d
+        """rows (x, y[, w]) of the raw image -> the same rows in the ideal pin-hole image (further columns untouched).  8 Newton steps in
+        float64 (lens.inverse: the device's expressions); a point the model cannot invert keeps its coordinates."""
+        from . import lens
+        return self._rows_xy(points2d, lens.undistort_uw)
+
+    def distort_points(self, points2d):
+        """rows (x, y[, w]) of the ideal pin-hole image -> the same rows in the raw image (the closed-form forward model)."""
+        from . import lens
+        return self._rows_xy(points2d, lens.distort_uw)
 
     def projectPoints_parallel(self, points3d):
         """(n,17,3) -> (n,17,2) in (y, x); host NumPy convenience (the device does this inside k_frame)."""
@@ -40,10 +66,16 @@ class Camera(object):
         h = (self.P @ hom.T).T
         return (h[:, :2] / h[:, 2:3])[:, ::-1].reshape(n, j, 2)
 
-    def projectPoints(self, points3d):
+    def projectPoints_undist(self, points3d):
+        """(n, 3) -> (n, 2) in (y, x), no distortion"""
         return self.projectPoints_parallel(np.asarray(points3d, dtype=np.float64)[None])[0]
 
-    projectPoints_undist = projectPoints
+    def projectPoints(self, points3d):
+        """(n, 3) -> (n, 2) in (y, x) with the lens considered: where the points lie in the raw image"""
+        yx = self.projectPoints_undist(points3d)
+        if self.lens is None:
+            return yx
+        return self.distort_points(yx[:, ::-1])[:, ::-1]
 
 
 def fundamental_matrices(K, RT):
@@ -173,9 +205,19 @@ class ivclabpose(object):
         RT = np.asarray(camera_parameter['RT']).astype(np.float32)
         if F is None:
             F = fundamental_matrices(K, RT)
-        self.cameras = [Camera(j, P[j], K[j], RT[j], F[j], w=im_width, h=im_height) for j in range(len(P))]
+        # optional key (not in the reference): 'distCoef' (C, 5), the lens of every camera as Panoptic's calibration files and OpenCV give
+        # it.  The pose network then undistorts the tracker's copy of every decode on the device, the tracker draws its boxes in the raw
+        # image; the host keypoints and the 9-tuple's pts stay in raw-image pixels.
+        dist = camera_parameter.get('distCoef') if hasattr(camera_parameter, 'get') else None
+        from . import _lib
+        self.lens = _lib.lens_table(K, dist)
+        dist = np.asarray(dist, dtype=np.float64) if self.lens is not None else None
+        self.cameras = [Camera(j, P[j], K[j], RT[j], F[j], w=im_width, h=im_height, distCoef=None if dist is None else dist[j])
+                        for j in range(len(P))]
         if self.tracker is not None:
             self.tracker.set_cameras(self.cameras)
+        if self.pose_model is not None:
+            self.pose_model.set_lens(self.lens)
         return self.cameras
 
     def PersonDetect(self, imglist, image_id):
@@ -271,7 +313,12 @@ class ivclabpose(object):
             poses = self._unpack(dump_results)
             boxes = [np.array([it['bbox'] for it in items]) for items in dump_results]
             frames = [(b[0]['data'] if len(b) else []) for b in person_bbox_list]
-            asso_time, update_time, init_time = self.tracker.tracking(frame_id, self.cameras, frames, boxes, poses, build3D)
+            ideal = poses
+            if any(c.lens is not None for c in self.cameras):
+                # the dicts hold raw-image pixels (and pts below is built from them): the tracker gets an undistorted copy
+                from . import lens
+                ideal = [p if c.lens is None else lens.undistort_rows(c.lens, p) for c, p in zip(self.cameras, poses)]
+            asso_time, update_time, init_time = self.tracker.tracking(frame_id, self.cameras, frames, boxes, ideal, build3D)
         camera_ids, pts, person_ids, pts3d, pts3d_joints_views, person3d_ids = [], [], [], [], [], []
         for tr in self.tracker.tracks:
             if not tr.emitted:

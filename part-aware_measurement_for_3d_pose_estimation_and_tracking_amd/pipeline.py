@@ -36,7 +36,7 @@ class FramePipeline(object):
                  rank=0, group=None, use_graph=True, hrnet=True, seed=0, shard='views', overlap_tracker=False, net=None, exchange='torch',
                  pose_streams=1, autotune=True, prewarm=False, width=48, resolution=(384, 288), flip_test=False, shift_heatmap=True,
                  post_process=False, model_name='HRNet', crop_cap=None, detect_every=1, dark=False, blur_kernel=None, pose_nms=False,
-                 oks_thre=0.9, in_vis_thre=0.2):
+                 oks_thre=0.9, in_vis_thre=0.2, lens=None):
         """shard: 'views' -- rank owns whole camera views (pose_step / track_step take view-local inputs); 'crops' -- the
         frame's crops are dealt out evenly over the ranks (pose_step_crops / track_step_crops take global view indices).
         overlap_tracker (either mode): exchange + tracker kernel + fetch of frame t run on their own stream, under the conv
@@ -63,7 +63,18 @@ class FramePipeline(object):
         per view).  ``self.nms_n_det`` (device, one count per view of this rank) is then the n_det_local for track_step -- it replaces
         ``table_n_det`` -- and results() adds rec['pose_nms'] = dict(n_det, keep_from).  Box scores: the detector's, read in place from
         its list, on detector frames; 1.0 on track-box frames; pose_step takes a table.  The pipeline's own setting: a shared `net`
-        keeps its own (HRNetPose.predict's).  Off: every step issues exactly the launches it issued without the option."""
+        keeps its own (HRNetPose.predict's).  Off: every step issues exactly the launches it issued without the option.
+        lens: the rig's (C, 10) float64 lens table (_lib.lens_table; one row per camera, of ALL C views).  Behind the decode of every
+        frame -- and behind pose_nms, whose OKS areas come from raw-image boxes -- this rank's keypoints are undistorted in place on the
+        device (pam_undistort_keypoints; the model: include/pam.h), so view sharding exchanges ideal coordinates; ``undistort_local``
+        does the same for rows a caller placed with write_local.  track_boxes then draws its boxes in the raw image (pam_set_lens).
+        ``lens_info`` (device, 2 int32): [points that could not be inverted and were left as they were, points looked at] of the last
+        launch.  None, or no non-zero coefficient: every step issues exactly the launches it issued without the option."""
+        lens = _lib.check_lens(lens, len(calib_cameras))
+        if lens is not None and shard == 'crops':
+            raise ValueError("lens needs shard='views': crop sharding gathers rows whose view the device-side step cannot name")
+        if lens is not None and max_dets > _lib.POSE_NMS_MAX:
+            raise ValueError('lens takes at most %d slots per view (max_dets=%d)' % (_lib.POSE_NMS_MAX, max_dets))
         if pose_nms and shard == 'crops':
             raise ValueError("pose_nms needs shard='views': crop sharding builds its select index from the host box list, before the filter")
         if pose_nms and max_dets > _lib.POSE_NMS_MAX:
@@ -79,6 +90,11 @@ class FramePipeline(object):
         self.handle = _lib.Handle(self.C, self.params, max_dets=max_dets, max_tracks=max_tracks, n_scenes=1, device=device)
         self.handle.set_cameras(np.stack([c.P for c in calib_cameras]), np.stack([c.F for c in calib_cameras]),
                                 np.stack([c.RK_INV for c in calib_cameras]), np.stack([c.position for c in calib_cameras]))
+        self.lens, self.lens_info = None, None
+        if lens is not None:
+            self.handle.set_lens(lens)
+            self.lens = torch.from_numpy(lens).to(self.device)
+            self.lens_info = torch.zeros(2, dtype=torch.int32, device=self.device)
         # net: an existing HRNetPose to share (weights, packed images, captured graphs) between several pipelines of one process
         self.net = net if net is not None else (HRNetPose(width, 17, None, model_name=model_name, resolution=tuple(resolution), device=device,
                                                           use_graph=use_graph, seed=seed,
@@ -97,6 +113,7 @@ class FramePipeline(object):
         self.gather = ViewGather(self.C, max_dets, world, rank, self.device, group, abi=(self.handle, self.comm) if self.comm else None)
         self.crop_gather = CropGather(self.C, max_dets, world, rank, self.device, group) if shard == 'crops' else None
         self.mine = self.gather.mine
+        self._lens_views = torch.tensor(list(self.mine) or [0], dtype=torch.int32, device=self.device) if lens is not None else None
         # decode target: this rank's views only -- the leading records of the exchange's send buffer, (len(mine), max_dets + 1, 17, 3):
         # slot stride max_dets + 1, the extra row carries the view's detection count (ViewGather)
         self.det_local = self.gather.det_local
@@ -278,6 +295,17 @@ class FramePipeline(object):
                           self.nms_keep_from, self.nms_pose_score, max_dets=self.max_dets, score=score[0], score_strides=score[1],
                           views=score[2], oks_thre=self.oks_thre, in_vis_thre=self.in_vis_thre)
             self._nms_live = True
+        if self.lens is not None:
+            self.undistort_local(self.nms_n_det if self.pose_nms else n_det)
+
+    def undistort_local(self, n_det):
+        """Lens distortion out of this rank's rows, in place in ``self.det_local`` (decode, write_local), behind whatever the current
+        stream holds and in front of track_step: n_det = one int32 device count per view of this rank, what track_step is given.
+        Local view i is camera mine[i] of the lens table.  Nothing is launched when the pipeline has no table."""
+        if self.lens is None or not len(self.mine):
+            return
+        _lib.undistort_keypoints(torch.cuda.current_stream(self.device).cuda_stream, self.det_local, n_det, self.lens, self.lens_info,
+                                 max_dets=self.max_dets, views=self._lens_views)
 
     @contextlib.contextmanager
     def frame(self):
@@ -301,6 +329,8 @@ class FramePipeline(object):
         self._table_info, self._nms_live = None, False
         if self.pose_nms and self.net is not None and n_det is None:
             raise ValueError('pose_step with pose_nms needs n_det: the filter starts from the per-view counts')
+        if self.lens is not None and self.net is not None and n_det is None:
+            raise ValueError('pose_step with a lens table needs n_det: the step undistorts the rows below the per-view counts')
         if int(view_local.numel()) == 0 or self.net is None:
             if after_crop is not None:
                 after_crop()

@@ -31,6 +31,22 @@ def build_model(cfg):
                       conf_threshold=pipe['CONF_THRESHOLD']), pipe['BUILD_3D']
 
 
+def load_calibration(dataset):
+    """DATASET.CALIBRATION_FILE, the reference's {'P', 'K', 'RT'} pickle (/root/reference/src/testmodel.py:29-30; a 'distCoef' it
+    holds is kept).  DATASET.DISTORTION_FILE (optional, not in the reference): a pickle whose 'distCoef' (C, 5) -- (k1, k2, p1, p2, k3)
+    per camera, in FOLDERS_ORDER -- is handed to GetCameraParameters next to them (tools/panoptic_calibration.py writes one)."""
+    with open(os.path.join(dataset.ROOT, dataset.CALIBRATION_FILE), 'rb') as f:
+        camera_parameter = dict(pickle.load(f))
+    lens_file = dataset.get('DISTORTION_FILE')
+    if lens_file:
+        with open(os.path.join(dataset.ROOT, lens_file), 'rb') as f:
+            dist = np.asarray(pickle.load(f)['distCoef'], dtype=np.float64)
+        if dist.shape != (len(camera_parameter['K']), 5):
+            raise ValueError('%s: distCoef is %s, the calibration has %d cameras' % (lens_file, dist.shape, len(camera_parameter['K'])))
+        camera_parameter['distCoef'] = dist
+    return camera_parameter
+
+
 def frame_inputs(model, precomputed, frame_id, imagelist, ahead=None, next_frame=None):
     """person_bbox_list + dump_result_list for one frame -> (pbl, dump, detect seconds, pose seconds, the next frame's detection ticket).
     ahead: this frame's detection, issued one frame ago (PersonDetectAhead); next_frame = (frame_id, imagelist) of the frame after this
@@ -63,8 +79,7 @@ def frame_inputs(model, precomputed, frame_id, imagelist, ahead=None, next_frame
 def test_ivclabpose_PersonTrack_Project3DPose(cfg, inputs, on_frame=None):
     dataset = cfg.DATASET
     os.makedirs(cfg.OUTPUT, exist_ok=True)
-    with open(os.path.join(dataset.ROOT, dataset.CALIBRATION_FILE), 'rb') as f:
-        camera_parameter = pickle.load(f)
+    camera_parameter = load_calibration(dataset)
     model, build3D = build_model(cfg)
     precomputed = {}
     if model.person_detector is None:

@@ -99,6 +99,13 @@ class IterativeTracker(object):
         self.cameras = cameras
         self.handle.set_cameras(np.stack([c.P for c in cameras]), np.stack([c.F for c in cameras]),
                                 np.stack([c.RK_INV for c in cameras]), np.stack([c.position for c in cameras]))
+        # cameras with a lens (Camera(distCoef=)): predict_boxes then draws its boxes in the raw image (pam_set_lens); none = no table
+        rows = [getattr(c, 'lens', None) for c in cameras]
+        if any(r is not None for r in rows):
+            self.handle.set_lens(np.stack([r if r is not None else _lib.lens_table(np.asarray(c.K)[None], None, always=True)[0]
+                                           for r, c in zip(rows, cameras)]))
+        else:
+            self.handle.set_lens(None)
 
     def track_restart(self):
         self.handle.reset()
