@@ -1,5 +1,5 @@
 // The lens model of include/pam.h (Brown-Conrady, OpenCV / Panoptic order k1 k2 p1 p2 k3 on normalised coordinates; K upper-triangular
-// with skew), float64, as device functions: shared by k_undistort_keypoints (pam_lens.hip) and k_track_boxes (pam_tracker.hip), so the
+// with skew), float64, as device functions: shared by k_undistort_keypoints (pam_lens.hip) and k_track_boxes (pam_track_boxes.hip), so the
 // boxes are drawn with the expressions the keypoints were undistorted with.  Built with -ffp-contract=off: every expression is
 // evaluated as written.
 #pragma once

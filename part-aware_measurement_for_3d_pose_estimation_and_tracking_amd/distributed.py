@@ -117,7 +117,7 @@ class ViewGather(object):
         rank's records, rank-major -- identical on every rank; read it through ``rows``.
         void_word: this rank's (1,) int32 device word that is non-zero when the forward that decoded these rows gave up
         (HRNetPose.void_word): it travels in the second double of every record's count row, and the frame kernel of EVERY rank skips the
-        frame when any record carries it (csrc/pam_tracker.hip) -- the replicated trackers stay identical.  With one rank the frame
+        frame when any record carries it (csrc/pam_frame.hip) -- the replicated trackers stay identical.  With one rank the frame
         kernel reads the word itself (pam_set_input_guard)."""
         k = len(self.mine)
         if k:

@@ -2,7 +2,7 @@
 (/root/reference/src/tracking/IterativeTracker.py:34-180) on top of the C ABI (include/pam.h).
 
 All per-frame work -- association, part-aware view filter, DLT, smoothing, motion, hypothesis initialisation, life
-cycle -- runs in one fused HIP kernel launch (csrc/pam_tracker.hip, k_frame); this module only packs detections,
+cycle -- runs in one fused HIP kernel launch (csrc/pam_frame.hip, k_frame); this module only packs detections,
 calls ``pam_frame`` and decodes the output record."""
 import numpy as np
 

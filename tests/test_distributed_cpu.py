@@ -138,7 +138,7 @@ def test_surface_keypoint_gather_world2_gloo():
 
 def _void_worker(rank, world, port, ret):
     """The producer's "these keypoints are void" word through both exchanges: raised on ONE rank it must be seen by every rank -- in every
-    view record's count row (what the frame kernel checks, csrc/pam_tracker.hip) and as CropGather.void_any -- and be gone the frame after
+    view record's count row (what the frame kernel checks, csrc/pam_frame.hip) and as CropGather.void_any -- and be gone the frame after
     it was lowered; and the device-sharing rule decided from identities."""
     from pam.distributed import ranks_share_a_device
     os.environ['MASTER_ADDR'] = '127.0.0.1'
