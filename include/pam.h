@@ -236,6 +236,48 @@ int pam_undistort_keypoints(void* stream, int n_views, int max_dets, int det_slo
                             const int32_t* dev_views, const double* dev_lens, int32_t* dev_info);
 int pam_set_lens(PamHandle* h, const double* lens /* host, C * 10, or NULL */);
 
+/* ---- One-Euro filter on the tracks' 3D output (csrc/pam_one_euro.hip, csrc/pam_one_euro.hpp) ------------------------------------------
+ * replaces: OneEuroFilter.__call__ (/root/reference/src/tracking/OneEuroFilter.py:41-77) as IterTrack.__init__ sets it up per joint and
+ * axis (IterativeTracker.py:225-237: freq 25, mincutoff 0.8, beta 0.4, dcutoff 0.4); the reference's three calls in smooth_3dpose are
+ * commented out (:373-376), so this is an OUTPUT filter: it reads the tracker state and never writes it; the frame step, its record and
+ * every decision stay what they are.  All float64.  One scalar channel with state (n, freq, t_last, x_prev, x_hat, dx_hat) takes sample x
+ * at time t (the class's own expressions, its truthiness test on the time stamps included: a time stamp of 0.0 never updates freq):
+ *   if n > 0 and t_last != 0.0 and t != 0.0:  freq = 1.0 / (t - t_last)
+ *   t_last = t
+ *   alpha(c) = 1.0 / (1.0 + (1.0 / (2 * pi * c)) / (1.0 / freq))              pi = 3.141592653589793
+ *   dx   = 0.0 if n == 0 else (x - x_prev) * freq
+ *   edx  = dx  if n == 0 else alpha(dcutoff) * dx + (1.0 - alpha(dcutoff)) * dx_hat
+ *   cut  = mincutoff + beta * fabs(edx)
+ *   x_hat = x  if n == 0 else alpha(cut) * x + (1.0 - alpha(cut)) * x_hat
+ *   dx_hat = edx;  x_prev = x;  n += 1;  the output is x_hat
+ * The library is built with -ffp-contract=off, so these are computed as written; the division is the device's.
+ * The 51 channels of a track (17 joints x 3 axes) share n, freq and t_last; t = (double)frame_id / cfg.freq, so cfg.freq is the frame rate
+ * and the filter's initial frequency.
+ *
+ * pam_set_one_euro stores the configuration and allocates the zeroed filter state in the handle (per scene and track slot: id, last_frame,
+ * n, freq, t_last, x_prev[51], x_hat[51], dx_hat[51]); setting it again restarts every filter, and so does pam_reset while one is set.
+ * NULL switches the filter off and frees the state.  Synchronises the device.  PAM_E_ARG: NULL handle, a value that is not finite, freq,
+ * mincutoff or dcutoff <= 0 (beta may be 0).
+ *
+ * pam_one_euro (k_one_euro: one workgroup per scene, asynchronous on `stream`) filters the newest pose of every listed track, Tentative
+ * and Confirmed alike, as the frame launches already on `stream` leave the state; it does not look at the input guard.  For the track at
+ * list position i (the record's order) in slot s, with `fresh` = the time of its newest pose equals frame_id:
+ *   - a slot that holds no samples, or whose stored id is not the track's, starts over: n = 0, freq = cfg.freq (a slot reused by a track
+ *     born in the frame its predecessor died);
+ *   - fresh, same id and last_frame == frame_id: the sample has been consumed, the state is left alone -- a second call, or a call after a
+ *     frame that was skipped and re-submitted, changes nothing and writes the same buffers;
+ *   - fresh with frame_id < last_frame (time went back without a pam_reset): starts over, then consumes the sample;
+ *   - fresh otherwise: consumes the sample (one step of every channel) and sets last_frame = frame_id;
+ *   - not fresh: the row is the held x_hat; a track without state (the filter was switched on mid-run) gives its newest pose as it is,
+ *     with samples = 0.
+ * dev_pose: n_scenes * max_tracks * 51 doubles, row i = the 17 x 3 filtered joints of list position i, rows from n_tracks on 0.0; on a
+ * track's first sample the row holds the raw pose's bits.  dev_meta: n_scenes * (2 + 3 * max_tracks) int32, [0] = n_tracks, [1] = fresh
+ * rows (the samples of this frame that are in dev_pose), then per row (id, fresh, samples = n after the call); rows from n_tracks on are
+ * (-1, 0, 0).  PAM_E_STATE without a configuration; PAM_E_ARG, before any device call: a NULL handle or buffer. */
+typedef struct PamOneEuro { double freq, mincutoff, beta, dcutoff; } PamOneEuro;
+int pam_set_one_euro(PamHandle* h, const PamOneEuro* cfg /* host, or NULL = off */);
+int pam_one_euro(PamHandle* h, void* stream, int frame_id, double* dev_pose, int32_t* dev_meta);
+
 /* ---- per-operator entry points (parity tests; host buffers, synchronous) -----------------------------------*/
 /* Camera.projectPoints_parallel, ivclabpose.py:91-98: n poses (17x3) -> (17x2) in (y, x) */
 int pam_op_project(PamHandle* h, int cid, int n, const double* poses3d, double* out_yx);
@@ -273,6 +315,10 @@ int pam_op_velocity(PamHandle* h, int L, const double* hist, float* vel);
 /* Hypothesis.calculate_cost, hypothesis.py:53-68 */
 int pam_op_hyp_cost(PamHandle* h, int n_members, const int32_t* cids, const double* poses, int o_cid,
                     const double* o_pose, double* cost, int32_t* veto);
+/* OneEuroFilter.__call__, OneEuroFilter.py:63-77, through the device function k_one_euro runs: K independent channels (one lane each)
+ * walk the n samples x[i * K + k] at times t[i], every filter new (n = 0, freq = cfg->freq) -> out n*K.  n >= 0, 1 <= K <= 4096, the
+ * configuration as pam_set_one_euro takes it (the handle's own is neither read nor changed). */
+int pam_op_one_euro(PamHandle* h, int n, int K, const double* t, const double* x, const PamOneEuro* cfg, double* out);
 
 /* ---- image side of a1 (HRNetPose.predict pre/post-processing; call site ivclabpose.py:210) ------------------
  * pam_preprocess_crops: n person boxes (x, y, w, h float32, in pixels of frame view_of[i]) cropped from BGR uint8

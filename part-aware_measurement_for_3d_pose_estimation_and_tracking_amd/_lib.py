@@ -28,6 +28,10 @@ class PamParams(C.Structure):
     ]
 
 
+class PamOneEuro(C.Structure):
+    _fields_ = [('freq', C.c_double), ('mincutoff', C.c_double), ('beta', C.c_double), ('dcutoff', C.c_double)]
+
+
 class PamOutLayout(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         'n_views', 'max_dets', 'max_tracks', 'n_scenes', 'int_words', 'dbl_words', 'hdr_words', 'trk_words',
@@ -104,6 +108,9 @@ _SIGS = {
     'pam_pose_nms': (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, C.c_longlong, C.c_longlong, _P, _P, C.c_double, C.c_double, _P, _P, _P]),
     'pam_undistort_keypoints': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
     'pam_set_lens': (_I, [_P, _P]),
+    'pam_set_one_euro': (_I, [_P, C.POINTER(PamOneEuro)]),
+    'pam_one_euro': (_I, [_P, _P, _I, _P, _P]),
+    'pam_op_one_euro': (_I, [_P, _I, _I, _P, _P, C.POINTER(PamOneEuro), _P]),
     'pam_comm_unique_id': (_I, [_P]),
     'pam_comm_init': (_I, [C.POINTER(_P), _I, _I, _P, _I]),
     'pam_comm_destroy': (_I, [_P]),
@@ -145,6 +152,28 @@ COCO_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1
 OKS_VARS = (COCO_SIGMAS * 2) ** 2
 LENS_WORDS = 10                            # doubles of a camera's row in a lens table: fx, fy, cx, cy, skew, k1, k2, p1, p2, k3
 LENS_ITERS, LENS_TOL = 8, 1e-9             # Newton steps of the inverse and its residual bound, normalised units (include/pam.h)
+# the One-Euro filter on the tracks' 3D output (pam_set_one_euro): the values IterTrack.__init__ gives its 3D filters
+# (IterativeTracker.py:225-237); freq is the frame rate, the time of frame f is f / freq
+ONE_EURO_3D = dict(freq=25, mincutoff=0.8, beta=0.4, dcutoff=0.4)
+
+
+def one_euro_config(cfg):
+    """None / False -> None; True -> ONE_EURO_3D; a dict (keys freq, mincutoff, beta, dcutoff in either letter case, missing ones from
+    ONE_EURO_3D) or a PamOneEuro -> a PamOneEuro.  ValueError for an unknown key and for what pam_set_one_euro refuses."""
+    if cfg is None or cfg is False:
+        return None
+    if isinstance(cfg, PamOneEuro):
+        cfg = dict(freq=cfg.freq, mincutoff=cfg.mincutoff, beta=cfg.beta, dcutoff=cfg.dcutoff)
+    v = dict(ONE_EURO_3D)
+    if cfg is not True:
+        for k, x in dict(cfg).items():
+            if str(k).lower() not in v:
+                raise ValueError('one_euro: unknown key %r (freq, mincutoff, beta, dcutoff)' % (k,))
+            v[str(k).lower()] = x
+    v = {k: float(x) for k, x in v.items()}
+    if not all(math.isfinite(x) for x in v.values()) or v['freq'] <= 0 or v['mincutoff'] <= 0 or v['dcutoff'] <= 0:
+        raise ValueError('one_euro: values must be finite, freq, mincutoff and dcutoff > 0 (got %r)' % (v,))
+    return PamOneEuro(v['freq'], v['mincutoff'], v['beta'], v['dcutoff'])
 
 
 def lens_table(K, dist, always=False):
@@ -307,7 +336,8 @@ class Handle(object):
             raise PamError('pam_create failed (%d): %s' % (rc, self.lib.pam_last_error(None).decode()))
         self.layout = PamOutLayout()
         self._chk(self.lib.pam_out_layout(self._h, C.byref(self.layout)))
-        self.C, self.max_dets, self.max_tracks, self.n_scenes = n_views, max_dets, max_tracks, n_scenes
+        self.C, self.max_dets, self.max_tracks, self.n_scenes, self.device = n_views, max_dets, max_tracks, n_scenes, device
+        self.one_euro_cfg = None
         self.out_i = np.zeros((n_scenes, self.layout.int_words), dtype=np.int32)
         self.out_d = np.zeros((n_scenes, self.layout.dbl_words), dtype=np.float64)
 
@@ -372,6 +402,39 @@ class Handle(object):
         projection goes through its camera's forward model before the min / max (pam_set_lens).  None or all-zero coefficients remove it."""
         lens = check_lens(lens, self.C)
         self._chk(self.lib.pam_set_lens(self._h, _ptr(lens)))
+
+    def set_one_euro(self, cfg):
+        """cfg: what one_euro_config takes (None: off, the state is freed).  Setting it (again) starts every filter over; so does reset()
+        while one is set (pam_set_one_euro)."""
+        c = one_euro_config(cfg)
+        self._chk(self.lib.pam_set_one_euro(self._h, C.byref(c) if c is not None else None))
+        self.one_euro_cfg = c
+
+    def one_euro_buffers(self, pinned=False):
+        """(pose, meta) for one_euro: (n_scenes, max_tracks, 17, 3) float64 and (n_scenes, 2 + 3 * max_tracks) int32 torch tensors, on the
+        handle's device or (pinned=True) in pinned host memory."""
+        import torch
+        kw = dict(device='cuda:%d' % self.device) if not pinned else {}
+        pose = torch.zeros((self.n_scenes, self.max_tracks, PAM_J, 3), dtype=torch.float64, **kw)
+        meta = torch.zeros((self.n_scenes, 2 + 3 * self.max_tracks), dtype=torch.int32, **kw)
+        return (pose.pin_memory(), meta.pin_memory()) if pinned else (pose, meta)
+
+    def one_euro(self, stream, frame_id, pose, meta):
+        """The tracks' newest 3D poses through their One-Euro filters, behind whatever is queued on ``stream`` (pam_one_euro; the rules:
+        include/pam.h).  pose / meta: the device tensors of one_euro_buffers.  Reads the tracker state, never writes it."""
+        assert pose.is_contiguous() and meta.is_contiguous() and pose.numel() == self.n_scenes * self.max_tracks * PAM_J * 3
+        assert meta.numel() == self.n_scenes * (2 + 3 * self.max_tracks) and str(pose.dtype) == 'torch.float64' and str(meta.dtype) == 'torch.int32'
+        self._chk(self.lib.pam_one_euro(self._h, C.c_void_p(stream), int(frame_id), C.c_void_p(pose.data_ptr()), C.c_void_p(meta.data_ptr())))
+
+    @staticmethod
+    def decode_one_euro(pose, meta, scene=0):
+        """host copies of one_euro's buffers (shaped as one_euro_buffers gives them) -> dict(n_tracks, n_fresh, ids, fresh, samples (n_tracks,), pose (n_tracks, 17, 3)), rows in
+        the record's order."""
+        m, p = np.asarray(meta)[scene], np.asarray(pose)[scene]
+        n = int(m[0])
+        rows = m[2:2 + 3 * n].reshape(n, 3)
+        return dict(n_tracks=n, n_fresh=int(m[1]), ids=rows[:, 0].copy(), fresh=rows[:, 1].astype(bool), samples=rows[:, 2].copy(),
+                    pose=p[:n].copy())
 
     def track_boxes(self, stream, frame_id, frame_w, frame_h, boxes, count, ids=None, info=None, scene=0, grow=1.25, pad_px=8.0,
                     min_size_px=8.0, max_gap=3):
@@ -513,6 +576,16 @@ class Handle(object):
             hs = np.zeros((1, PAM_J, 3))
         r = np.ascontiguousarray(raw, dtype=np.float64); out = np.zeros((PAM_J, 3))
         self._chk(self.lib.pam_op_smooth(self._h, L, _ptr(hs), _ptr(r), _ptr(out)))
+        return out
+
+    def op_one_euro(self, t, x, cfg=True):
+        """t (n,) time stamps, x (n, K) samples -> (n, K): every column through a new One-Euro filter of configuration cfg
+        (one_euro_config), by the device function k_one_euro runs."""
+        tt = np.ascontiguousarray(t, dtype=np.float64); xx = np.ascontiguousarray(x, dtype=np.float64)
+        assert xx.ndim == 2 and tt.shape == (xx.shape[0],)
+        out = np.zeros_like(xx)
+        c = one_euro_config(cfg)
+        self._chk(self.lib.pam_op_one_euro(self._h, xx.shape[0], xx.shape[1], _ptr(tt), _ptr(xx), C.byref(c), _ptr(out)))
         return out
 
     def op_velocity(self, hist):

@@ -78,7 +78,7 @@ extern "C" int pam_destroy(PamHandle* h) {
     hipSetDevice(h->device);
     hipFree(h->d_prm); hipFree(h->d_P); hipFree(h->d_F); hipFree(h->d_RK); hipFree(h->d_pos);
     hipFree(h->d_state); hipFree(h->d_ws); hipFree(h->d_ndet); hipFree(h->d_det);
-    hipFree(h->d_lens);
+    hipFree(h->d_lens); hipFree(h->d_oe);
     hipFree(h->d_out_i); hipFree(h->d_op);                  // (d_out_d lives in d_out_i's allocation)
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -103,6 +103,7 @@ extern "C" int pam_reset(PamHandle* h) {
     HIPCHK(h, hipSetDevice(h->device));
     HIPCHK(h, hipDeviceSynchronize());
     HIPCHK(h, hipMemset(h->d_state, 0, h->state_stride * h->d.S));
+    if (h->d_oe) HIPCHK(h, hipMemset(h->d_oe, 0, h->oe_stride * h->d.S));      // pam_set_one_euro: every filter starts over with its tracks
     return PAM_OK;
 }
 

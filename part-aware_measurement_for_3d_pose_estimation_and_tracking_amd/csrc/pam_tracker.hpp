@@ -1,6 +1,7 @@
-// What the tracker's sources share (pam_tracker.hip, pam_frame.hip, pam_track_boxes.hip, pam_track_ops.hip, pam_comm.hip): the layout of
-// the device-resident scene state and of the per-frame scratch, the handle behind the C ABI of include/pam.h, the host-side error
-// macros and the staging helper of the per-operator entry points.  No kernels, and nothing with external linkage.
+// What the tracker's sources share (pam_tracker.hip, pam_frame.hip, pam_track_boxes.hip, pam_track_ops.hip, pam_comm.hip,
+// pam_one_euro.hip): the layout of the device-resident scene state and of the per-frame scratch, the handle behind the C ABI of
+// include/pam.h, the host-side error macros and the staging helper of the per-operator entry points.  No kernels, and nothing with
+// external linkage.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -155,6 +156,8 @@ struct PamHandle {
     char* d_op = nullptr; size_t op_bytes = 0;     // staging for the per-operator entry points
     const int* d_guard = nullptr;                  // pam_set_input_guard
     double* d_lens = nullptr;                      // pam_set_lens: C * PAM_LENS_WORDS doubles while a table is set
+    char* d_oe = nullptr; size_t oe_stride = 0;    // pam_set_one_euro: the filter state of every scene (pam_one_euro.hip) while a
+    PamOneEuro oe{};                               // configuration is set, and that configuration
     std::string err;
 };
 

@@ -19,6 +19,16 @@ def _cfg(obj, key):
     return obj[key] if isinstance(obj, dict) else getattr(obj, key)
 
 
+def one_euro_from_matcher(m):
+    """The optional block ONE_EURO {FREQ, MINCUTOFF, BETA, DCUTOFF} of a PERSON_MATCHERS.ITERATIVE block (not in the reference's YAMLs,
+    whose filters are built with fixed values and never called) -> the dict IterativeTracker(one_euro=) takes, keys in lower case, a
+    missing key left to its default (_lib.ONE_EURO_3D); None when the block is absent."""
+    blk = m.get('ONE_EURO') if isinstance(m, dict) else getattr(m, 'ONE_EURO', None)
+    if blk is None or blk is False:
+        return None
+    return {} if blk is True else {str(k).lower(): v for k, v in dict(blk).items()}
+
+
 class Camera(object):
     """Calibrated view: P, K, RT (float32), F[other] (float32), RK_INV (float32), position (float64).
     distCoef (not in the reference, whose lens methods are identity stubs): (k1, k2, p1, p2, k3) of the camera's lens, OpenCV / Panoptic
@@ -109,6 +119,7 @@ class ivclabpose(object):
         self.device = device
         self.cameras = None
         self.pose_model = None
+        self.pts3d_filtered = None
         # optional keys of the detector's block (not in the reference's YAMLs; absent = the detector on every frame): DETECT_EVERY = K runs
         # the detector on every K-th frame and takes the boxes of the frames in between from the tracks (PersonBoxesFromTracks);
         # TRACK_BOX_GROW / TRACK_BOX_PAD = that box rule's growth and pad in pixels
@@ -193,7 +204,10 @@ class ivclabpose(object):
                              ('lambda_a', 'LAMBDA_A'), ('lambda_t', 'LAMBDA_T'), ('sigma', 'SIGMA'),
                              ('arm_sigma', 'ARM_SIGMA')):
                 a[dst] = _cfg(m, src)
-            self.tracker = IterativeTracker(a, max_dets=max_dets, max_tracks=max_tracks, device=device)
+            # optional block ONE_EURO: the tracks' 3D output also through One-Euro filters on the device (pam_one_euro) -> pts3d_filtered
+            oe = one_euro_from_matcher(m)
+            self.tracker = IterativeTracker(a, max_dets=max_dets, max_tracks=max_tracks, device=device,
+                                            one_euro=oe if oe is None else dict(oe))
             if self.pose_model is not None:
                 self.tracker.set_input_guard(self.pose_model)      # keypoints of a forward whose gate timed out never reach the tracker state
             print("Person Matcher : ", _cfg(m, 'NAME'))
@@ -320,15 +334,20 @@ class ivclabpose(object):
                 ideal = [p if c.lens is None else lens.undistort_rows(c.lens, p) for c, p in zip(self.cameras, poses)]
             asso_time, update_time, init_time = self.tracker.tracking(frame_id, self.cameras, frames, boxes, ideal, build3D)
         camera_ids, pts, person_ids, pts3d, pts3d_joints_views, person3d_ids = [], [], [], [], [], []
+        # ONE_EURO: the emitted tracks' filtered poses, aligned with the returned pts3d ((n, 3, 17)); None without the block
+        filtered = [] if self.tracker.one_euro is not None else None
         for tr in self.tracker.tracks:
             if not tr.emitted:
                 continue
             pts3d.append(tr.pose3d.T)
+            if filtered is not None:
+                filtered.append(tr.pose3d_filtered.T)
             pts3d_joints_views.append(tr.joints_views)
             person3d_ids.append(tr.track_id)
             person_ids.append([tr.track_id] * len(tr.order))
             cams = [cid for cid in tr.order if tr.time2d[cid] == frame_id]
             camera_ids.append(cams)
             pts.append([poses[cid][tr.matched_det[cid]] for cid in cams])
+        self.pts3d_filtered = np.array(filtered) if filtered is not None else None
         return (np.array(camera_ids, dtype='object'), np.array(pts, dtype='object'), person_ids, np.array(pts3d),
                 pts3d_joints_views, np.array(person3d_ids), asso_time, update_time, init_time)

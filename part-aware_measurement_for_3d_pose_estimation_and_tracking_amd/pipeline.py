@@ -36,7 +36,7 @@ class FramePipeline(object):
                  rank=0, group=None, use_graph=True, hrnet=True, seed=0, shard='views', overlap_tracker=False, net=None, exchange='torch',
                  pose_streams=1, autotune=True, prewarm=False, width=48, resolution=(384, 288), flip_test=False, shift_heatmap=True,
                  post_process=False, model_name='HRNet', crop_cap=None, detect_every=1, dark=False, blur_kernel=None, pose_nms=False,
-                 oks_thre=0.9, in_vis_thre=0.2, lens=None):
+                 oks_thre=0.9, in_vis_thre=0.2, lens=None, one_euro=None):
         """shard: 'views' -- rank owns whole camera views (pose_step / track_step take view-local inputs); 'crops' -- the
         frame's crops are dealt out evenly over the ranks (pose_step_crops / track_step_crops take global view indices).
         overlap_tracker (either mode): exchange + tracker kernel + fetch of frame t run on their own stream, under the conv
@@ -69,7 +69,12 @@ class FramePipeline(object):
         device (pam_undistort_keypoints; the model: include/pam.h), so view sharding exchanges ideal coordinates; ``undistort_local``
         does the same for rows a caller placed with write_local.  track_boxes then draws its boxes in the raw image (pam_set_lens).
         ``lens_info`` (device, 2 int32): [points that could not be inverted and were left as they were, points looked at] of the last
-        launch.  None, or no non-zero coefficient: every step issues exactly the launches it issued without the option."""
+        launch.  None, or no non-zero coefficient: every step issues exactly the launches it issued without the option.
+        one_euro: True (_lib.ONE_EURO_3D) or dict(freq, mincutoff, beta, dcutoff): behind the frame kernel of every track_step /
+        track_step_crops, on the tracker's stream, the tracks' newest 3D poses go through One-Euro filters on the device (pam_one_euro;
+        the rules: include/pam.h) and results() adds rec['pose3d_filtered'] ((n_tracks, 17, 3), the record's order) and
+        rec['filter_meta'] = dict(n_fresh, ids, fresh, samples).  An output filter: the tracker state and the record are what they are
+        without it; with view sharding every rank filters its own replica, nothing is exchanged.  None: the launches of before."""
         lens = _lib.check_lens(lens, len(calib_cameras))
         if lens is not None and shard == 'crops':
             raise ValueError("lens needs shard='views': crop sharding gathers rows whose view the device-side step cannot name")
@@ -90,6 +95,10 @@ class FramePipeline(object):
         self.handle = _lib.Handle(self.C, self.params, max_dets=max_dets, max_tracks=max_tracks, n_scenes=1, device=device)
         self.handle.set_cameras(np.stack([c.P for c in calib_cameras]), np.stack([c.F for c in calib_cameras]),
                                 np.stack([c.RK_INV for c in calib_cameras]), np.stack([c.position for c in calib_cameras]))
+        self.one_euro, self._oe_fetched = _lib.one_euro_config(one_euro), False
+        if self.one_euro is not None:
+            self.handle.set_one_euro(self.one_euro)
+            self._oe_dev, self._oe_host = self.handle.one_euro_buffers(), self.handle.one_euro_buffers(pinned=True)
         self.lens, self.lens_info = None, None
         if lens is not None:
             self.handle.set_lens(lens)
@@ -357,6 +366,7 @@ class FramePipeline(object):
         def issue(st):
             recv = self.gather.exchange(n_det_local, self.net.void_word if self.net is not None else None)
             self.handle.frame_dev_views(st, frame_id, recv.data_ptr(), self.gather.rows.data_ptr())
+            self._one_euro_step(st, frame_id, fetch)
             if fetch:
                 self.handle.fetch(st, self.out_i.numpy(), self.out_d.numpy())
                 self._ct_fetched = self._table_info is not None
@@ -378,6 +388,17 @@ class FramePipeline(object):
                 self._ev_slot_read[k] = self._ev_slot_read[k] or torch.cuda.Event()
                 self._ev_slot_read[k].record(self.track_stream)
         self._track_pending = True
+
+    def _one_euro_step(self, st, frame_id, fetch):
+        """one_euro: the filter launch behind the frame kernel that was just issued on stream ``st`` (the torch stream that is current
+        there), and with ``fetch`` its two buffers on their way to pinned host memory, in front of the record's copy."""
+        if self.one_euro is None:
+            return
+        pose, meta = self._oe_dev
+        self.handle.one_euro(st, frame_id, pose, meta)
+        self._oe_fetched = bool(fetch)
+        if fetch:
+            self._oe_host[0].copy_(pose, non_blocking=True); self._oe_host[1].copy_(meta, non_blocking=True)
 
     # -- person boxes that never visit the host ------------------------------------------------------------------------------
     def reset(self):
@@ -508,6 +529,7 @@ class FramePipeline(object):
             det = self.crop_gather.gather(select, vw)
             st = self.stream_ptr()
             self.handle.frame_dev(st, frame_id, n_det.data_ptr(), det.data_ptr())
+            self._one_euro_step(st, frame_id, fetch)
             if fetch:
                 self.handle.fetch(st, self.out_i.numpy(), self.out_d.numpy())
             return
@@ -517,6 +539,7 @@ class FramePipeline(object):
             det = self.crop_gather.gather(select, vw)
             st = self.track_stream.cuda_stream
             self.handle.frame_dev(st, frame_id, n_det.data_ptr(), det.data_ptr())
+            self._one_euro_step(st, frame_id, fetch)
             if fetch:
                 self.handle.fetch(st, self.out_i.numpy(), self.out_d.numpy())
             self.ev_track.record(self.track_stream)
@@ -543,6 +566,12 @@ class FramePipeline(object):
         if strict and (rec['status'] | rec['status_sticky']) != 0:
             raise _lib.PamError('tracker status 0x%x on frame %d, 0x%x over the run (1 track slots, 2 hypothesis slots, 4 infeasible '
                                 'assignment, 8 clamped detection count)' % (rec['status'], rec['frame_id'], rec['status_sticky']))
+        if self._oe_fetched:
+            f = _lib.Handle.decode_one_euro(self._oe_host[0].numpy(), self._oe_host[1].numpy(), 0)
+            if f['n_tracks'] != rec['n_tracks'] or f['ids'].tolist() != [t['track_id'] for t in rec['tracks']]:
+                raise _lib.PamError('the One-Euro rows do not follow the record (ids %s)' % (f['ids'].tolist(),))
+            rec['pose3d_filtered'] = f['pose']
+            rec['filter_meta'] = dict(n_fresh=f['n_fresh'], ids=f['ids'], fresh=f['fresh'], samples=f['samples'])
         if self._ct_fetched:
             w = self._ct_host.numpy()
             rec['crop_table'] = dict(rows=int(w[0]), wanted=int(w[1]), status=int(w[2]))

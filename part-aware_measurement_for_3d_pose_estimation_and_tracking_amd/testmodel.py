@@ -124,6 +124,9 @@ def test_ivclabpose_PersonTrack_Project3DPose(cfg, inputs, on_frame=None):
                                                               person_index=pid, points_color_palette='gist_rainbow',
                                                               skeleton_color_palette='tab20', points_palette_samples=17,
                                                               confidence_threshold=0.0)
+            if getattr(model, 'pts3d_filtered', None) is not None:                              # ONE_EURO: the filtered 3D poses, re-projected
+                from pam.visualization import draw_tracks
+                imagelist = draw_tracks(imagelist, model.cameras, model.tracker.tracks)
             if cfg.get('SAVE_IMAGE'):
                 from PIL import Image
                 store = os.path.join(cfg.OUTPUT, dataset.TEST_DATASET, 'Images')

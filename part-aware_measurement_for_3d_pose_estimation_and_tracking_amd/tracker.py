@@ -36,6 +36,11 @@ class TrackView(object):
         self.last_time = rec['last_time']
         self.pose3d = rec['pose3d']
         self.velocity_3d = rec['velocity']
+        # IterativeTracker(one_euro=...): the pose through the track's One-Euro filters (17, 3), whether this frame's sample is in it, and
+        # the samples the filters have taken; None without the option
+        self.pose3d_filtered = rec.get('pose3d_filtered')
+        self.filter_fresh = rec.get('filter_fresh')
+        self.filter_samples = rec.get('filter_samples')
 
     def is_confirmed(self):
         return self.state == TrackState.Confirmed
@@ -52,9 +57,13 @@ class TrackView(object):
 
 
 class IterativeTracker(object):
-    def __init__(self, args, n_views=None, max_dets=16, max_tracks=32, max_hyps=0, device=0):
+    def __init__(self, args, n_views=None, max_dets=16, max_tracks=32, max_hyps=0, device=0, one_euro=None):
         """args: the reference's iter_args (attribute access) -- conf_threshold, epi_threshold, init_threshold,
-        joint_threshold, num_joints, init_method, n_init, max_age, alpha2d, lambda_a, lambda_t, sigma, arm_sigma."""
+        joint_threshold, num_joints, init_method, n_init, max_age, alpha2d, lambda_a, lambda_t, sigma, arm_sigma.
+        one_euro: True (``_lib.ONE_EURO_3D``, the values IterTrack.__init__ gives its 3D filters) or a dict(freq, mincutoff, beta,
+        dcutoff): every track's output pose also goes through One-Euro filters on the device (pam_one_euro, one launch behind the frame
+        step) and TrackView gains pose3d_filtered / filter_fresh / filter_samples.  An output filter: the tracker's state, its record
+        and its decisions are the same with and without it.  None: the calls of before."""
         self.args = args
         assert int(args.num_joints) == NUM_JOINTS, 'the path is specialised for 17 COCO joints (ivclabpose.py:96)'
         assert args.init_method == 'GD', "only INIT_METHOD 'GD' exists in the reference (IterativeTracker.py:52)"
@@ -69,6 +78,7 @@ class IterativeTracker(object):
         self.tracks = []
         self.last = None
         self._guard = None           # set_input_guard: the pose network whose void word the frame kernel reads
+        self.one_euro = _lib.one_euro_config(one_euro)
         if n_views is not None:
             self._open(n_views)
 
@@ -83,6 +93,10 @@ class IterativeTracker(object):
         self._rec_keep, self._rec_i, self._rec_d = self.handle.pinned_record()
         if self._guard is not None:
             self.handle.set_input_guard(self._guard.void_word.data_ptr())
+        if self.one_euro is not None:
+            self.handle.set_one_euro(self.one_euro)
+            self._oe_dev = self.handle.one_euro_buffers()
+            self._oe_host = self.handle.one_euro_buffers(pinned=True)
 
     def set_input_guard(self, net):
         """net: the HRNetPose whose decode feeds this tracker (None removes the guard).  While its ``void_word`` is raised -- a device-side
@@ -144,6 +158,7 @@ class IterativeTracker(object):
                 self._det[0, v, :n] = dets
         self.handle.frame(frame_id, self._ndet, self._det)
         self.last = self.handle.decode(0)
+        self._filter_host(frame_id)
         if self.last['status'] & _lib.ST_INPUT_VOID:
             # host keypoints are valid by construction (DumpResults re-ran a void forward before handing them out); the word was left
             # raised by a forward nobody consumed: lower it and apply the frame
@@ -152,9 +167,41 @@ class IterativeTracker(object):
             self._guard.check_void(); self._guard.clear_void()
             self.handle.frame(frame_id, self._ndet, self._det)
             self.last = self.handle.decode(0)
+            self._filter_host(frame_id)
         self.tracks = [TrackView(r, self.cameras, detections_list) for r in self.last['tracks']]
         c = self.last['clocks']
         return float(c[1] - c[0]), float(c[2] - c[1]), float(c[3] - c[2])
+
+    # -- the One-Euro filter behind the frame step (one_euro=) -------------------------------------------------------------------------
+    def _filter_issue(self, stream, frame_id):
+        """pam_one_euro behind the frame step on ``stream`` and its two buffers on their way to pinned host memory, in front of the
+        caller's host wait.  The launch is idempotent per frame (include/pam.h), so it may follow every attempt of a retried frame."""
+        (pose, meta), (hp, hm) = self._oe_dev, self._oe_host
+        self.handle.one_euro(stream, frame_id, pose, meta)
+        hp.copy_(pose, non_blocking=True); hm.copy_(meta, non_blocking=True)
+
+    def _filter_attach(self):
+        """The fetched filter rows into the decoded record's tracks (same order: both follow the state's list)."""
+        if self.one_euro is None or (self.last['status'] & _lib.ST_INPUT_VOID):        # (a void frame's record lists no tracks)
+            return
+        f = _lib.Handle.decode_one_euro(self._oe_host[0].numpy(), self._oe_host[1].numpy(), 0)
+        self.last['one_euro'] = f
+        if f['n_tracks'] != self.last['n_tracks'] or any(int(i) != r['track_id'] for i, r in zip(f['ids'], self.last['tracks'])):
+            raise _lib.PamError('the One-Euro rows do not follow the record (ids %s)' % (f['ids'].tolist(),))
+        for k, r in enumerate(self.last['tracks']):
+            r['pose3d_filtered'], r['filter_fresh'], r['filter_samples'] = f['pose'][k], bool(f['fresh'][k]), int(f['samples'][k])
+
+    def _filter_host(self, frame_id):
+        """tracking()'s form: the step was synchronous on the handle's own stream; the filter follows on the current stream, with a wait
+        of its own."""
+        if self.one_euro is None:
+            return
+        import torch
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream().cuda_stream
+            self._filter_issue(st, frame_id)
+            self.handle.sync(st)
+        self._filter_attach()
 
     def tracking_dev(self, frame_id, camera_list, dev_n_det, dev_det, build3D='SVD', on_void=None):
         """The same step on detections that are already on the device: dev_n_det (views,) int32, dev_det (views, max_dets, 17, 3)
@@ -171,9 +218,12 @@ class IterativeTracker(object):
         for attempt in (0, 1):
             st = torch.cuda.current_stream(dev_det.device).cuda_stream
             self.handle.frame_dev(st, frame_id, dev_n_det.data_ptr(), dev_det.data_ptr())
+            if self.one_euro is not None:
+                self._filter_issue(st, frame_id)
             self.handle.fetch(st, oi, od)
             self.handle.sync(st)
             self.last = self.handle.decode(0, oi, od)
+            self._filter_attach()
             # on_void: the keypoints' producer re-runs its forward into the same device buffers (DumpResults.redo_if_void) -- the frame
             # kernel skipped the frame (state untouched), so the second attempt is the frame's first application
             if not (self.last['status'] & _lib.ST_INPUT_VOID) or attempt == 1 or on_void is None or not on_void():

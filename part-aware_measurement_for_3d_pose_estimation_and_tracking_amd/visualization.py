@@ -1,7 +1,9 @@
 """2D overlay of the tracked poses: the ``joints_dict`` / ``draw_points_and_skeleton`` pair that the
 reference's demo driver imports from the absent ``HRPose.misc.visualization`` (/root/reference/src/testmodel.py:34,72-75).
 Pure host code (NumPy + PIL; OpenCV is not a dependency here).  Points are rows (y, x, confidence) like the 2D poses
-``PersonTrack_Project3DPose`` returns; images are H x W x 3 uint8 BGR arrays and a new array is returned."""
+``PersonTrack_Project3DPose`` returns; images are H x W x 3 uint8 BGR arrays and a new array is returned.
+``draw_tracks`` overlays the tracks' 3D poses instead, re-projected into every view: the One-Euro filtered pose of a track that has one
+(IterativeTracker(one_euro=...), ``TrackView.pose3d_filtered``), else its raw one."""
 import colorsys
 
 import numpy as np
@@ -45,3 +47,28 @@ def draw_points_and_skeleton(image, points, skeleton, points_color_palette='tab2
         if c > confidence_threshold:
             draw.ellipse([x - radius, y - radius, x + radius, y + radius], fill=pt_colors[j % len(pt_colors)])
     return np.asarray(im)[..., ::-1].copy()
+
+
+def track_pose3d(track):
+    """The 3D pose (17, 3) an overlay shows for a TrackView: the filtered one when the track has one, else ``pose3d``."""
+    f = getattr(track, 'pose3d_filtered', None)
+    return np.asarray(track.pose3d if f is None else f, dtype=np.float64)
+
+
+def draw_tracks(imagelist, cameras, tracks, skeleton=None, emitted_only=True, **style):
+    """Every (emitted) track's 3D pose (``track_pose3d``) re-projected into every view with ``Camera.projectPoints`` and drawn with
+    ``draw_points_and_skeleton`` (colour by track id) -> a new list of images.  Joints behind a camera are not drawn."""
+    skeleton = joints_dict()['coco']['skeleton'] if skeleton is None else skeleton
+    kw = dict(points_color_palette='gist_rainbow', skeleton_color_palette='tab20', points_palette_samples=17, confidence_threshold=0.0)
+    kw.update(style)
+    out = list(imagelist)
+    for tr in tracks:
+        if emitted_only and not getattr(tr, 'emitted', True):
+            continue
+        X = track_pose3d(tr)
+        for v, cam in enumerate(cameras):
+            depth = np.asarray(cam.P, dtype=np.float64)[2] @ np.concatenate([X, np.ones((len(X), 1))], axis=1).T
+            yx = np.asarray(cam.projectPoints(X), dtype=np.float64)
+            rows = np.concatenate([np.where(depth[:, None] > 0, yx, 0.0), (depth[:, None] > 0).astype(np.float64)], axis=1)
+            out[v] = draw_points_and_skeleton(out[v], rows, skeleton, person_index=tr.track_id, **kw)
+    return out
