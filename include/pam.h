@@ -730,6 +730,88 @@ int pam_maxpool_nhwc_bf16(void* stream, const void* in, void* out, int N, int H,
 int pam_spp_concat_nhwc_bf16(void* stream, const void* in, void* out, int N, int H, int W, int C, int s1, int s2, int s3);
 int pam_spp_concat_slab_nhwc_bf16(void* stream, const void* in, void* out, int N, int H, int W, int C, int s1, int s2, int s3, int slab);
 
+/* ---- baseline JPEG frames decoded on the device behind a host entropy pass (csrc/pam_jpeg_entropy.hpp, csrc/pam_jpeg.hip; the
+ * reference decodes with one cv2.imread per camera per frame on the main thread, dataset.py:36-45).  The host does the serial half --
+ * header parse and Huffman decode into quantised coefficients -- and the device the parallel half: dequantisation, inverse DCT, chroma
+ * upsampling, colour conversion and the store as BGR uint8 (H, W, 3), cv2.imread's layout.  The bytes are those of libjpeg's default
+ * decode (slow-integer DCT, fancy upsampling), i.e. of PIL.Image.open(..).convert('RGB') with the channels flipped.
+ *
+ * Files taken: SOF0 (baseline), 8-bit samples, Huffman coding, ONE interleaved scan, 8-bit quantisation tables; one component, or three
+ * YCbCr components with chroma 1x1 and luma 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0); byte stuffing, FF fill bytes in front of markers,
+ * restart intervals (DRI, RST0-7); APPn / COM skipped, bytes behind the scan's end ignored.  Everything else is reported in
+ * PamJpegInfo.unsupported and left to another decoder; it is not an error. */
+#define PAM_JPEG_U_NOT_JPEG 1    /* no SOI */
+#define PAM_JPEG_U_PROGRESSIVE 2 /* SOF2 */
+#define PAM_JPEG_U_ARITHMETIC 3  /* SOF9-11, 13-15, DAC */
+#define PAM_JPEG_U_SOF 4         /* SOF1 (extended sequential), lossless and differential frames */
+#define PAM_JPEG_U_PRECISION 5   /* samples of other than 8 bits */
+#define PAM_JPEG_U_QUANT16 6     /* a 16-bit quantisation table */
+#define PAM_JPEG_U_COMPONENTS 7  /* neither one nor three components (CMYK / YCCK) */
+#define PAM_JPEG_U_COLORSPACE 8  /* three components that are not YCbCr: Adobe APP14 with a transform other than 1, or ids R, G, B without JFIF */
+#define PAM_JPEG_U_SAMPLING 9    /* sampling factors other than the three above (4:4:0, 4:1:1, subsampled luma, ...) */
+#define PAM_JPEG_U_SCAN 10       /* the first scan does not hold all components in frame order with Ss = 0, Se = 63, Ah = Al = 0 */
+#define PAM_JPEG_U_DNL 11        /* zero height / a DNL marker */
+
+/* What the header of a file says, and where the entropy pass puts its coefficients.  Component c's blocks start at word coef_offset[c]
+ * of the coefficient buffer: blocks_h[c] rows of blocks_w[c] blocks, row-major, 64 int16 each in natural (row-major, de-zigzagged)
+ * order, QUANTISED (as coded; the device multiplies by quant[c]).  blocks_w[c] = mcu_w * h_samp[c], blocks_h[c] = mcu_h * v_samp[c]:
+ * the padding blocks of partial MCUs are included.  coef_words = 64 * all blocks; the component planes the device writes take
+ * coef_words BYTES (one uint8 per coefficient; component c's plane at byte coef_offset[c], blocks_w[c] * 8 bytes per row). */
+typedef struct PamJpegInfo {
+    int32_t width, height, n_comp;
+    int32_t unsupported;         /* 0 = taken, else PAM_JPEG_U_*: the fields behind what the parser had read by then are zero */
+    int32_t h_samp[3], v_samp[3];
+    int32_t mcu_w, mcu_h;        /* MCUs per row, MCU rows */
+    int32_t blocks_w[3], blocks_h[3];
+    int32_t restart_interval;    /* MCUs between RSTn markers, 0 = none */
+    int32_t reserved;
+    int64_t coef_offset[3];      /* int16 words */
+    int64_t coef_words;
+    uint16_t quant[3][64];       /* per component, natural order */
+} PamJpegInfo;
+
+/* pam_jpeg_probe: SOI through SOS of the n bytes at data -> *info.  PAM_OK with info->unsupported = 0 or a reason; PAM_E_ARG for a
+ * header that is cut short or corrupt (*info is then not to be used).
+ * pam_jpeg_entropy: the scan of a file the probe took -> coef[0 .. info->coef_words), zeros where nothing is coded.  PAM_E_ARG when
+ * coef_words < info->coef_words, when *info does not belong to the file, and for a stream that is cut short or corrupt (an undefined
+ * code, a run that leaves its block, a missing or wrong restart marker): what decoded until then is in coef.
+ * Neither has a handle, global state or a HIP call: any number of threads may run them at once.  Neither reads outside data[0 .. n) or
+ * writes outside coef[0 .. coef_words), whatever the bytes are. */
+int pam_jpeg_probe(const uint8_t* data, size_t n, PamJpegInfo* info);
+int pam_jpeg_entropy(const uint8_t* data, size_t n, const PamJpegInfo* info, int16_t* coef, size_t coef_words);
+
+/* One image of a reconstruction.  dev_coef: info.coef_words int16 as the entropy pass wrote them; dev_quant: n_comp * 64 uint16
+ * (info.quant); dev_planes: info.coef_words bytes of scratch (written in full, never read before written); dev_out: height * width * 3
+ * bytes, B, G, R per pixel.  dev_coef, dev_quant and dev_planes are 16-byte aligned, dev_out 4-byte aligned.  h_samp, v_samp: the luma
+ * sampling factors (1, 1 for one component); the block counts follow from these five integers as PamJpegInfo states them. */
+typedef struct PamJpegImage {
+    const int16_t* dev_coef;
+    const uint16_t* dev_quant;
+    uint8_t* dev_planes;
+    uint8_t* dev_out;
+    int32_t width, height, n_comp, h_samp, v_samp, reserved;
+} PamJpegImage;
+
+/* pam_jpeg_reconstruct: n_img (1 .. PAM_MAX_VIEWS) images of any mix of sizes and samplings in ONE launch pair on `stream`; images is a
+ * host array, copied into the kernel arguments.  Every byte of every dev_out is written, nothing outside it.  PAM_E_ARG, before anything
+ * is launched, for a null or misaligned pointer, a size outside 1 .. 65535, and a component count or sampling outside the list above.
+ *
+ * k_jpeg_idct, per 8x8 block: v = coef * quant, then one 1-D pass down the columns with s = 11 and one along the rows with s = 18, then
+ * + 128, clamped to 0 .. 255.  All int32 (wrapping), >> arithmetic.  The 1-D pass on x0 .. x7:
+ *   z1 = (x2 + x6) * 4433;  t2 = z1 - x6 * 15137;  t3 = z1 + x2 * 6270;  t0 = (x0 + x4) << 13;  t1 = (x0 - x4) << 13
+ *   t10 = t0 + t3;  t13 = t0 - t3;  t11 = t1 + t2;  t12 = t1 - t2;  a0 = x7;  a1 = x5;  a2 = x3;  a3 = x1
+ *   z1 = a0 + a3;  z2 = a1 + a2;  z3 = a0 + a2;  z4 = a1 + a3;  z5 = (z3 + z4) * 9633
+ *   a0 *= 2446;  a1 *= 16819;  a2 *= 25172;  a3 *= 12299;  z1 *= -7373;  z2 *= -20995;  z3 = z3 * -16069 + z5;  z4 = z4 * -3196 + z5
+ *   a0 += z1 + z3;  a1 += z2 + z4;  a2 += z2 + z3;  a3 += z1 + z4
+ *   out = [t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3], each (v + (1 << (s - 1))) >> s
+ * k_jpeg_color, per output pixel, with w = ceil(W / 2), h = ceil(H / 2) the TRUE subsampled extents and neighbours clamped to them:
+ *   2x1:  out[2i] = (3 p[i] + p[i-1] + 1) >> 2,  out[2i+1] = (3 p[i] + p[i+1] + 2) >> 2
+ *   2x2:  s[i] = 3 p[r][i] + p[r'][i], r' the row above (even output row) or below (odd);  out[2i] = (3 s[i] + s[i-1] + 8) >> 4,
+ *         out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4
+ *   cb -= 128, cr -= 128;  R = Y + ((91881 cr + 32768) >> 16);  G = Y + ((-22554 cb - 46802 cr + 32768) >> 16);
+ *   B = Y + ((116130 cb + 32768) >> 16), clamped to 0 .. 255; one component: B = G = R = Y. */
+int pam_jpeg_reconstruct(void* stream, int n_img, const PamJpegImage* images);
+
 #ifdef __cplusplus
 }
 #endif

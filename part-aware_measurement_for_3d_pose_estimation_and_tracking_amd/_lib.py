@@ -38,6 +38,21 @@ class PamOutLayout(C.Structure):
         'off_order', 'off_matched', 'off_time2d', 'off_nviews', 'dbl_hdr_words', 'dbl_trk_words')]
 
 
+class PamJpegInfo(C.Structure):
+    """What pam_jpeg_probe reads from a file's header (include/pam.h)."""
+    _fields_ = [('width', C.c_int32), ('height', C.c_int32), ('n_comp', C.c_int32), ('unsupported', C.c_int32),
+                ('h_samp', C.c_int32 * 3), ('v_samp', C.c_int32 * 3), ('mcu_w', C.c_int32), ('mcu_h', C.c_int32),
+                ('blocks_w', C.c_int32 * 3), ('blocks_h', C.c_int32 * 3), ('restart_interval', C.c_int32), ('reserved', C.c_int32),
+                ('coef_offset', C.c_int64 * 3), ('coef_words', C.c_int64), ('quant', (C.c_uint16 * 64) * 3)]
+
+
+class PamJpegImage(C.Structure):
+    """One image of a pam_jpeg_reconstruct call: four device pointers and what fixes the layout."""
+    _fields_ = [('dev_coef', C.c_void_p), ('dev_quant', C.c_void_p), ('dev_planes', C.c_void_p), ('dev_out', C.c_void_p),
+                ('width', C.c_int32), ('height', C.c_int32), ('n_comp', C.c_int32), ('h_samp', C.c_int32), ('v_samp', C.c_int32),
+                ('reserved', C.c_int32)]
+
+
 # every symbol include/pam.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _I = C.c_int
@@ -136,6 +151,9 @@ _SIGS = {
     'pam_maxpool_nhwc_bf16': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I]),
     'pam_spp_concat_nhwc_bf16': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
     'pam_spp_concat_slab_nhwc_bf16': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I]),
+    'pam_jpeg_probe': (_I, [_P, C.c_size_t, C.POINTER(PamJpegInfo)]),
+    'pam_jpeg_entropy': (_I, [_P, C.c_size_t, C.POINTER(PamJpegInfo), _P, C.c_size_t]),
+    'pam_jpeg_reconstruct': (_I, [_P, _I, C.POINTER(PamJpegImage)]),
 }
 EXPORTS = tuple(_SIGS)
 YOLO_MAX_CAND = 1024        # PAM_YOLO_MAX_CAND in include/pam.h
@@ -155,6 +173,12 @@ LENS_ITERS, LENS_TOL = 8, 1e-9             # Newton steps of the inverse and its
 # the One-Euro filter on the tracks' 3D output (pam_set_one_euro): the values IterTrack.__init__ gives its 3D filters
 # (IterativeTracker.py:225-237); freq is the frame rate, the time of frame f is f / freq
 ONE_EURO_3D = dict(freq=25, mincutoff=0.8, beta=0.4, dcutoff=0.4)
+JPEG_MAX_IMAGES = 32                       # images of one pam_jpeg_reconstruct call (PAM_MAX_VIEWS)
+# PamJpegInfo.unsupported: why pam_jpeg_probe leaves a file to another decoder (PAM_JPEG_U_* in include/pam.h)
+JPEG_UNSUPPORTED = {1: 'not a JPEG', 2: 'progressive', 3: 'arithmetic coding', 4: 'SOF1 / lossless / differential frame',
+                    5: 'sample precision other than 8 bits', 6: '16-bit quantisation table', 7: 'neither one nor three components',
+                    8: 'three components that are not YCbCr', 9: 'sampling other than 4:4:4, 4:2:2, 4:2:0', 10: 'not one interleaved scan',
+                    11: 'zero height / DNL'}
 
 
 def one_euro_config(cfg):

@@ -91,11 +91,13 @@ def test_ivclabpose_PersonTrack_Project3DPose(cfg, inputs, on_frame=None):
     # images are decoded a few frames ahead on worker threads; with a GPU pipeline behind them (detector or pose network) they are
     # uploaded from pinned memory on a copy stream and arrive as CUDA tensors (LOADER_DEVICE: false keeps them NumPy arrays, which
     # the overlay needs anyway).  DETECT_AHEAD (default on): frame t + 1's person detection is issued before frame t's pose network.
+    # DEVICE_JPEG (optional key, default off): the workers run only the Huffman pass of a baseline JPEG and the device rebuilds the
+    # frame (pam.ingest.FrameLoader(device_decode=True)); a file that path does not take goes through Pillow as before.
     draw = bool(cfg.get('VISUALIZATION') or cfg.get('SAVE_IMAGE'))
     on_gpu = (model.person_detector is not None or model.pose_model is not None) and not draw and bool(dataset.get('LOADER_DEVICE', True))
     look_ahead = model.person_detector is not None and bool(dataset.get('DETECT_AHEAD', True))
     loader = FrameLoader(dataset.TEST_DATASET, inputs, indices=range(start, end), workers=int(dataset.get('LOADER_THREADS', 8)),
-                         device=(model.device if on_gpu else None))
+                         device=(model.device if on_gpu else None), device_decode=bool(dataset.get('DEVICE_JPEG', False)))
     it = iter(loader)
     cur = next(it, None)
     ahead = None
