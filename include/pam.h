@@ -812,6 +812,109 @@ typedef struct PamJpegImage {
  *   B = Y + ((116130 cb + 32768) >> 16), clamped to 0 .. 255; one component: B = G = R = Y. */
 int pam_jpeg_reconstruct(void* stream, int n_img, const PamJpegImage* images);
 
+/* ---- baseline JPEG frames ENCODED behind the device (csrc/pam_jpeg_fwd.hip, csrc/pam_jpeg_encode.hpp; the reference saves its annotated
+ * frames with one cv2.imwrite per camera per frame on the main thread, testmodel.py:76-80).  The mirror image of the decode: the device does
+ * the parallel half -- colour conversion, chroma downsampling, forward DCT, quantisation -- into the coefficient layout PamJpegInfo
+ * describes, and the host the serial half, the Huffman pass and the file's headers.  The arithmetic is libjpeg's default encoder (slow-
+ * integer DCT, standard Huffman tables, JFIF header), so at quality 75 and 4:2:0 the file is byte for byte what
+ * PIL.Image.fromarray(rgb).save(path) writes from the same pixels.  Three components; luma sampling 1x1, 2x1 or 2x2, chroma 1x1. */
+
+/* One image of a forward pass.  dev_bgr: height * width * 3 bytes, B, G, R per pixel, any alignment; dev_quant: 3 * 64 uint16, per
+ * component in natural order (pam_jpeg_quality_tables writes them); dev_coef: the int16 buffer of PamJpegInfo's layout for these five
+ * integers (64 * (mw hs mh vs + 2 mw mh) words with mw = ceil(width / (8 hs)), mh = ceil(height / (8 vs))), written IN FULL: the padding
+ * blocks of partial MCUs as zeros, so the buffer can go to pam_jpeg_reconstruct as it is.  dev_quant and dev_coef are 16-byte aligned. */
+typedef struct PamJpegFwdImage {
+    const uint8_t* dev_bgr;
+    const uint16_t* dev_quant;
+    int16_t* dev_coef;
+    int32_t width, height, h_samp, v_samp;
+} PamJpegFwdImage;
+
+/* pam_jpeg_forward: n_img (1 .. PAM_MAX_VIEWS) images of any mix of sizes and samplings in ONE launch on `stream`; images is a host array,
+ * copied into the kernel arguments.  PAM_E_ARG, before anything is launched, for a null or misaligned pointer, a size outside 1 .. 65535,
+ * a sampling outside the three above.  The quantisation tables are device memory and not looked at: the kernel takes a zero as 1.
+ *
+ * Per component c (h_c, v_c its sampling, h_max x v_max the luma's): wb = ceil(ceil(W h_c / h_max) / 8) real blocks per row, hb likewise;
+ * the other blocks of the layout are zeros.  Samples of a real block, all int32, >> arithmetic:
+ *   Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16
+ *   Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16;  Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16
+ *   not subsampled: sample (y, x) is pixel (min(y, H - 1), min(x, W - 1)).
+ *   subsampled chroma: sample (y, x) with y' = min(y, ceil(H / v_max) - 1) averages the pixels (min(v_max y' + dy, H - 1),
+ *   min(h_max x + dx, W - 1)):  2x2: (p00 + p01 + p10 + p11 + bias) >> 2, bias 1 for even x, 2 for odd;  2x1: (p0 + p1 + bias) >> 1,
+ *   bias 0 for even x, 1 for odd.
+ * Forward DCT on sample - 128, along the rows first, then down the columns, with the constants of the inverse pass above.  On d0 .. d7:
+ *   t0..t3 = d0+d7, d1+d6, d2+d5, d3+d4;  t7..t4 = d0-d7, d1-d6, d2-d5, d3-d4;  t10 = t0+t3; t13 = t0-t3; t11 = t1+t2; t12 = t1-t2
+ *   rows: o0 = (t10+t11) << 2, o4 = (t10-t11) << 2;  columns: o0 = (t10+t11+2) >> 2, o4 = (t10-t11+2) >> 2
+ *   z1 = (t12+t13) * 4433;  o2 = z1 + t13 * 6270;  o6 = z1 - t12 * 15137
+ *   z1 = t4+t7; z2 = t5+t6; z3 = t4+t6; z4 = t5+t7; z5 = (z3+z4) * 9633
+ *   t4 *= 2446; t5 *= 16819; t6 *= 25172; t7 *= 12299; z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5
+ *   o7 = t4+z1+z3; o5 = t5+z2+z4; o3 = t6+z2+z3; o1 = t7+z1+z4;  o1, o2, o3, o5, o6, o7: (v + (1 << (s - 1))) >> s, s = 11 rows, 15 columns
+ * Quantisation of c with qv = 8 quant: sign(c) * ((|c| + (qv >> 1)) / qv), the division truncating. */
+int pam_jpeg_forward(void* stream, int n_img, const PamJpegFwdImage* images);
+
+/* What the entropy encoder needs besides the coefficients.  quality 1 .. 100: the tables of pam_jpeg_quality_tables (quant is ignored);
+ * quality 0: quant[0] for the luma and quant[1] for both chroma components, natural order, every entry 1 .. 255. */
+typedef struct PamJpegEncodeParams {
+    int32_t width, height, h_samp, v_samp;
+    int32_t quality, reserved;
+    uint16_t quant[2][64];
+} PamJpegEncodeParams;
+
+/* pam_jpeg_quality_tables: libjpeg's tables for a quality of 1 .. 100 -> tables[0] (luma), tables[1] (chroma), natural order: the tables
+ * of Annex K of the standard, each entry (base * scale + 50) / 100 clamped to 1 .. 255 with scale = 5000 / quality below 50, else
+ * 200 - 2 quality.  PAM_E_ARG: a null pointer, a quality outside 1 .. 100.
+ * pam_jpeg_encode_bound: *bytes = a capacity that pam_jpeg_encode never exceeds for an image of this size and sampling, whatever the
+ * coefficients: 625 header and trailer bytes + 420 for every coded block.  PAM_E_ARG: a null pointer, a size outside 1 .. 65535, a
+ * sampling outside the three above.
+ * pam_jpeg_encode: coef[0 .. coef_words) in PamJpegInfo's layout (as pam_jpeg_forward or pam_jpeg_entropy wrote them) -> a complete file
+ * in out[0 .. *out_bytes), *out_bytes <= capacity.  SOI; APP0 (JFIF 1.01, no units, density 1 x 1, no thumbnail); two DQT segments in
+ * zigzag order; SOF0 (ids 1, 2, 3; luma h << 4 | v, chroma 0x11; tables 0, 1, 1); four DHT segments DC0, AC0, DC1, AC1 with the tables of
+ * Annex K.3 - K.6; SOS; one MCU-interleaved scan (DC difference category + value bits, AC run/size with ZRL and EOB, FF stuffed with 00,
+ * the last byte padded with one-bits); EOI.  The padding blocks of partial MCUs are NOT read: each is coded as all-zero AC with the DC of
+ * the block coded just before it.
+ * PAM_E_ARG, with out[capacity ..) untouched whatever was written below it: a null pointer, what pam_jpeg_encode_bound refuses,
+ * coef_words below the layout's, a quality outside 0 .. 100 or a table entry outside 1 .. 255 at quality 0, a capacity the file does not
+ * fit in, and a coefficient the standard tables have no code for (a DC difference beyond 11 bits, an AC value beyond 10).
+ * None of the three has a handle, global state, an allocation or a HIP call: any number of threads may run them at once. */
+int pam_jpeg_quality_tables(int quality, uint16_t* tables);
+int pam_jpeg_encode_bound(int width, int height, int h_samp, int v_samp, size_t* bytes);
+int pam_jpeg_encode(const int16_t* coef, size_t coef_words, const PamJpegEncodeParams* params, uint8_t* out, size_t capacity, size_t* out_bytes);
+
+/* ---- the overlay of the tracked skeletons drawn on the device (csrc/pam_overlay.hip; the host form is visualization.
+ * draw_points_and_skeleton, which the reference's demo loop calls once per person and view, testmodel.py:70-75).  This is the project's
+ * own rasteriser, defined in integers so that it can be restated exactly (tests/overlay_ref.py); it is not PIL's.
+ *
+ * A primitive is a capsule: every pixel within hw of the segment A - B, in units of 1/8 pixel (the host quantises a coordinate v to
+ * floor(8 v + 0.5) and drops what is not finite or beyond 2^18 in magnitude).  A joint's disc is the capsule with A = B and hw = 8 r.
+ * Pixel (px, py) has its centre at P = (8 px, 8 py).  With d = B - A, p = P - A, t = p . d, all int64:
+ *   t <= 0:      inside iff |p|^2 <= hw^2
+ *   t >= d . d:  inside iff |P - B|^2 <= hw^2
+ *   else:        inside iff |cross(p, d)| < 2^31 and cross^2 <= hw^2 (d . d)
+ * Of all primitives of its view that cover a pixel, the LAST in table order gives the pixel its colour; a pixel none covers is not
+ * written. */
+typedef struct PamOverlayPrim {
+    int32_t ax, ay, bx, by;      /* 1/8 pixel, |.| <= 2^18 */
+    int32_t hw;                  /* 1/8 pixel, 0 .. 2^12 */
+    uint32_t bgr;                /* B | G << 8 | R << 16 */
+    int32_t reserved[2];
+} PamOverlayPrim;
+
+/* One view of a draw: its frame, BGR uint8 (height, width, 3), drawn in place, and its primitives prim_first .. prim_first + prim_count
+ * of the table, in painter's order. */
+typedef struct PamOverlayView {
+    uint8_t* dev_bgr;
+    int32_t width, height;
+    int32_t prim_first, prim_count;
+} PamOverlayView;
+
+/* pam_overlay_draw: n_views (1 .. PAM_MAX_VIEWS) views of any mix of sizes in ONE launch on `stream`; views is a host array, copied
+ * into the kernel arguments; dev_prims: n_prims primitives in device memory, 16-byte aligned (may be null when n_prims is 0: nothing is
+ * launched).  One workgroup per 64 x 16 pixel tile: it culls its view's primitives against the tile by their bounding boxes into LDS
+ * and leaves when none is left.  A primitive whose coordinates or hw are outside the ranges above is not drawn.  PAM_E_ARG, before
+ * anything is launched: a null views or frame pointer, n_views outside 1 .. 32, a size outside 1 .. 65535, a range of primitives that
+ * leaves the table. */
+int pam_overlay_draw(void* stream, int n_views, const PamOverlayView* views, const PamOverlayPrim* dev_prims, int n_prims);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,29 @@ class PamJpegImage(C.Structure):
                 ('reserved', C.c_int32)]
 
 
+class PamJpegFwdImage(C.Structure):
+    """One image of a pam_jpeg_forward call: the BGR frame, the three quantisation tables, the coefficient buffer it fills."""
+    _fields_ = [('dev_bgr', C.c_void_p), ('dev_quant', C.c_void_p), ('dev_coef', C.c_void_p),
+                ('width', C.c_int32), ('height', C.c_int32), ('h_samp', C.c_int32), ('v_samp', C.c_int32)]
+
+
+class PamJpegEncodeParams(C.Structure):
+    """What pam_jpeg_encode needs besides the coefficients; quality 0 = the tables in ``quant`` (luma, chroma; natural order)."""
+    _fields_ = [('width', C.c_int32), ('height', C.c_int32), ('h_samp', C.c_int32), ('v_samp', C.c_int32),
+                ('quality', C.c_int32), ('reserved', C.c_int32), ('quant', (C.c_uint16 * 64) * 2)]
+
+
+class PamOverlayPrim(C.Structure):
+    """One capsule of the overlay table, coordinates and half-width in 1/8 pixel (a joint's disc has a == b)."""
+    _fields_ = [('ax', C.c_int32), ('ay', C.c_int32), ('bx', C.c_int32), ('by', C.c_int32), ('hw', C.c_int32), ('bgr', C.c_uint32),
+                ('reserved', C.c_int32 * 2)]
+
+
+class PamOverlayView(C.Structure):
+    """One view of a pam_overlay_draw call: its frame and its range of the primitive table."""
+    _fields_ = [('dev_bgr', C.c_void_p), ('width', C.c_int32), ('height', C.c_int32), ('prim_first', C.c_int32), ('prim_count', C.c_int32)]
+
+
 # every symbol include/pam.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _I = C.c_int
@@ -154,6 +177,11 @@ _SIGS = {
     'pam_jpeg_probe': (_I, [_P, C.c_size_t, C.POINTER(PamJpegInfo)]),
     'pam_jpeg_entropy': (_I, [_P, C.c_size_t, C.POINTER(PamJpegInfo), _P, C.c_size_t]),
     'pam_jpeg_reconstruct': (_I, [_P, _I, C.POINTER(PamJpegImage)]),
+    'pam_jpeg_forward': (_I, [_P, _I, C.POINTER(PamJpegFwdImage)]),
+    'pam_jpeg_quality_tables': (_I, [_I, _P]),
+    'pam_jpeg_encode_bound': (_I, [_I, _I, _I, _I, C.POINTER(C.c_size_t)]),
+    'pam_jpeg_encode': (_I, [_P, C.c_size_t, C.POINTER(PamJpegEncodeParams), _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    'pam_overlay_draw': (_I, [_P, _I, C.POINTER(PamOverlayView), _P, _I]),
 }
 EXPORTS = tuple(_SIGS)
 YOLO_MAX_CAND = 1024        # PAM_YOLO_MAX_CAND in include/pam.h
@@ -173,7 +201,8 @@ LENS_ITERS, LENS_TOL = 8, 1e-9             # Newton steps of the inverse and its
 # the One-Euro filter on the tracks' 3D output (pam_set_one_euro): the values IterTrack.__init__ gives its 3D filters
 # (IterativeTracker.py:225-237); freq is the frame rate, the time of frame f is f / freq
 ONE_EURO_3D = dict(freq=25, mincutoff=0.8, beta=0.4, dcutoff=0.4)
-JPEG_MAX_IMAGES = 32                       # images of one pam_jpeg_reconstruct call (PAM_MAX_VIEWS)
+JPEG_MAX_IMAGES = 32                       # images of one pam_jpeg_reconstruct / pam_jpeg_forward call (PAM_MAX_VIEWS)
+OVERLAY_MAX_VIEWS = 32                     # views of one pam_overlay_draw call (PAM_MAX_VIEWS)
 # PamJpegInfo.unsupported: why pam_jpeg_probe leaves a file to another decoder (PAM_JPEG_U_* in include/pam.h)
 JPEG_UNSUPPORTED = {1: 'not a JPEG', 2: 'progressive', 3: 'arithmetic coding', 4: 'SOF1 / lossless / differential frame',
                     5: 'sample precision other than 8 bits', 6: '16-bit quantisation table', 7: 'neither one nor three components',

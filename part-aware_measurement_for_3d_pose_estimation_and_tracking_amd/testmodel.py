@@ -76,6 +76,29 @@ def frame_inputs(model, precomputed, frame_id, imagelist, ahead=None, next_frame
     return pbl, dump, dt_det, time.time() - t0, nxt
 
 
+def _device_available():
+    import torch
+    return torch.cuda.is_available()
+
+
+def overlay_on_device(model, imagelist, result):
+    """The overlay of one frame drawn on the device: the 2D poses of PersonTrack_Project3DPose's result per view, in the order the host
+    path draws them, then (ONE_EURO) the re-projected filtered tracks.  Frames that are still NumPy arrays are uploaded first.
+    -> the list of CUDA frames, drawn in place."""
+    import torch
+    from pam.visualization import draw_overlay_device, draw_tracks
+    device = torch.device('cuda', model.device) if isinstance(model.device, int) else torch.device(model.device)
+    frames = [im if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im)).to(device) for im in imagelist]
+    people = [[] for _ in frames]
+    for cids, poses_2d, pids in zip(result[0], result[1], result[2]):
+        for cid, pose_2d, pid in zip(cids, poses_2d, pids):
+            people[cid].append((pose_2d, pid))
+    draw_overlay_device(frames, people)
+    if getattr(model, 'pts3d_filtered', None) is not None:
+        draw_tracks(frames, model.cameras, model.tracker.tracks, device=True)
+    return frames
+
+
 def test_ivclabpose_PersonTrack_Project3DPose(cfg, inputs, on_frame=None):
     dataset = cfg.DATASET
     os.makedirs(cfg.OUTPUT, exist_ok=True)
@@ -90,17 +113,23 @@ def test_ivclabpose_PersonTrack_Project3DPose(cfg, inputs, on_frame=None):
     n_views = len(dataset.FOLDERS_ORDER)
     # images are decoded a few frames ahead on worker threads; with a GPU pipeline behind them (detector or pose network) they are
     # uploaded from pinned memory on a copy stream and arrive as CUDA tensors (LOADER_DEVICE: false keeps them NumPy arrays, which
-    # the overlay needs anyway).  DETECT_AHEAD (default on): frame t + 1's person detection is issued before frame t's pose network.
+    # the host overlay needs anyway).  DETECT_AHEAD (default on): frame t + 1's person detection is issued before frame t's pose network.
     # DEVICE_JPEG (optional key, default off): the workers run only the Huffman pass of a baseline JPEG and the device rebuilds the
     # frame (pam.ingest.FrameLoader(device_decode=True)); a file that path does not take goes through Pillow as before.
+    # DEVICE_OVERLAY (optional key, default off; needs a device): VISUALIZATION / SAVE_IMAGE no longer switch the device loader off --
+    # the overlay is drawn into the CUDA frames by pam_overlay_draw (pam.visualization.draw_overlay_device) and SAVE_IMAGE encodes them
+    # behind the device (pam.egress.FrameWriter: pam_jpeg_forward, then the Huffman pass and the file on worker threads).
     draw = bool(cfg.get('VISUALIZATION') or cfg.get('SAVE_IMAGE'))
-    on_gpu = (model.person_detector is not None or model.pose_model is not None) and not draw and bool(dataset.get('LOADER_DEVICE', True))
+    device_overlay = draw and bool(dataset.get('DEVICE_OVERLAY', False)) and _device_available()
+    on_gpu = ((model.person_detector is not None or model.pose_model is not None) and (not draw or device_overlay)
+              and bool(dataset.get('LOADER_DEVICE', True)))
     look_ahead = model.person_detector is not None and bool(dataset.get('DETECT_AHEAD', True))
     loader = FrameLoader(dataset.TEST_DATASET, inputs, indices=range(start, end), workers=int(dataset.get('LOADER_THREADS', 8)),
                          device=(model.device if on_gpu else None), device_decode=bool(dataset.get('DEVICE_JPEG', False)))
     it = iter(loader)
     cur = next(it, None)
     ahead = None
+    writer = store = None
     i = -1
     while cur is not None:
         i += 1
@@ -117,7 +146,16 @@ def test_ivclabpose_PersonTrack_Project3DPose(cfg, inputs, on_frame=None):
             t0 = time.time()
             result = model.PersonTrack_Project3DPose(frame_id=frame_id, person_bbox_list=pbl, dump_results=dump, build3D=build3D)
             dt_track = time.time() - t0
-        if result is not None and (cfg.get('VISUALIZATION') or cfg.get('SAVE_IMAGE')):      # testmodel.py:70-75 overlay
+        if result is not None and device_overlay:
+            if writer is None and cfg.get('SAVE_IMAGE'):
+                from pam.egress import FrameWriter
+                store = os.path.join(cfg.OUTPUT, dataset.TEST_DATASET, 'Images')
+                os.makedirs(store, exist_ok=True)
+                writer = FrameWriter(model.device, workers=int(dataset.get('WRITER_THREADS', 4)), depth=int(dataset.get('WRITER_DEPTH', 4)))
+            imagelist = overlay_on_device(model, imagelist, result)
+            if cfg.get('SAVE_IMAGE'):
+                writer.submit(frame_id, imagelist, [os.path.join(store, '%s_%d.jpg' % (frame_id, cid)) for cid in range(len(imagelist))])
+        elif result is not None and (cfg.get('VISUALIZATION') or cfg.get('SAVE_IMAGE')):      # testmodel.py:70-75 overlay
             from pam.visualization import joints_dict, draw_points_and_skeleton
             camera_ids, pts, person_ids = result[0], result[1], result[2]
             for cids, poses_2d, pids in zip(camera_ids, pts, person_ids):
@@ -142,6 +180,8 @@ def test_ivclabpose_PersonTrack_Project3DPose(cfg, inputs, on_frame=None):
             t_pose += dt_pose
             t_track += dt_track
     loader.close()
+    if writer is not None:
+        writer.close()
     n = max(1, end - start - 10)
     print("Person Detect Processing time (s/f): %f" % (t_det / n))
     print("Pose Detect Processing time (s/f): %f" % (t_pose / n))

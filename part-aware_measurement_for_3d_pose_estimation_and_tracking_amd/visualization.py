@@ -3,8 +3,14 @@ reference's demo driver imports from the absent ``HRPose.misc.visualization`` (/
 Pure host code (NumPy + PIL; OpenCV is not a dependency here).  Points are rows (y, x, confidence) like the 2D poses
 ``PersonTrack_Project3DPose`` returns; images are H x W x 3 uint8 BGR arrays and a new array is returned.
 ``draw_tracks`` overlays the tracks' 3D poses instead, re-projected into every view: the One-Euro filtered pose of a track that has one
-(IterativeTracker(one_euro=...), ``TrackView.pose3d_filtered``), else its raw one."""
+(IterativeTracker(one_euro=...), ``TrackView.pose3d_filtered``), else its raw one.
+
+``overlay_table`` / ``draw_overlay_device`` are the device form (csrc/pam_overlay.hip): the same primitives in the same order -- per
+person the limbs, then the joints, the same colours, radius and width -- as one table of integer capsules that ONE launch paints into
+the CUDA frames of all views in place.  The rasteriser is the project's own, defined in include/pam.h; it is not pixel-identical to
+ImageDraw's lines and ellipses.  ``draw_tracks(..., device=True)`` feeds it the re-projected tracks."""
 import colorsys
+import math
 
 import numpy as np
 from PIL import Image, ImageDraw
@@ -55,12 +61,106 @@ def track_pose3d(track):
     return np.asarray(track.pose3d if f is None else f, dtype=np.float64)
 
 
-def draw_tracks(imagelist, cameras, tracks, skeleton=None, emitted_only=True, **style):
+OVERLAY_COORD_MAX = 1 << 18          # 1/8 pixel: what pam_overlay_draw takes (include/pam.h)
+
+
+def overlay_style(width, height):
+    """(joint radius, limb width) in pixels for a frame of this size, as draw_points_and_skeleton picks them."""
+    radius = max(2, int(round(min(width, height) / 150.0)))
+    return radius, max(1, radius // 2 + 1)
+
+
+def _overlay_q(v):
+    v = float(v)
+    if not math.isfinite(v):
+        return None
+    q = int(math.floor(8.0 * v + 0.5))
+    return q if abs(q) <= OVERLAY_COORD_MAX else None
+
+
+def overlay_table(per_view_people, sizes, skeleton=None, points_color_palette='gist_rainbow', points_palette_samples=17,
+                  skeleton_color_palette='tab20', skeleton_palette_samples=8, confidence_threshold=0.0):
+    """The primitive table of one pam_overlay_draw call.  per_view_people: per view a list of (pose rows (y, x, confidence),
+    person_index), the pairs draw_points_and_skeleton is called with, in drawing order; sizes: per view (width, height).
+    -> (int32 (n, 8) rows of PamOverlayPrim, [(first, count)] per view).  A joint is drawable when its confidence is above the threshold,
+    both coordinates are finite and within 2^18 eighths of a pixel; a limb needs both of its joints."""
+    skeleton = joints_dict()['coco']['skeleton'] if skeleton is None else skeleton
+    limb_colors = _palette(skeleton_color_palette, skeleton_palette_samples)
+    pt_colors = _palette(points_color_palette, points_palette_samples)
+    bgr = lambda c: int(c[2]) | (int(c[1]) << 8) | (int(c[0]) << 16)          # palettes are RGB, the word is B | G << 8 | R << 16
+    rows, ranges = [], []
+    for people, (width, height) in zip(per_view_people, sizes):
+        first = len(rows)
+        radius, limb_width = overlay_style(width, height)
+        for points, person_index in people:
+            pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+            q = [(_overlay_q(x), _overlay_q(y)) if c > confidence_threshold else (None, None) for y, x, c in pts]
+            ok = [a is not None and b is not None for a, b in q]
+            color = bgr(limb_colors[int(person_index) % len(limb_colors)])
+            for a, b in skeleton:
+                if ok[a] and ok[b]:
+                    rows.append((q[a][0], q[a][1], q[b][0], q[b][1], 4 * limb_width, color, 0, 0))
+            for j, (x, y) in enumerate(q):
+                if ok[j]:
+                    rows.append((x, y, x, y, 8 * radius, bgr(pt_colors[j % len(pt_colors)]), 0, 0))
+        ranges.append((first, len(rows) - first))
+    return np.asarray(rows, dtype=np.int64).reshape(-1, 8).astype(np.int32), ranges
+
+
+def draw_overlay_device(frames, per_view_people, stream=None, **style):
+    """Draws every view's people into its CUDA frame IN PLACE with one pam_overlay_draw launch on ``stream`` (default: the current
+    one).  frames: per view a contiguous uint8 (H, W, 3) BGR CUDA tensor; per_view_people and style as ``overlay_table`` takes them.
+    -> frames.  More than 32 views take one launch per 32."""
+    import torch
+    from . import _lib
+    lib = _lib.load()
+    for f in frames:
+        if not (f.is_cuda and f.dtype == torch.uint8 and f.dim() == 3 and f.shape[2] == 3 and f.is_contiguous()):
+            raise ValueError('draw_overlay_device takes contiguous uint8 (H, W, 3) CUDA tensors')
+    if not frames:
+        return frames
+    device = frames[0].device
+    stream = torch.cuda.current_stream(device) if stream is None else stream
+    for lo in range(0, len(frames), _lib.OVERLAY_MAX_VIEWS):
+        part = frames[lo:lo + _lib.OVERLAY_MAX_VIEWS]
+        table, ranges = overlay_table(per_view_people[lo:lo + len(part)], [(f.shape[1], f.shape[0]) for f in part], **style)
+        if not len(table):
+            continue                                     # nothing to draw: no upload, no launch
+        with torch.cuda.stream(stream):
+            prims = torch.from_numpy(table).pin_memory().to(device, non_blocking=True)
+        views = (_lib.PamOverlayView * len(part))()
+        for v, f, (first, count) in zip(views, part, ranges):
+            v.dev_bgr, v.width, v.height, v.prim_first, v.prim_count = f.data_ptr(), f.shape[1], f.shape[0], first, count
+        rc = lib.pam_overlay_draw(stream.cuda_stream, len(part), views, prims.data_ptr(), len(table))
+        if rc != 0:
+            raise _lib.PamError('pam_overlay_draw failed (%d)' % rc)
+    return frames
+
+
+def track_rows(cameras, tracks, emitted_only=True):
+    """Per view the (rows, track id) pairs ``draw_tracks`` draws: every (emitted) track's 3D pose re-projected with
+    ``Camera.projectPoints``, joints behind the camera with confidence 0."""
+    out = [[] for _ in cameras]
+    for tr in tracks:
+        if emitted_only and not getattr(tr, 'emitted', True):
+            continue
+        X = track_pose3d(tr)
+        for v, cam in enumerate(cameras):
+            depth = np.asarray(cam.P, dtype=np.float64)[2] @ np.concatenate([X, np.ones((len(X), 1))], axis=1).T
+            yx = np.asarray(cam.projectPoints(X), dtype=np.float64)
+            out[v].append((np.concatenate([np.where(depth[:, None] > 0, yx, 0.0), (depth[:, None] > 0).astype(np.float64)], axis=1), tr.track_id))
+    return out
+
+
+def draw_tracks(imagelist, cameras, tracks, skeleton=None, emitted_only=True, device=False, **style):
     """Every (emitted) track's 3D pose (``track_pose3d``) re-projected into every view with ``Camera.projectPoints`` and drawn with
-    ``draw_points_and_skeleton`` (colour by track id) -> a new list of images.  Joints behind a camera are not drawn."""
+    ``draw_points_and_skeleton`` (colour by track id) -> a new list of images.  Joints behind a camera are not drawn.
+    device=True: imagelist holds CUDA frames, which ``draw_overlay_device`` draws into in place (the same list comes back)."""
     skeleton = joints_dict()['coco']['skeleton'] if skeleton is None else skeleton
     kw = dict(points_color_palette='gist_rainbow', skeleton_color_palette='tab20', points_palette_samples=17, confidence_threshold=0.0)
     kw.update(style)
+    if device:
+        return draw_overlay_device(imagelist, track_rows(cameras, tracks, emitted_only), skeleton=skeleton, **kw)
     out = list(imagelist)
     for tr in tracks:
         if emitted_only and not getattr(tr, 'emitted', True):
