@@ -915,6 +915,59 @@ typedef struct PamOverlayView {
  * leaves the table. */
 int pam_overlay_draw(void* stream, int n_views, const PamOverlayView* views, const PamOverlayPrim* dev_prims, int n_prims);
 
+/* pam_overlay_draw_counted: pam_overlay_draw with the views' primitive counts read on the device (the same kernel with one more
+ * pointer): view i draws the first clamp(dev_count[i], 0, views[i].prim_count) primitives of its range, so a device count never reaches
+ * past the range the host names.  Workgroups are launched for every view whose host-side prim_count is positive; a tile of a view
+ * whose device count is 0 leaves at once.  For the fixed-layout table of pam_overlay_tracks, whose ranges are mostly null rows that
+ * every tile would otherwise cull.  PAM_E_ARG: what pam_overlay_draw refuses, and a null dev_count (n_views int32 in device memory). */
+int pam_overlay_draw_counted(void* stream, int n_views, const PamOverlayView* views, const PamOverlayPrim* dev_prims, int n_prims,
+                             const int32_t* dev_count);
+
+/* ---- the overlay's primitive table from the tracker state (csrc/pam_overlay_tracks.hip; the host form is visualization.track_rows +
+ * overlay_table on a fetched record) and the free-viewpoint 3D view (the plot3DPose the reference's demo loop calls and does not ship,
+ * testmodel.py:77-81: "you can design your own method to visualize 3D poses") -----------------------------------------------------------
+ * pam_overlay_tracks (k_overlay_tracks: one workgroup, asynchronous on `stream`) reads the state of `scene` as the frame launches already
+ * on `stream` leave it, writes nothing to it and does not look at the input guard.  The host never learns a count.
+ *   tracks      in list order (the record's order), positions 0 .. n_tracks - 1; with emitted_only != 0 only the tracks the record calls
+ *               emitted: time_since_update == 0 and Confirmed (ivclabpose.py:266).
+ *   pose        of the track at list position i: row i of dev_pose (17 x 3 doubles; pam_one_euro's dev_pose of this scene) when that
+ *               pointer is given, else the newest pose of the track's history ring -- the record's pose3d.
+ *   view v      views[v].camera = c in 0 .. C - 1: P = the handle's camera c (pam_set_cameras; float32); camera = -1: P = row
+ *               views[v].extra of dev_extra_P (12 float32 each, row-major 3 x 4; device memory).
+ *   projection  of joint (X, Y, Z), P promoted to double, sums left to right:
+ *                 h0 = P[0] X + P[1] Y + P[2] Z + P[3];  h1 = P[4] X + ... + P[7];  h2 = P[8] X + ... + P[11]
+ *                 ih = 1.0 / h2;  u = h0 * ih (column);  w = h1 * ih (row)
+ *               While a lens table is set (pam_set_lens) and the row of camera c has a non-zero coefficient, (u, w) then goes through
+ *               normalise, forward and pixels of the lens section above, as in pam_track_boxes: the skeleton lies on the RAW image.  Extra
+ *               views have no lens.  The library is built with -ffp-contract=off: computed as written, the division is the device's.
+ *   drawable    a joint: h2 > 0.0, u and w finite, and qx = floor(8.0 * u + 0.5), qy = floor(8.0 * w + 0.5) both within 2^18 in
+ *               magnitude.  A limb: both of its joints.
+ *   rows        of view v in painter's order: per track the 19 COCO limbs (a, b) in the order (15,13) (13,11) (16,14) (14,12) (11,12)
+ *               (5,11) (6,12) (5,6) (5,7) (6,8) (7,9) (8,10) (1,2) (0,1) (0,2) (1,3) (2,4) (0,5) (0,6), then the 17 joints.
+ *               limb:  A = (qx, qy) of a, B = that of b, hw = 4 * limb_width, bgr = palette[track id mod 8] (the non-negative remainder)
+ *               joint: A = B = (qx, qy), hw = 8 * radius, bgr = palette[8 + j];  reserved words 0
+ *               radius = max(2, the integer nearest min(width, height) / 150.0, ties to even), limb_width = radius / 2 + 1 (integer
+ *               division), from the view's width and height: the frame it will be drawn into.
+ *   layout      view v owns rows [v * cap, (v + 1) * cap) of dev_prims.  Its drawable rows stand at the front in the order above,
+ *               dev_count[v] is their number, and every other row of the range is a null row (hw = -1, all else 0: pam_overlay_draw*
+ *               skips it).  All n_views * cap rows are defined after the launch and nothing outside them is written.
+ * For a pin-hole camera this is the table visualization.overlay_table(track_rows(...)) builds from the fetched record (to the ulp by
+ * which the one-division projection may differ from h0 / h2).
+ * palette: 25 host words B | G << 8 | R << 16, copied into the launch: 8 limb colours, then the 17 joint colours.
+ * PAM_E_ARG, before any device call: a NULL handle, views, palette, dev_prims or dev_count; n_views outside 1 .. PAM_MAX_VIEWS; a camera
+ * outside -1 .. C - 1; an extra row outside 0 .. n_extra - 1 (n_extra > 0 needs dev_extra_P); a width or height outside 1 .. 65535;
+ * cap < PAM_OVERLAY_TRACK_ROWS * max_tracks (or > 2^20); dev_prims not 16-byte aligned; a scene the handle does not have.
+ * PAM_E_STATE: pam_set_cameras has not been called. */
+#define PAM_OVERLAY_TRACK_ROWS 36    /* rows of one track in one view: 19 limbs + 17 joints */
+typedef struct PamOverlayTrackView {
+    int32_t camera;              /* 0 .. C - 1: a camera of the handle; -1: extra view `extra` */
+    int32_t extra;               /* row of dev_extra_P when camera == -1 */
+    int32_t width, height;       /* of the frame the view is drawn into: fixes joint radius and limb width */
+} PamOverlayTrackView;
+int pam_overlay_tracks(PamHandle* h, void* stream, int scene, int n_views, const PamOverlayTrackView* views, const float* dev_extra_P,
+                       int n_extra, const double* dev_pose, const uint32_t* palette, int emitted_only, int cap,
+                       PamOverlayPrim* dev_prims, int32_t* dev_count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,11 @@ class PamOverlayView(C.Structure):
     _fields_ = [('dev_bgr', C.c_void_p), ('width', C.c_int32), ('height', C.c_int32), ('prim_first', C.c_int32), ('prim_count', C.c_int32)]
 
 
+class PamOverlayTrackView(C.Structure):
+    """One view of a pam_overlay_tracks call: a camera of the handle (or -1 and a row of the extra matrices) and the size of its frame."""
+    _fields_ = [('camera', C.c_int32), ('extra', C.c_int32), ('width', C.c_int32), ('height', C.c_int32)]
+
+
 # every symbol include/pam.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _I = C.c_int
@@ -182,6 +187,8 @@ _SIGS = {
     'pam_jpeg_encode_bound': (_I, [_I, _I, _I, _I, C.POINTER(C.c_size_t)]),
     'pam_jpeg_encode': (_I, [_P, C.c_size_t, C.POINTER(PamJpegEncodeParams), _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     'pam_overlay_draw': (_I, [_P, _I, C.POINTER(PamOverlayView), _P, _I]),
+    'pam_overlay_draw_counted': (_I, [_P, _I, C.POINTER(PamOverlayView), _P, _I, _P]),
+    'pam_overlay_tracks': (_I, [_P, _P, _I, _I, C.POINTER(PamOverlayTrackView), _P, _I, _P, _P, _I, _I, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 YOLO_MAX_CAND = 1024        # PAM_YOLO_MAX_CAND in include/pam.h
@@ -203,6 +210,7 @@ LENS_ITERS, LENS_TOL = 8, 1e-9             # Newton steps of the inverse and its
 ONE_EURO_3D = dict(freq=25, mincutoff=0.8, beta=0.4, dcutoff=0.4)
 JPEG_MAX_IMAGES = 32                       # images of one pam_jpeg_reconstruct / pam_jpeg_forward call (PAM_MAX_VIEWS)
 OVERLAY_MAX_VIEWS = 32                     # views of one pam_overlay_draw call (PAM_MAX_VIEWS)
+OVERLAY_TRACK_ROWS = 36                    # rows of one track in one view of pam_overlay_tracks' table (PAM_OVERLAY_TRACK_ROWS)
 # PamJpegInfo.unsupported: why pam_jpeg_probe leaves a file to another decoder (PAM_JPEG_U_* in include/pam.h)
 JPEG_UNSUPPORTED = {1: 'not a JPEG', 2: 'progressive', 3: 'arithmetic coding', 4: 'SOF1 / lossless / differential frame',
                     5: 'sample precision other than 8 bits', 6: '16-bit quantisation table', 7: 'neither one nor three components',
@@ -501,6 +509,26 @@ class Handle(object):
                                            float(pad_px), float(min_size_px), int(max_gap), max_det, C.c_void_p(boxes.data_ptr()),
                                            C.c_void_p(count.data_ptr()), C.c_void_p(ids.data_ptr()) if ids is not None else None,
                                            C.c_void_p(info.data_ptr())))
+
+    def overlay_tracks(self, stream, views, palette, prims, count, extra_P=None, pose=None, emitted_only=True, scene=0):
+        """The overlay's primitive table from the tracker state behind whatever is queued on ``stream`` (pam_overlay_tracks; the rules:
+        include/pam.h).  views: a PamOverlayTrackView array; palette: 25 words B | G << 8 | R << 16 (8 limb, 17 joint colours);
+        prims (len(views), cap, 8) int32 and count (len(views),) int32: contiguous device tensors, every row of which is written;
+        extra_P: (n_extra, 3, 4) float32 device tensor for the views with camera -1; pose: one_euro's device pose buffer (the rows of
+        ``scene`` are taken), None = the tracks' newest raw poses.  Reads the tracker state, never writes it."""
+        n = len(views)
+        assert prims.dim() == 3 and prims.shape[0] == n and prims.shape[2] == 8 and prims.is_contiguous() and str(prims.dtype) == 'torch.int32'
+        assert count.numel() == n and count.is_contiguous() and str(count.dtype) == 'torch.int32'
+        assert extra_P is None or (extra_P.is_contiguous() and str(extra_P.dtype) == 'torch.float32' and extra_P.numel() % 12 == 0)
+        pal = (C.c_uint32 * 25)(*[int(c) for c in palette])
+        pose_ptr = None
+        if pose is not None:
+            assert pose.is_contiguous() and str(pose.dtype) == 'torch.float64' and pose.numel() == self.n_scenes * self.max_tracks * PAM_J * 3
+            pose_ptr = C.c_void_p(pose.data_ptr() + 8 * int(scene) * self.max_tracks * PAM_J * 3)
+        self._chk(self.lib.pam_overlay_tracks(self._h, C.c_void_p(stream), int(scene), n, views,
+                                              C.c_void_p(extra_P.data_ptr()) if extra_P is not None else None,
+                                              extra_P.numel() // 12 if extra_P is not None else 0, pose_ptr, pal, int(bool(emitted_only)),
+                                              int(prims.shape[1]), C.c_void_p(prims.data_ptr()), C.c_void_p(count.data_ptr())))
 
     def pinned_record(self):
         """(keep, out_i, out_d): ONE pinned host buffer laid out like the device record (int32 section padded to 8 bytes, float64 section

@@ -24,6 +24,7 @@ struct OvView {
 struct OvArgs {
     OvView view[PAM_MAX_VIEWS];
     const PamOverlayPrim* prims;
+    const int32_t* counts;            // pam_overlay_draw_counted: the views' primitive counts on the device, or nullptr
     int n_views;
 };
 static_assert(sizeof(OvArgs) <= 4096, "descriptors travel in the kernel arguments");
@@ -62,10 +63,12 @@ __global__ __launch_bounds__(OV_BLOCK) void k_overlay(const OvArgs a) {
     uint32_t colour[OV_RUN];
 #pragma unroll
     for (int k = 0; k < OV_RUN; ++k) { best[k] = -1; colour[k] = 0; }
-    for (int base = 0; base < v.prim_count; base += OV_LIST) {
+    // workgroup-uniform: a device count never reaches past the host's range of the table; a tile of a view that has 0 leaves at once
+    const int prim_count = a.counts ? min(max(a.counts[vi], 0), v.prim_count) : v.prim_count;
+    for (int base = 0; base < prim_count; base += OV_LIST) {
         if (threadIdx.x == 0) n_list = 0;
         __syncthreads();
-        const int n = min(v.prim_count - base, OV_LIST);
+        const int n = min(prim_count - base, OV_LIST);
         for (int i = threadIdx.x; i < n; i += OV_BLOCK) {
             const PamOverlayPrim p = a.prims[v.prim_first + base + i];
             if (abs(p.ax) > OV_COORD_MAX || abs(p.ay) > OV_COORD_MAX || abs(p.bx) > OV_COORD_MAX || abs(p.by) > OV_COORD_MAX || p.hw < 0 ||
@@ -101,13 +104,15 @@ __global__ __launch_bounds__(OV_BLOCK) void k_overlay(const OvArgs a) {
         }
 }
 
-extern "C" int pam_overlay_draw(void* stream, int n_views, const PamOverlayView* views, const PamOverlayPrim* dev_prims, int n_prims) {
+static int ov_draw(void* stream, int n_views, const PamOverlayView* views, const PamOverlayPrim* dev_prims, int n_prims,
+                   const int32_t* dev_count) {
     if (!views || n_views < 1 || n_views > PAM_MAX_VIEWS || n_prims < 0) return PAM_E_ARG;
     if (n_prims > 0 && (!dev_prims || ((uintptr_t)dev_prims & 15))) return PAM_E_ARG;
     OvArgs a;
     memset(&a, 0, sizeof(a));
     a.n_views = n_views;
     a.prims = dev_prims;
+    a.counts = dev_count;
     uint64_t wg = 0;
     for (int i = 0; i < n_views; ++i) {
         const PamOverlayView& s = views[i];
@@ -123,4 +128,15 @@ extern "C" int pam_overlay_draw(void* stream, int n_views, const PamOverlayView*
     if (wg == 0) return PAM_OK;
     hipLaunchKernelGGL(k_overlay, dim3((unsigned)wg), dim3(OV_BLOCK), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+}
+
+extern "C" int pam_overlay_draw(void* stream, int n_views, const PamOverlayView* views, const PamOverlayPrim* dev_prims, int n_prims) {
+    return ov_draw(stream, n_views, views, dev_prims, n_prims, nullptr);
+}
+
+// the same launch with the views' counts read on the device (pam_overlay_tracks' dev_count)
+extern "C" int pam_overlay_draw_counted(void* stream, int n_views, const PamOverlayView* views, const PamOverlayPrim* dev_prims, int n_prims,
+                                        const int32_t* dev_count) {
+    if (!dev_count) return PAM_E_ARG;
+    return ov_draw(stream, n_views, views, dev_prims, n_prims, dev_count);
 }

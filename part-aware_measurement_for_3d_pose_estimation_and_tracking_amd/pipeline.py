@@ -36,7 +36,7 @@ class FramePipeline(object):
                  rank=0, group=None, use_graph=True, hrnet=True, seed=0, shard='views', overlap_tracker=False, net=None, exchange='torch',
                  pose_streams=1, autotune=True, prewarm=False, width=48, resolution=(384, 288), flip_test=False, shift_heatmap=True,
                  post_process=False, model_name='HRNet', crop_cap=None, detect_every=1, dark=False, blur_kernel=None, pose_nms=False,
-                 oks_thre=0.9, in_vis_thre=0.2, lens=None, one_euro=None):
+                 oks_thre=0.9, in_vis_thre=0.2, lens=None, one_euro=None, overlay=None):
         """shard: 'views' -- rank owns whole camera views (pose_step / track_step take view-local inputs); 'crops' -- the
         frame's crops are dealt out evenly over the ranks (pose_step_crops / track_step_crops take global view indices).
         overlap_tracker (either mode): exchange + tracker kernel + fetch of frame t run on their own stream, under the conv
@@ -74,7 +74,13 @@ class FramePipeline(object):
         track_step_crops, on the tracker's stream, the tracks' newest 3D poses go through One-Euro filters on the device (pam_one_euro;
         the rules: include/pam.h) and results() adds rec['pose3d_filtered'] ((n_tracks, 17, 3), the record's order) and
         rec['filter_meta'] = dict(n_fresh, ids, fresh, samples).  An output filter: the tracker state and the record are what they are
-        without it; with view sharding every rank filters its own replica, nothing is exchanged.  None: the launches of before."""
+        without it; with view sharding every rank filters its own replica, nothing is exchanged.  None: the launches of before.
+        overlay: dict(view3d=None | dict(size=(width, height), azimuth=, elevation=, up=), emitted_only=True) switches ``overlay_step``
+        on: the tracks drawn into this rank's CUDA frames -- and into a free-viewpoint 3D canvas when view3d is given -- straight from
+        the device-resident state (pam_overlay_tracks + pam_overlay_draw_counted; the rules: include/pam.h), the One-Euro poses when
+        one_euro is on.  Needs shard='views'.  None: no step, no buffer, the launches of before."""
+        if overlay is not None and shard == 'crops':
+            raise ValueError("overlay needs shard='views': a rank draws the frames of the views it owns")
         lens = _lib.check_lens(lens, len(calib_cameras))
         if lens is not None and shard == 'crops':
             raise ValueError("lens needs shard='views': crop sharding gathers rows whose view the device-side step cannot name")
@@ -178,6 +184,24 @@ class FramePipeline(object):
             self.nms_n_det, self.nms_keep_from = self._nms_i[:nv], self._nms_i[nv:].view(nv, max_dets)
             self.nms_pose_score = torch.zeros((nv, max_dets), dtype=torch.float64, device=self.device)
             self._nms_host = torch.zeros(nv + nv * max_dets, dtype=torch.int32).pin_memory()
+        self.overlay = None
+        if overlay is not None:
+            unknown = set(overlay) - {'view3d', 'emitted_only'}
+            if unknown:
+                raise ValueError('overlay: unknown key(s) %s (view3d, emitted_only)' % sorted(unknown))
+            self.overlay = dict(emitted_only=bool(overlay.get('emitted_only', True)), view3d=None)
+            self.ev_overlay = (torch.cuda.Event(), torch.cuda.Event())      # frames ready -> draw, draw done -> consumer
+            v3 = overlay.get('view3d')
+            if v3 is not None:
+                from . import visualization as V
+                v3 = dict(v3)
+                size = tuple(int(x) for x in v3.pop('size', (640, 480)))
+                up = v3.pop('up', (0, 0, 1))
+                P3 = V.view3d_camera(calib_cameras, size, up=up, **v3)
+                self.view3d_P = torch.from_numpy(P3.reshape(1, 3, 4)).to(self.device)
+                self.view3d_background = V.view3d_background(calib_cameras, P3, size, up=up, device=self.device)
+                self.view3d_canvas = None
+                self.overlay['view3d'] = dict(size=size, P=P3)
 
     def _pick_track_stream(self, tries=8, spin_us=400, avoid=None):
         """A stream for the exchange + tracker that REALLY runs beside the caller's (pose) stream.  HIP streams are multiplexed onto a few
@@ -399,6 +423,41 @@ class FramePipeline(object):
         self._oe_fetched = bool(fetch)
         if fetch:
             self._oe_host[0].copy_(pose, non_blocking=True); self._oe_host[1].copy_(meta, non_blocking=True)
+
+    def overlay_step(self, frames):
+        """overlay=: the tracks as the last track_step left them, drawn into ``frames`` -- this rank's CUDA frames, one contiguous uint8
+        (H, W, 3) BGR tensor per view of ``mine`` in order -- IN PLACE, and into the 3D canvas when view3d is configured: a NEW tensor every
+        call (``view3d_canvas``: the background's copy with the tracks on top), so that a FrameWriter may still be reading the one
+        before.  Issued on the tracker's stream behind the frame kernel and the One-Euro launch of that step, and behind whatever
+        the current stream holds (the frames' producer); the current stream then waits for the draw, so the result can go straight to
+        FrameWriter.submit.  Nothing is fetched: it works with track_step(fetch=False).  -> the list of frames (+ the canvas)."""
+        if self.overlay is None:
+            raise ValueError('overlay_step needs FramePipeline(overlay=...)')
+        from .visualization import draw_tracks_device
+        frames = list(frames)
+        if len(frames) != len(self.mine):
+            raise ValueError('overlay_step takes one frame per view of this rank (%d), got %d' % (len(self.mine), len(frames)))
+        views, extra = [int(c) for c in self.mine], None
+        cur = torch.cuda.current_stream(self.device)
+        if self.overlay['view3d'] is not None:
+            self.view3d_canvas = torch.empty_like(self.view3d_background)      # (allocated on the consumer's stream, filled on the draw's)
+            frames, views, extra = frames + [self.view3d_canvas], views + [-1], self.view3d_P
+        pose = self._oe_dev[0] if self.one_euro is not None else None
+
+        def issue(st):
+            if extra is not None:
+                self.view3d_canvas.copy_(self.view3d_background)
+            draw_tracks_device(self.handle, frames, views=views, extra=extra, pose=pose, emitted_only=self.overlay['emitted_only'], stream=st)
+        if self.track_stream is None or not self._track_pending:
+            issue(cur)
+            return frames
+        self.ev_overlay[0].record(cur)
+        with torch.cuda.stream(self.track_stream):
+            self.track_stream.wait_event(self.ev_overlay[0])
+            issue(self.track_stream)
+            self.ev_overlay[1].record(self.track_stream)
+        cur.wait_event(self.ev_overlay[1])
+        return frames
 
     # -- person boxes that never visit the host ------------------------------------------------------------------------------
     def reset(self):

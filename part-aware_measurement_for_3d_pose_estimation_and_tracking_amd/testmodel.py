@@ -81,14 +81,41 @@ def _device_available():
     return torch.cuda.is_available()
 
 
-def overlay_on_device(model, imagelist, result):
+def view3d_setup(model, block):
+    """DATASET.VIEW3D {SIZE: [width, height], AZIMUTH, ELEVATION, UP, MARGIN} (every key optional) -> what overlay_on_device needs for the
+    free-viewpoint 3D view: the look-at matrix on the device and the background canvas, both made once."""
+    import torch
+    from pam.visualization import view3d_camera, view3d_background
+    block = dict(block) if hasattr(block, 'keys') else {}
+    unknown = set(k.upper() for k in block) - {'SIZE', 'AZIMUTH', 'ELEVATION', 'UP', 'MARGIN'}
+    if unknown:
+        raise ValueError('DATASET.VIEW3D: unknown key(s) %s (SIZE, AZIMUTH, ELEVATION, UP, MARGIN)' % sorted(unknown))
+    kw = {k.lower(): v for k, v in block.items()}
+    size = tuple(int(x) for x in kw.pop('size', (640, 480)))
+    up = tuple(float(x) for x in kw.pop('up', (0, 0, 1)))
+    device = torch.device('cuda', model.device) if isinstance(model.device, int) else torch.device(model.device)
+    P = view3d_camera(model.cameras, size, up=up, **{k: float(v) for k, v in kw.items()})
+    return dict(P=torch.from_numpy(P.reshape(1, 3, 4)).to(device), background=view3d_background(model.cameras, P, size, up=up, device=device))
+
+
+def overlay_on_device(model, imagelist, result, tracks=False, view3d=None):
     """The overlay of one frame drawn on the device: the 2D poses of PersonTrack_Project3DPose's result per view, in the order the host
     path draws them, then (ONE_EURO) the re-projected filtered tracks.  Frames that are still NumPy arrays are uploaded first.
-    -> the list of CUDA frames, drawn in place."""
+    tracks (DATASET.OVERLAY_TRACKS): the tracks' 3D poses instead, projected and drawn straight from the tracker's device-resident
+    state -- the filtered ones under ONE_EURO -- without a host table (pam.visualization.draw_tracks_device); view3d (view3d_setup): a
+    3D canvas more, appended to the list.  -> the list of CUDA frames, drawn in place."""
     import torch
-    from pam.visualization import draw_overlay_device, draw_tracks
+    from pam.visualization import draw_overlay_device, draw_tracks, draw_tracks_device
     device = torch.device('cuda', model.device) if isinstance(model.device, int) else torch.device(model.device)
     frames = [im if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im)).to(device) for im in imagelist]
+    if tracks or view3d is not None:
+        trk = model.tracker
+        pose = trk._oe_dev[0] if getattr(trk, 'one_euro', None) is not None else None
+        canvas = [view3d['background'].clone()] if view3d is not None else []          # a new one per frame: the writer reads the last
+        if tracks:
+            draw_tracks_device(trk.handle, frames + canvas, extra=view3d['P'] if canvas else None, pose=pose)
+            return frames + canvas
+        draw_tracks_device(trk.handle, canvas, views=[-1], extra=view3d['P'], pose=pose)
     people = [[] for _ in frames]
     for cids, poses_2d, pids in zip(result[0], result[1], result[2]):
         for cid, pose_2d, pid in zip(cids, poses_2d, pids):
@@ -96,7 +123,7 @@ def overlay_on_device(model, imagelist, result):
     draw_overlay_device(frames, people)
     if getattr(model, 'pts3d_filtered', None) is not None:
         draw_tracks(frames, model.cameras, model.tracker.tracks, device=True)
-    return frames
+    return frames + (canvas if view3d is not None else [])
 
 
 def test_ivclabpose_PersonTrack_Project3DPose(cfg, inputs, on_frame=None):
@@ -119,8 +146,15 @@ def test_ivclabpose_PersonTrack_Project3DPose(cfg, inputs, on_frame=None):
     # DEVICE_OVERLAY (optional key, default off; needs a device): VISUALIZATION / SAVE_IMAGE no longer switch the device loader off --
     # the overlay is drawn into the CUDA frames by pam_overlay_draw (pam.visualization.draw_overlay_device) and SAVE_IMAGE encodes them
     # behind the device (pam.egress.FrameWriter: pam_jpeg_forward, then the Huffman pass and the file on worker threads).
+    # OVERLAY_TRACKS / VIEW3D (optional keys, default off, only with DEVICE_OVERLAY): the tracks' 3D poses are drawn from the tracker's
+    # device-resident state instead of the 9-tuple's 2D poses (pam_overlay_tracks: no host table), and a free-viewpoint 3D view of them
+    # is written as <frame_id>_3d.jpg beside the per-camera files (VIEW3D: {SIZE: [w, h], AZIMUTH:, ELEVATION:, UP:}).
     draw = bool(cfg.get('VISUALIZATION') or cfg.get('SAVE_IMAGE'))
     device_overlay = draw and bool(dataset.get('DEVICE_OVERLAY', False)) and _device_available()
+    overlay_tracks, view3d_block = bool(dataset.get('OVERLAY_TRACKS', False)), dataset.get('VIEW3D')
+    if (overlay_tracks or view3d_block) and not dataset.get('DEVICE_OVERLAY', False):
+        raise ValueError('DATASET.OVERLAY_TRACKS / DATASET.VIEW3D need DATASET.DEVICE_OVERLAY: true')
+    view3d = None
     on_gpu = ((model.person_detector is not None or model.pose_model is not None) and (not draw or device_overlay)
               and bool(dataset.get('LOADER_DEVICE', True)))
     look_ahead = model.person_detector is not None and bool(dataset.get('DETECT_AHEAD', True))
@@ -152,9 +186,12 @@ def test_ivclabpose_PersonTrack_Project3DPose(cfg, inputs, on_frame=None):
                 store = os.path.join(cfg.OUTPUT, dataset.TEST_DATASET, 'Images')
                 os.makedirs(store, exist_ok=True)
                 writer = FrameWriter(model.device, workers=int(dataset.get('WRITER_THREADS', 4)), depth=int(dataset.get('WRITER_DEPTH', 4)))
-            imagelist = overlay_on_device(model, imagelist, result)
+            if view3d_block and view3d is None:
+                view3d = view3d_setup(model, view3d_block)
+            imagelist = overlay_on_device(model, imagelist, result, tracks=overlay_tracks, view3d=view3d)
             if cfg.get('SAVE_IMAGE'):
-                writer.submit(frame_id, imagelist, [os.path.join(store, '%s_%d.jpg' % (frame_id, cid)) for cid in range(len(imagelist))])
+                names = ['%s_%d.jpg' % (frame_id, cid) for cid in range(n_views)] + (['%s_3d.jpg' % frame_id] if view3d is not None else [])
+                writer.submit(frame_id, imagelist, [os.path.join(store, n) for n in names])
         elif result is not None and (cfg.get('VISUALIZATION') or cfg.get('SAVE_IMAGE')):      # testmodel.py:70-75 overlay
             from pam.visualization import joints_dict, draw_points_and_skeleton
             camera_ids, pts, person_ids = result[0], result[1], result[2]
