@@ -601,7 +601,7 @@ int pam_bottleneck_tail_nhwc_bf16(void* stream, const void* y2, const void* x0, 
                                   const float* bias3, const void* w1_img, const float* bias1, void* out_x, void* out_y1,
                                   long long n_pixels, int tile_cfg);
 
-/* ---- round 5: the fuse layers of an HR module (row a1; hrnet.py:64-100 -- stands inside the absent HRNet backend behind
+/* ---- round 5: the fuse layers of an HR module (row a1; hrnet_model.py, HighResolutionModule -- stands inside the absent HRNet backend behind
  * /root/reference/src/ivclabpose.py:210): every output i of a module is ReLU(x_i + strided-convolution chains from the finer branches +
  * up-sampled 1x1 convolutions of the coarser ones).
  *
@@ -641,7 +641,7 @@ int pam_fuse_sum_nhwc_bf16(void* stream, const void* base, int n_plain, const vo
                            const float* const* up_bias, void* out, int N, int H, int W, int C, int relu, int tile_a, int tile_b,
                            int max_workgroups);
 
-/* ---- round 5: device-side ordering of the forward's branch streams (csrc/pam_sync.hip; the module-end exchange of hrnet.py:64-100 inside
+/* ---- round 5: device-side ordering of the forward's branch streams (csrc/pam_sync.hip; the module-end exchange of hrnet_model.py, HighResolutionModule inside
  * the absent HRNet backend, /root/reference/src/ivclabpose.py:210).  pam_flag_signal: one agent-scope atomic add on *dev_counter behind
  * everything already queued on `stream`.  pam_flag_gate: [arrive != 0: first the same add, then] `stream` goes on once *dev_counter >= target (one wave polls; the launches that
  * follow on the stream see what the signalling streams' earlier kernels wrote); after *dev_max_us microseconds (a device word read when

@@ -1,7 +1,7 @@
 // libpam_hip.so, fuse-layer part of a1 (round 5): the 3x3 STRIDE-2 convolutions of HRNet's fuse layers and transitions
 //     out = [ReLU on channels >= relu_from]( conv3x3 s2 p1 (x) + b [+ res] )
 // Call site these stand for: the absent HRNet backend inside HRNetPose.predict, /root/reference/src/ivclabpose.py:210 (SURVEY.md section 8,
-// row a1; the module semantics are hrnet.py:64-100: every output of an HR module sums strided-conv chains from the finer branches).
+// row a1; the module semantics are hrnet_model.py, HighResolutionModule: every output of an HR module sums strided-conv chains from the finer branches).
 //
 // Until round 5 these 29 layers per forward ran on the generic gather kernel (k_conv_gs): every 16-byte piece of the im2col tile fetched
 // from its own address, 13 VALU + SALU instructions per MFMA, 8 % of the MFMA roof and 11 % of the HBM roof, 14.6 us per launch.

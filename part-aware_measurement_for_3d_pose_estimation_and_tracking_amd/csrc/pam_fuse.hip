@@ -1,6 +1,6 @@
 // libpam_hip.so, fuse-layer part of a1 (round 5): one output of an HR module's fuse layer in ONE launch
 //     out_i = ReLU( x_i + sum_{j < i} down_ij + sum_{j > i} nearest_up_{2^(j-i)}( W_ij x_j + b_ij ) )
-// (hrnet.py:64-100; stands inside the absent HRNet backend behind /root/reference/src/ivclabpose.py:210).
+// (hrnet_model.py, HighResolutionModule; stands inside the absent HRNet backend behind /root/reference/src/ivclabpose.py:210).
 // down_ij = the result of the strided-convolution chain from the finer branch j (already at out_i's resolution: a "plain" term);
 // the coarser branches j > i enter through a 1x1 convolution at THEIR resolution, up-sampled by pixel replication.
 //

@@ -1,5 +1,5 @@
 // libpam_hip.so, scheduling part of a1 (round 5): device-side ordering of the HRNet forward's branch streams.
-// An HR module ends with a full exchange: every output's sum reads every branch (hrnet.py:64-100; stands inside the absent HRNet backend
+// An HR module ends with a full exchange: every output's sum reads every branch (hrnet_model.py, HighResolutionModule; stands inside the absent HRNet backend
 // behind /root/reference/src/ivclabpose.py:210).  As stream events inside a captured hipGraph that join costs 15-21 us of idle chip per
 // module on ROCm 7.2 (two cross-queue hops through the caller's stream: pairwise event waits between the branch streams crash the
 // capture) -- ten times per forward.  Here the branch streams stay independent chains of the graph and meet through a counter in device
@@ -9,7 +9,7 @@
 // the usual kernel-boundary acquire).  The poll is BOUNDED: past max_us (2 s in the executor: far beyond any stall of a healthy run,
 // e.g. the context switches of two processes sharing a device) the gate sets *err and lets the stream go on -- a mapping of two chains
 // onto one in-order hardware queue, or a profiler that serialises kernels, cannot hang the device; the host checks err after the first
-// replay of every capture and falls back to stream events (pam/hrnet.py).  A time-out also stores 1 to *host_err when the caller gave
+// replay of every capture and falls back to stream events (pam/replay.py).  A time-out also stores 1 to *host_err when the caller gave
 // one (a word of pinned host memory: the host reads it before every later replay at no cost to the device), so a time-out in ANY replay
 // is reported -- e.g. two flagged replays in flight at the same time can block each other's queues, which no check of one replay sees.
 #include <hip/hip_runtime.h>

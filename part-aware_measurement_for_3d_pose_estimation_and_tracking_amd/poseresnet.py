@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as Fnn
 
-from .hrnet import Bottleneck
+from .hrnet_model import Bottleneck
 
 DEPTHS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
 MODEL_NAMES = ('PoseResNet', 'poseresnet', 'ResNet', 'resnet')
@@ -70,7 +70,7 @@ class PoseResNet(nn.Module):
 
 
 def init_random(model, seed=0):
-    """Seeded He-normal convolutions (transposed ones too), BN as the identity, bn3 of every residual branch 0.3 (as hrnet.init_random)."""
+    """Seeded He-normal convolutions (transposed ones too), BN as the identity, bn3 of every residual branch 0.3 (as hrnet_model.init_random)."""
     g = torch.Generator().manual_seed(seed)
     for m in model.modules():
         if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):

@@ -254,7 +254,7 @@ def soft_slack(hm, bound, beta, h, w):
 
 
 def decode64(py, px, boxes, h, w):
-    """Box mapping of hrnet.reference_decode: float64 arithmetic, one float32 rounding -> (y, x) float64."""
+    """Box mapping of selfcheck.reference_decode: float64 arithmetic, one float32 rounding -> (y, x) float64."""
     b = np.asarray(f32(boxes), dtype=np.float64)
     y = f32(np.asarray(py, dtype=np.float64) / h * b[:, 3:4] + b[:, 1:2]).astype(np.float64)
     x = f32(np.asarray(px, dtype=np.float64) / w * b[:, 2:3] + b[:, 0:1]).astype(np.float64)

@@ -3,7 +3,7 @@ dicts are exactly what predict() produced -- the reference reads 'keypoints' AND
 (/root/reference/src/ivclabpose.py:236-244), so any caller edit must fall back to the dicts."""
 import numpy as np
 
-from pam.hrnet import DumpResults
+from pam.dump import DumpResults
 
 
 def _dump():

@@ -297,7 +297,7 @@ def test_whole_network_on_calibrated_weights_in_every_configuration(env, calibra
     """HRNetPose built from a checkpoint of the calibrated network, ONE replaying object: in each executor configuration the replay
     equals the same object's eager forward bitwise, the heat-maps' error vs the fp32 network stays within NET_FLOOR_RATIO of what bf16
     storage alone costs, and every joint drift_statistics calls decided (k = 4, 8) decodes to the same cell."""
-    from pam import hrnet, hrnet_hip
+    from pam import hrnet, hrnet_hip, selfcheck
     n = 3
     net = hrnet.HRNetPose(48, 17, calibrated_checkpoint, resolution=(384, 288), use_graph=True, max_crops=n)
     assert net.weights == calibrated_checkpoint
@@ -313,8 +313,7 @@ def test_whole_network_on_calibrated_weights_in_every_configuration(env, calibra
     bad = []
     for name in hrnet_hip.HipHRNet.CONFIGS:
         net.config_for = lambda k, name=name: name
-        net._dead_graphs.extend(v for v in net._graphs.values()); net._dead_graphs.extend(v for v in net._alt.values() if v is not None)
-        net._graphs.clear(); net._alt.clear(); net.flag_synced.clear(); net.flag_timing.clear()
+        net.drop_captures()
         hr = net.heatmaps(x8).clone()                                 # capture, then replay
         hr2 = net.heatmaps(x8).clone()
         assert net.hip.config_name == name
@@ -322,7 +321,7 @@ def test_whole_network_on_calibrated_weights_in_every_configuration(env, calibra
             he = net._forward(x8, 'heatmaps').clone()                 # the same object's executor, eager
         torch.cuda.synchronize()
         assert torch.equal(hr, hr2) and torch.equal(hr, he), name
-        d = hrnet.drift_statistics(h32, he.float())
+        d = selfcheck.drift_statistics(h32, he.float())
         print('NETWORK ' + json.dumps(dict(config=name, rel=d['rel_l2_err'], floor=floor, rms=d['rms_err'], decided=d['decided'],
                                            planted=d['planted_peak_max_cells'], moved=d['argmax_moved_frac'])))
         if not d['rel_l2_err'] <= NET_FLOOR_RATIO * floor:

@@ -19,7 +19,7 @@ def net():
 
 
 def test_preprocess_vs_torch(net):
-    from pam import hrnet
+    from pam import selfcheck
     dev = net.device
     g = torch.Generator().manual_seed(0)
     frames = torch.randint(0, 256, (3, 288, 360, 3), dtype=torch.uint8, generator=g).to(dev)
@@ -30,7 +30,7 @@ def test_preprocess_vs_torch(net):
     x = net.input_buffer(4)
     assert x.is_contiguous(memory_format=torch.channels_last) and x.dtype == torch.bfloat16
     net.preprocess(ptrs, 288, 360, view_of, boxes, x)
-    ref = hrnet.reference_preprocess(frames, view_of, boxes, (384, 288))
+    ref = selfcheck.reference_preprocess(frames, view_of, boxes, (384, 288))
     torch.cuda.synchronize()
     assert x.shape[1] == 8 and float(x[:, 3:].float().abs().max()) == 0.0      # RGB + 5 zero channels for the MFMA conv
     assert (x[:, :3].float() - ref).abs().max().item() <= 2.0 ** -7 * 2.7 + 1e-3       # one bf16 ulp at |v| <= 2.7
@@ -41,7 +41,7 @@ def test_preprocess_vs_torch(net):
 
 @pytest.mark.parametrize('layout', ['nhwc', 'nchw'])
 def test_decode_vs_torch(net, layout):
-    from pam import hrnet
+    from pam import selfcheck
     dev = net.device
     g = torch.Generator().manual_seed(1)
     n = 5
@@ -57,7 +57,7 @@ def test_decode_vs_torch(net, layout):
     det = torch.zeros((3, 4, 17, 3), dtype=torch.float64, device=dev)
     kp = torch.zeros((n, 17, 3), dtype=torch.float32, device=dev)
     net.decode(hm, view_of, slot_of, boxes, det, kp)
-    exp = hrnet.reference_decode(hm, boxes)
+    exp = selfcheck.reference_decode(hm, boxes)
     torch.cuda.synchronize()
     for i in range(n):
         got = det[int(view_of[i]), int(slot_of[i])]
@@ -70,7 +70,7 @@ def test_decode_vs_torch(net, layout):
 def test_bf16_stack_vs_fp32(net):
     """Self-consistency of the conv stack (parity with the authors' backend is unpinned): bf16 channels-last folded-BN
     heat-maps vs the same weights in fp32 eager; reports arg-max drift."""
-    from pam import hrnet
+    from pam import hrnet, selfcheck
     dev = net.device
     ref = hrnet.fold_batchnorm(hrnet.init_random(hrnet.PoseHighResolutionNet(), seed=0)).to(dev).eval()
     g = torch.Generator().manual_seed(2)
@@ -88,7 +88,7 @@ def test_bf16_stack_vs_fp32(net):
     assert rel < 0.03, rel
     assert rel <= 1.5 * rel_mi + 5e-3
     # the recorded drift figure (bench.py's `hrnet_drift`): bounded, and no worse than PyTorch-ROCm's own bf16 convs on the same input
-    d = hrnet.measure_bf16_drift(net, n_crops=2, seed=2)
+    d = selfcheck.measure_bf16_drift(net, n_crops=2, seed=2)
     drift_mi = (hm.float().flatten(2).argmax(2) != h32.flatten(2).argmax(2)).float().mean().item()
     print('hrnet_drift', d, 'miopen bf16 drift %.3f' % drift_mi)
     assert abs(d['rel_l2_err'] - rel) < 1e-6
@@ -98,7 +98,7 @@ def test_bf16_stack_vs_fp32(net):
     # and a planted peak of 16 error sigmas (the same cell raised in both heat-maps) decodes to the same cell
     assert d['decided']['8']['max_cells'] <= 1, d
     assert d['planted_peak_max_cells']['16'] == 0, d
-    dm = hrnet.drift_statistics(h32, hm.float())                                  # PyTorch-ROCm's own bf16 convolutions: the same order of error
+    dm = selfcheck.drift_statistics(h32, hm.float())                                  # PyTorch-ROCm's own bf16 convolutions: the same order of error
     assert dm['decided']['8']['max_cells'] <= 1 and d['rms_err'] <= 2.0 * dm['rms_err'] + 1e-4, (dm, d)
 
 
@@ -118,7 +118,7 @@ def test_hipgraph_replay_matches_eager():
 def test_device_pipeline_decode_to_tracker_vs_oracle():
     """Heat-maps with planted peaks -> k_decode -> det buffer (device) -> k_frame, no host round trip; the oracle is fed the
     torch-decoded keypoints.  ids / view sets bit-exact, 3D <= 1e-6 m."""
-    from pam import hrnet
+    from pam import hrnet, selfcheck
     from pam.ivclabpose import Camera, fundamental_matrices
     from pam.pipeline import FramePipeline
     from oracle import cpu_ref as O
@@ -159,7 +159,7 @@ def test_device_pipeline_decode_to_tracker_vs_oracle():
         pipe.track_step(t, n_det, pipe.det_local)
         got = pipe.results()
         # oracle on the torch-decoded keypoints
-        dec = hrnet.reference_decode(hm, boxes).cpu().numpy() if n else np.zeros((0, 17, 3))
+        dec = selfcheck.reference_decode(hm, boxes).cpu().numpy() if n else np.zeros((0, 17, 3))
         per_view = [[] for _ in views]
         for i in range(n):
             per_view[vl[i]].append(dec[i])
@@ -241,7 +241,7 @@ def test_head_decode_fused_vs_two_kernels(net):
     identical heat-map values, identical keypoint rows, np.argmax's first-index rule on exact ties (engineered through the weights:
     an all-zero head makes every map constant = its bias), ragged last tile, crops that are not the whole feature batch."""
     import ctypes as C
-    from pam import hrnet, _lib
+    from pam import _lib, selfcheck
     dev = net.device
     lib = _lib.load()
     g = torch.Generator().manual_seed(11)
@@ -257,7 +257,7 @@ def test_head_decode_fused_vs_two_kernels(net):
         ref_hm = torch.empty((n, 17, h, w), dtype=torch.float32, device=dev).contiguous(memory_format=torch.channels_last)
         assert lib.pam_head_heatmaps(None, n * h * w, C.c_void_p(f.data_ptr()), 48, C.c_void_p(wt.data_ptr()), C.c_void_p(b.data_ptr()), 17,
                                      C.c_void_p(ref_hm.data_ptr())) == 0
-        exp = hrnet.reference_decode(ref_hm, boxes)
+        exp = selfcheck.reference_decode(ref_hm, boxes)
         old_w, old_b = net.head_w, net.head_b
         net.head_w, net.head_b = wt.contiguous(), b.contiguous()
         try:
@@ -345,7 +345,7 @@ def test_soft_argmax_decode_vs_torch(net):
 def test_preprocess_hd_frames_with_boxes_leaving_the_frame(net):
     """k_preprocess_crops at the Panoptic frame size (1920 x 1080, S3 / S4 workloads), boxes clipped by every border and one covering the
     whole frame, against the torch float32 restatement."""
-    from pam import hrnet
+    from pam import selfcheck
     dev = net.device
     g = torch.Generator().manual_seed(5)
     frames = torch.randint(0, 256, (3, 1080, 1920, 3), dtype=torch.uint8, generator=g).to(dev)
@@ -361,7 +361,7 @@ def test_preprocess_hd_frames_with_boxes_leaving_the_frame(net):
     view_of = torch.tensor([0, 1, 2, 0, 1, 2, 0], dtype=torch.int32, device=dev)
     x = net.input_buffer(7)
     net.preprocess(ptrs, 1080, 1920, view_of, boxes, x)
-    ref = hrnet.reference_preprocess(frames, view_of, boxes, (384, 288))
+    ref = selfcheck.reference_preprocess(frames, view_of, boxes, (384, 288))
     torch.cuda.synchronize()
     assert float(x[:, 3:].float().abs().max()) == 0.0
     assert (x[:, :3].float() - ref).abs().max().item() <= 2.0 ** -7 * 2.7 + 1e-3       # one bf16 ulp at |v| <= 2.7
@@ -372,7 +372,7 @@ def test_predict_s3_sized_call_through_the_graph_buckets():
     graph bucket), hipGraph replays.  A 2-crop subset (one from each batch) is checked against (a) the same kernels driven by hand --
     k_preprocess_crops -> eager conv stack -> torch decode: identical keypoints -- and (b) reference_preprocess + the fp32 PyTorch module
     with the same weights: confidences close, positions equal except for the recorded bf16 drift."""
-    from pam import hrnet
+    from pam import hrnet, selfcheck
     net = hrnet.HRNetPose(48, 17, None, resolution=(384, 288), use_graph=True, max_dets=8, graph_bucket=4)
     dev = net.device
     g = torch.Generator().manual_seed(11)
@@ -397,10 +397,10 @@ def test_predict_s3_sized_call_through_the_graph_buckets():
     x = eager.input_buffer(2)
     eager.preprocess(ptrs, 1080, 1920, view_of, boxes, x)
     with torch.no_grad():
-        exp = hrnet.reference_decode(eager.heatmaps(x), boxes)    # rows (y, x, score)
+        exp = selfcheck.reference_decode(eager.heatmaps(x), boxes)    # rows (y, x, score)
         ref = hrnet.fold_batchnorm(hrnet.init_random(hrnet.PoseHighResolutionNet(), seed=0)).to(dev).eval()
-        x32 = hrnet.reference_preprocess(torch.stack(frames), view_of, boxes, (384, 288))
-        exp32 = hrnet.reference_decode(ref(x32), boxes)
+        x32 = selfcheck.reference_preprocess(torch.stack(frames), view_of, boxes, (384, 288))
+        exp32 = selfcheck.reference_decode(ref(x32), boxes)
     torch.cuda.synchronize()
     moved = 0
     for i, (v, p) in enumerate(pick):
@@ -437,8 +437,7 @@ def test_replay_equals_eager_forward_in_every_configuration(n, eager_and_replay)
             a.hip.apply_config(name)
             b.config_for = lambda n, name=name: name
             # the replay cache is keyed by crop count: forget the previous configuration's captures (kept alive, never destroyed)
-            b._dead_graphs.extend(v for v in b._graphs.values()); b._dead_graphs.extend(v for v in b._alt.values() if v is not None)
-            b._graphs.clear(); b._alt.clear(); b.flag_synced.clear(); b.flag_timing.clear()
+            b.drop_captures()
             x = a.input_buffer(n)
             x.copy_(torch.randn(x.shape, generator=torch.Generator().manual_seed(n)).to(x.device).to(x.dtype)); x[:, 3:] = 0
             ref = a.features(x).clone()

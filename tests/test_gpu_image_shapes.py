@@ -387,7 +387,7 @@ def test_predict_equals_the_hand_driven_chain(lib, c, model_name, res, channels)
     The hand-driven chain runs the call's own batches (20 crops, then 15 in a 16-crop buffer), not two crops alone: PoseResNet's
     features are bit-exact for a given batch size only (the layer2-4 convolutions choose their tile by the batch's pixel
     count), and on random weights one bf16 ulp moves the arg-max of a near-flat map by tens of pixels."""
-    from pam import hrnet
+    from pam import hrnet, selfcheck
     net = hrnet.HRNetPose(c, 17, None, model_name=model_name, resolution=res, use_graph=True, max_dets=8, graph_bucket=4)
     dev = net.device
     name = 'predict %s-%d %dx%d' % ((model_name, c) + res)
@@ -437,7 +437,7 @@ def test_predict_equals_the_hand_driven_chain(lib, c, model_name, res, channels)
         idx = np.argmax(m.astype(np.float64), axis=2)
         y, xx = R.decode64(idx // ww, idx % ww, boxes_np[s:e], hh, ww)
         rows_ = np.stack([y, xx, np.take_along_axis(m, idx[:, :, None], axis=2)[:, :, 0].astype(np.float64)], axis=2)     # (y, x, score)
-        ref = hrnet.reference_decode(hm[:e - s], boxes[s:e]).cpu().numpy()
+        ref = selfcheck.reference_decode(hm[:e - s], boxes[s:e]).cpu().numpy()
         diff = np.argwhere((ref != rows_).any(2))
         assert diff.size == 0, (name, [(int(i), int(j), ref[i, j].tolist(), rows_[i, j].tolist(), int((m[i, j] == m[i, j].max()).sum())) for i, j in diff[:4]])
         want.append(rows_)

@@ -141,7 +141,7 @@ def _net(depth=50, res=(256, 192), path=None, **kw):
 
 
 def test_pose_resnet_replay_equals_eager_and_within_the_bf16_floor(tmp_path):
-    from pam import hrnet, hrnet_hip
+    from pam import hrnet_hip, selfcheck
     path = os.path.join(str(tmp_path), 'pose_resnet_50_256x192.pth')
     torch.save(PC.calibrated(50)[0], path)
     n, res = 20, (256, 192)
@@ -157,8 +157,7 @@ def test_pose_resnet_replay_equals_eager_and_within_the_bf16_floor(tmp_path):
         floor = float((PC.bf16_storage(ref)(x.float()) - h32).norm() / h32.norm())
     for name in hrnet_hip.HipPoseResNet.CONFIGS:
         net.config_for = lambda k, name=name: name
-        net._dead_graphs.extend(v for v in net._graphs.values())
-        net._graphs.clear(); net._alt.clear(); net.flag_synced.clear(); net.flag_timing.clear()
+        net.drop_captures()
         hr = net.heatmaps(x8).clone()
         hr2 = net.heatmaps(x8).clone()
         assert net.hip.config_name == name and not any(net.flag_synced.values())
@@ -171,7 +170,7 @@ def test_pose_resnet_replay_equals_eager_and_within_the_bf16_floor(tmp_path):
         print('R50 NETWORK config=%s rel=%.5f floor=%.5f' % (name, rel, floor))
         assert rel <= NET_FLOOR_RATIO * floor, (name, rel, floor)
         if name == hrnet_hip.HipPoseResNet.config_name:
-            st = hrnet.drift_statistics(h32, he.float())
+            st = selfcheck.drift_statistics(h32, he.float())
             print('DRIFT ' + json.dumps(st))
             assert st['planted_peak_max_cells']['16'] == 0, st
 

@@ -144,8 +144,7 @@ def test_w32_pose_vs_fp32_and_replay_equals_eager_in_every_configuration(tmp_pat
     bad = []
     for name in hrnet_hip.HipHRNetW32.CONFIGS:
         net.config_for = lambda k, name=name: name
-        net._dead_graphs.extend(v for v in net._graphs.values()); net._dead_graphs.extend(v for v in net._alt.values() if v is not None)
-        net._graphs.clear(); net._alt.clear(); net.flag_synced.clear(); net.flag_timing.clear()
+        net.drop_captures()
         hr = net.heatmaps(x8).clone()
         hr2 = net.heatmaps(x8).clone()
         assert net.hip.config_name == name

@@ -1,5 +1,5 @@
-"""CPU: the float64 restatements of tests/image_ref.py agree with the older references (hrnet.reference_preprocess,
-hrnet.reference_decode, torch's antialiased interpolation, F.conv2d in float64), and every tolerance they hand to the GPU tests
+"""CPU: the float64 restatements of tests/image_ref.py agree with the older references (selfcheck.reference_preprocess,
+selfcheck.reference_decode, torch's antialiased interpolation, F.conv2d in float64), and every tolerance they hand to the GPU tests
 (tests/test_gpu_image_shapes.py) rejects a deliberately wrong restatement on the very inputs those tests use: pixel centres without the
 -0.5, channels not swapped, bf16 by truncation, a 1/32-pixel shift, a one-sided cut of the antialias window, a last-index tie rule, a
 head that skips its final 8 channels.  The share of heat-maps whose arg-max the float32 bound leaves open is asserted here too."""
@@ -27,10 +27,10 @@ def test_bf16_helpers_match_torch():
 @pytest.mark.parametrize('case', R.CROP_CASES[:2], ids=CROP_IDS[:2])
 @pytest.mark.parametrize('res', RESOLUTIONS, ids=['256x192', '384x288'])
 def test_preprocess64_agrees_with_the_float32_restatement(case, res):
-    from pam import hrnet
+    from pam import selfcheck
     frames, view_of, boxes = R.crop_case_inputs(case)
     val, tol = R.preprocess64(frames, view_of, boxes, res)
-    ref = hrnet.reference_preprocess(torch.from_numpy(frames), torch.from_numpy(view_of), torch.from_numpy(boxes), res).double().numpy()
+    ref = selfcheck.reference_preprocess(torch.from_numpy(frames), torch.from_numpy(view_of), torch.from_numpy(boxes), res).double().numpy()
     # the float32 restatement is one more float32 evaluation of the formula: it has to lie inside the tolerance without its bf16 term
     worst, bad = R.crop_check(ref, val, tol - 0.5 * R.bf16_ulp(np.abs(val)))
     assert bad == 0, worst
@@ -70,11 +70,11 @@ def test_head64_is_conv2d_in_float64():
 
 @pytest.mark.parametrize('hw', R.DECODE_MAPS, ids=['%dx%d' % m for m in R.DECODE_MAPS])
 def test_decode64_agrees_with_reference_decode(hw):
-    from pam import hrnet
+    from pam import selfcheck
     h, w = hw
     hm, boxes, cases = R.decode_inputs(h, w)
     hm = hm[:, [j for j in range(17) if j not in (7,)]]    # reference_decode's equality mask has no first index on a map of -inf
-    ref = hrnet.reference_decode(torch.from_numpy(hm).reshape(hm.shape[0], -1, h, w), torch.from_numpy(boxes)).numpy()
+    ref = selfcheck.reference_decode(torch.from_numpy(hm).reshape(hm.shape[0], -1, h, w), torch.from_numpy(boxes)).numpy()
     idx = np.argmax(hm.astype(np.float64), axis=2)
     y, x = R.decode64(idx // w, idx % w, boxes, h, w)
     assert np.array_equal(ref[:, :, 0], y) and np.array_equal(ref[:, :, 1], x)
