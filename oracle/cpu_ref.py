@@ -447,6 +447,7 @@ class Tracker(object):
         self.tracks = []
         self.next_id = 0
         self.unmatched = {}
+        self.n_hyp = 0
 
     # -- per-track update ---------------------------------------------------  IterativeTracker.py:253-395
     def _triangulate_update(self, tr, time, cams, Ts, pose_mat):
@@ -500,6 +501,7 @@ class Tracker(object):
     # -- new-track initialisation -------------------------------------------  IterativeTracker.py:52-113
     def _init_tracks(self, time):
         p = self.p
+        self.n_hyp = 0                             # hypotheses formed this frame (what a fixed-capacity implementation must hold)
         if len(self.unmatched) < 2:
             return
         hyps = []                                  # each: ([cams], [poses])
@@ -528,6 +530,7 @@ class Tracker(object):
             for d in range(nd):
                 if d not in handled:
                     hyps.append(([cam], [dets[d]]))
+        self.n_hyp = len(hyps)
         for hc, hp in hyps:
             if len(hp) < 2:
                 continue

@@ -132,6 +132,73 @@ def make_sequence(size='S2', n_frames=303, seed=0, noise_px=1.5, outlier_p=0.05,
             'meta': dict(size=size, C=C, P=Pn, w=w, h=h, f=f, seed=seed, n_frames=n_frames)}
 
 
+# Score classes of rescore_frames and how often each is drawn.  Every score is a multiple of 1/64, so the sum of a detection's 17 scores
+# is exact in any order: NumPy's pairwise mean, np.mean of a list and a sequential loop give the same double, and the two equality
+# classes sit on the thresholds bit for bit.
+SCORE_CLASSES = ('high', 'low', 'mixed', 'negative', 'half', 'two_fifths')
+SCORE_MIX = dict(high=0.25, low=0.25, mixed=0.15, negative=0.10, half=0.125, two_fifths=0.125)
+
+
+def draw_scores(cls, rng):
+    """17 keypoint scores of one class, all multiples of 1/64:
+       high        [45/64, 61/64]
+       low         [20/64, 30/64]: the mean lies in [0.31, 0.47], on either side of 0.4 and never above 0.5
+       mixed       9 to 11 joints in [-1, -1/4], the rest high: the mean over s >= 0 is high, the plain mean below 0.4
+       negative    all in [-1, -1/64]: no score counts, the mean confidence is NaN
+       half        all 0.5
+       two_fifths  twelve times -1/4 and five non-negative scores that sum to 2: the mean over s >= 0 is the double 0.4"""
+    if cls == 'high':
+        return rng.integers(45, 62, NUM_JOINTS) / 64.0
+    if cls == 'low':
+        return rng.integers(20, 31, NUM_JOINTS) / 64.0
+    if cls == 'mixed':
+        s = rng.integers(45, 62, NUM_JOINTS) / 64.0
+        neg = rng.permutation(NUM_JOINTS)[:int(rng.integers(9, 12))]
+        s[neg] = -(rng.integers(16, 65, len(neg)) / 64.0)
+        return s
+    if cls == 'negative':
+        return -(rng.integers(1, 65, NUM_JOINTS) / 64.0)
+    if cls == 'half':
+        return np.full(NUM_JOINTS, 0.5)
+    if cls == 'two_fifths':
+        five = np.array([26, 26, 26, 25, 25])
+        for _ in range(4):
+            i, j = rng.permutation(5)[:2]
+            d = int(rng.integers(0, 6))
+            five[i] += d
+            five[j] -= d
+        s = np.full(NUM_JOINTS, -0.25)
+        s[rng.permutation(NUM_JOINTS)[:5]] = five / 64.0
+        return s
+    raise ValueError('unknown score class %r' % (cls,))
+
+
+def rescore_frames(frames, seed, mix=None, with_classes=False):
+    """A copy of ``frames`` (list[frame][view] of (n,17,3) arrays) with every detection's score column replaced by scores of a class
+    drawn per detection from ``mix`` (class -> probability, default SCORE_MIX; see draw_scores).  Coordinates are unchanged, and the
+    random stream is the function's own (make_sequence's is untouched).  with_classes=True also returns list[frame][view] of the
+    class names drawn."""
+    mix = dict(SCORE_MIX if mix is None else mix)
+    names = [c for c in SCORE_CLASSES if mix.get(c, 0) > 0]
+    p = np.array([mix[c] for c in names], dtype=np.float64)
+    p = p / p.sum()
+    rng = np.random.default_rng([int(seed), 0x5c0e])
+    out, classes = [], []
+    for views in frames:
+        ov, oc = [], []
+        for dets in views:
+            d = np.array(dets, dtype=np.float64).reshape(-1, NUM_JOINTS, 3)
+            cl = []
+            for k in range(len(d)):
+                cl.append(names[int(rng.choice(len(names), p=p))])
+                d[k, :, 2] = draw_scores(cl[-1], rng)
+            ov.append(d)
+            oc.append(cl)
+        out.append(ov)
+        classes.append(oc)
+    return (out, classes) if with_classes else out
+
+
 def to_dump_results(view_dets):
     """(n,17,3) (x,y,score) arrays per view -> (person_bbox_list, dump_results) as the reference's
     PersonPoseDetect returns them (ivclabpose.py:195-203, 233-246)."""

@@ -4,6 +4,7 @@ import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 SIZES = ('S1', 'S2', 'S3', 'S4')
+RESCORED = ('S1s', 'S2s', 'S3s')        # trace_<S>s.npz: stress sequences of <S> with redrawn scores (synth.rescore_frames), on <S>'s rig
 
 
 def load(name):
@@ -26,7 +27,7 @@ def ops(size):
 
 
 def cameras(size):
-    return load('cameras_%s.npz' % size)
+    return load('cameras_%s.npz' % (size[:-1] if size in RESCORED else size))
 
 
 def camera_variants(size):

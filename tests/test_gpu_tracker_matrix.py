@@ -17,9 +17,7 @@ from pam import synth
 
 pytestmark = pytest.mark.gpu
 
-PLANS = {'A': dict(block=256, launches=1, hot_in_lds=1), 'B': dict(block=256, launches=1, hot_in_lds=0),
-         'C': dict(block=1024, launches=3, hot_in_lds=1), 'D': dict(block=1024, launches=3, hot_in_lds=0),
-         'E': dict(block=1024, launches=1, hot_in_lds=1), 'F': dict(block=1024, launches=1, hot_in_lds=0)}
+PLANS = M.PLANS
 
 
 @pytest.fixture(scope='module')

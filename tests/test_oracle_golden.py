@@ -90,8 +90,8 @@ def test_ops(size):
 from trace_driver import run_trace  # noqa: E402
 
 
-@pytest.mark.parametrize('size', G.SIZES)
-def test_trace(size):
+def _oracle_vs_trace(size):
+    """The oracle over a golden trace: the 9-tuple (run_trace) and the tracker state after every frame -> frames compared."""
     def factory(cfg, conf):
         return O.OracleIvclabpose(cfg, conf)
     nf = 0
@@ -109,4 +109,18 @@ def test_trace(size):
             np.testing.assert_allclose(x.hist[-1], tr[k + 'last_pose'][i], rtol=0, atol=1e-7)
             np.testing.assert_allclose(np.asarray(x.velocity, dtype=np.float64), tr[k + 'velocity'][i], rtol=0, atol=1e-6)
         nf += 1
-    assert nf > 20
+    return nf
+
+
+@pytest.mark.parametrize('size', G.SIZES)
+def test_trace(size):
+    assert _oracle_vs_trace(size) > 20
+
+
+@pytest.mark.parametrize('size', G.RESCORED)
+@pytest.mark.filterwarnings('ignore:Mean of empty slice', 'ignore:invalid value encountered')
+def test_trace_rescored(size):
+    """The traces whose scores synth.rescore_frames redrew: what the reference itself did with detections under the confidence
+    threshold, on it, without a single score >= 0 (the mean is NaN), with negative weights in the hypothesis cost and with vetoes that
+    a confidence of at most 0.5 suppresses (tests/test_tracker_scenarios_ref.py counts these branches on the same sequences)."""
+    assert _oracle_vs_trace(size) == 40

@@ -9,6 +9,9 @@ Fixtures:
   cameras_<S>.npz   calibration dict in, Camera attributes (F, RK_INV, position) out        (a18)
   ops_<S>.npz       per-function input/output records captured INSIDE a real tracker run      (a3-a16)
   trace_<S>.npz     whole sequences: per-frame detections in, the 9-tuple + tracker state out (a2-a17)
+  trace_<S>s.npz    40-frame stress sequences of S1, S2, S3 with the scores redrawn by synth.rescore_frames (confidence filter, NaN and
+                    equality cases, suppressed vetoes, negative weights in the hypothesis cost); same layout as trace_<S>.npz, cameras
+                    are cameras_<S>.npz's:   python tools/make_goldens.py --rescored
   pcp_S2.npz        Evaluate3DPose_PCP on a synthetic actorsGT.mat                              (gate)
   cameras_<S>_mkl_avx2.npz, cameras_<S>_mkl_compatible.npz  the same camera set-up on MKL's other kernel paths (AVX2: Intel CPUs
                     without AVX-512; compatible: MKL's baseline path, which it takes on other vendors' CPUs), whose float32 3x3
@@ -248,9 +251,11 @@ def dump_state(model, C):
     return st
 
 
-def run_trace(size, n_frames, seed, **seq_kw):
+def run_trace(size, n_frames, seed, rescore=None, **seq_kw):
     dataset = synth.SIZE_TO_DATASET[size]
     seq = synth.make_sequence(size, n_frames=n_frames, seed=seed, **seq_kw)
+    if rescore is not None:
+        seq['frames'] = synth.rescore_frames(seq['frames'], rescore)
     C = seq['meta']['C']
     matcher, conf = matcher_cfg(dataset)
     model = ref.ivclabpose.ivclabpose(person_detector=ref_shims.AttrDict(NAME=''), pose_detector=None,
@@ -428,13 +433,36 @@ CAMERA_PLANS = [
 ]
 
 
+# the re-scored traces: (size, frames, sequence seed, rescore seed); the stress pattern is tests/tracker_matrix.py's STRESS.  The seeds are
+# those tests/test_tracker_scenarios_ref.py witnesses (every score class dropped or split, vetoes suppressed, margins).
+RESCORED_STRESS = dict(occlusion_every=3, empty_view_every=7, birth_death_frame=14, churn_every=20, churn_len=12)
+RESCORED_PLANS = [('S1', 40, 703, 1703), ('S2', 40, 409, 1409), ('S3', 40, 406, 1406)]
+
+
+def make_rescored(out_dir):
+    for size, nf, seed, rescore in RESCORED_PLANS:
+        seq, cam_rec, trace, model = run_trace(size, nf, seed, rescore=rescore, **RESCORED_STRESS)
+        have = np.load(os.path.join(out_dir, 'cameras_%s.npz' % size))
+        for k, v in cam_rec.items():                          # the rig does not depend on the seed: cameras_<S>.npz serves the trace
+            assert np.array_equal(have[k], v), (size, k)
+        trace['meta.rescore_seed'] = np.int64(rescore)
+        path = os.path.join(out_dir, 'trace_%ss.npz' % size)
+        np.savez_compressed(path, **trace)
+        n_out = sum(len(trace['f%d.ids' % t]) for t in range(nf) if ('f%d.ids' % t) in trace)
+        print(size + 's', 'frames', nf, 'emitted poses', n_out, 'tracks now', len(model.tracker.tracks), os.path.getsize(path), 'bytes')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(ROOT, 'tests', 'golden'))
     ap.add_argument('--only-panoptic', action='store_true')
+    ap.add_argument('--rescored', action='store_true', help='write only trace_S1s.npz, trace_S2s.npz, trace_S3s.npz')
     ap.add_argument('--cameras-only', metavar='SUFFIX', default=None, help='write only cameras_<S>_<SUFFIX>.npz')
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
+    if args.rescored:
+        make_rescored(args.out)
+        return
     if args.cameras_only:
         for size, nf, seed, kw in CAMERA_PLANS:
             _, cam_rec, _, _ = run_trace(size, nf, seed, **kw)
