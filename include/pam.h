@@ -371,6 +371,38 @@ int pam_preprocess_crops_ex(void* stream, int n, int n_total, const void* const*
 int pam_preprocess_crops_flip(void* stream, int n, int n_total, const void* const* dev_frames, int frame_h, int frame_w,
                               const int32_t* dev_view_of, const float* dev_boxes, int out_h, int out_w, int out_c, void* dev_out_bf16,
                               int antialias);
+/* ---- the pose checkpoints' centre/scale box transform (official _box2cs + get_affine_transform + warpAffine + transform_preds) ----
+ * The EFFECTIVE box of a person box (x, y, w, h) for a network input of out_w x out_h (csrc/pam_box_cs.hpp, one __host__ __device__
+ * function), float64 from the float32 inputs in exactly this order, each of the four results rounded once to float32:
+ *     cx = x + w * 0.5;  cy = y + h * 0.5
+ *     if      (w * out_h > h * out_w)  h = w * out_h / out_w        too wide: grow the height
+ *     else if (w * out_h < h * out_w)  w = h * out_w / out_h        too tall: grow the width
+ *     We = w * box_scale;  He = We * out_h / out_w                  (box_scale: _box2cs's 1.25)
+ *     xe = cx - We * 0.5;  ye = cy - He * 0.5
+ * A box whose We is not > 0 (NaN included) gives (x, y, 0, 0) and an all-zero crop (before normalisation).  (The official code compares
+ * w > aspect * h with a float aspect; the integer-ratio form differs from it on exact ties only.)  The decodes map a heat-map cell with
+ * px / hm_w * box_w + box_x: handed the effective box as dev_boxes that IS transform_preds, and pam_pose_nms handed the same table takes
+ * the official area prod(scale * 200) = We * He.
+ * pam_preprocess_crops_affine: rows as pam_preprocess_crops_ex (flip = 0: n_total >= n, rows n .. repeat row n - 1) or as
+ * pam_preprocess_crops_flip (flip != 0: n_total >= 2 n, rows [n, 2n) the column reversal of the plain rows bit for bit, rows from 2n on
+ * repeat row 2n - 1), each row sampled from its box's effective box, which the launch also stores: dev_eff_xywh[r] for r < n (n x 4
+ * float32; rows >= n are never written).  Sampling is warpAffine's convention, not the stretch form's half-pixel one: in float32, output
+ * pixel (u, v) reads the frame at sx = xe + u * (We / out_w), sy = ye + v * (He / out_h), integer coordinates are pixel centres, bilinear
+ * over the four neighbours, and a tap outside the frame contributes 0 (BORDER_CONSTANT; the edge is not replicated).  Normalisation,
+ * bf16 store and out_c as pam_preprocess_crops.  antialias != 0: where We / out_w > 1 the taps are the integer positions within
+ * max(We / out_w, 1) of sx (likewise in y), triangle weights, at most 24 per axis (the ones nearest the centre); a tap outside the frame
+ * carries colour 0 but counts in the normaliser, so borders fade to black as the zero border does; where the scale is <= 1 the result is
+ * the plain affine form's.  Like PIL's uint8 rounding above, warpAffine's uint8 rounding of the resampled image and its 1/32-pixel
+ * fixed-point coordinates are not reproduced (float32 throughout), and there is no rotation.
+ * PAM_E_ARG: as pam_preprocess_crops_ex / _flip, and for a NULL dev_eff_xywh or a box_scale that is not > 0.
+ * pam_box_cs: the whole table in one tiny launch without cropping (n rows; a rank of the crop-sharded predict() crops its share only
+ * while pam_pose_nms wants every row).  pam_box_cs_host: the same function in plain C++ on host memory.  The three tables agree bit for
+ * bit (the library is built with -ffp-contract=off). */
+int pam_preprocess_crops_affine(void* stream, int n, int n_total, int flip, const void* const* dev_frames, int frame_h, int frame_w,
+                                const int32_t* dev_view_of, const float* dev_boxes, float box_scale, int out_h, int out_w, int out_c,
+                                void* dev_out_bf16, int antialias, float* dev_eff_xywh);
+int pam_box_cs(void* stream, int n, const float* dev_boxes, int out_w, int out_h, float box_scale, float* dev_eff_xywh);
+int pam_box_cs_host(int n, const float* boxes, int out_w, int out_h, float box_scale, float* eff);
 /* pam_head_decode_flip: pam_head_decode on the merged map of a plain and a mirrored crop, with the optional quarter-pixel offset.
  * feat: the feature batch of the forward above; crop i's plain features are row i, its mirrored features row flip_row0 + i (flip_row0 = n
  * in the layout of pam_preprocess_crops_flip).  P / F: the head's maps of the two (the FMA chain of pam_head_heatmaps, bit for bit).

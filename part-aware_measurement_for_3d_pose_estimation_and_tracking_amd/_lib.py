@@ -113,6 +113,9 @@ _SIGS = {
     'pam_preprocess_crops': (_I, [_P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
     'pam_preprocess_crops_ex': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I]),
     'pam_preprocess_crops_flip': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I]),
+    'pam_preprocess_crops_affine': (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, C.c_float, _I, _I, _I, _P, _I, _P]),
+    'pam_box_cs': (_I, [_P, _I, _P, _I, _I, C.c_float, _P]),
+    'pam_box_cs_host': (_I, [_I, _P, _I, _I, C.c_float, _P]),
     'pam_decode_heatmaps': (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
     'pam_clock_probe': (_I, [_P, _P, _I]),
     'pam_conv2d_nhwc_bf16': (_I, [_P, _P, _P, _P, _P, _P, _P] + [_I] * 11),
@@ -697,6 +700,43 @@ def crop_table(stream, boxes, count, frame_w, frame_h, max_dets, view_of, slot_o
                                C.c_void_p(xywh.data_ptr()), C.c_void_p(n_det.data_ptr()), C.c_void_p(info.data_ptr()))
     if rc != 0:
         raise PamError('pam_crop_table failed (%d)' % rc)
+
+
+BOX_TRANSFORMS = ('stretch', 'affine')     # HRNetPose(box_transform=): the raw box stretched to the input, or the checkpoints' own transform
+BOX_SCALE = 1.25                           # _box2cs's enlargement
+
+
+def check_box_transform(box_transform, box_scale=BOX_SCALE):
+    """(box_transform, box_scale) as HRNetPose takes them -> (name, float scale); anything but 'stretch' / 'affine', or a scale that is
+    not > 0, is a ValueError.  None stands for the default of either (a YAML without the optional keys)."""
+    name = 'stretch' if box_transform is None else box_transform
+    if name not in BOX_TRANSFORMS:
+        raise ValueError("box_transform must be 'stretch' or 'affine' (got %r)" % (box_transform,))
+    scale = BOX_SCALE if box_scale is None else float(box_scale)
+    if not scale > 0.0:
+        raise ValueError('box_scale must be > 0 (got %r)' % (box_scale,))
+    return name, scale
+
+
+def box_cs(boxes, out_w, out_h, scale=BOX_SCALE):
+    """The effective boxes of person boxes (n, 4) xywh for a network input of out_w x out_h on the host (pam_box_cs_host; the
+    transform: include/pam.h) -> (n, 4) float32, bit for bit what pam_box_cs and the affine crop launch leave on the device."""
+    b = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 4)
+    out = np.empty_like(b)
+    rc = load().pam_box_cs_host(len(b), _ptr(b), int(out_w), int(out_h), float(scale), _ptr(out))
+    if rc != 0:
+        raise PamError('pam_box_cs_host failed (%d)' % rc)
+    return out
+
+
+def box_cs_dev(stream, boxes, out_w, out_h, scale, eff):
+    """pam_box_cs: boxes (n, 4) float32 device rows -> eff (n, 4) float32, the whole table in one launch on ``stream``."""
+    n = int(boxes.numel()) // 4
+    assert eff.numel() >= 4 * n and boxes.is_contiguous() and eff.is_contiguous()
+    rc = load().pam_box_cs(C.c_void_p(stream), n, C.c_void_p(boxes.data_ptr()), int(out_w), int(out_h), float(scale),
+                           C.c_void_p(eff.data_ptr()))
+    if rc != 0:
+        raise PamError('pam_box_cs failed (%d)' % rc)
 
 
 def pose_nms(stream, det, n_det_in, view_of, slot_of, xywh, n_det_out, keep_from, pose_score, max_dets=None, score=None,

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "../../include/pam.h"
 #include "pam_kernel.hpp"
+#include "pam_box_cs.hpp"
 
 #define J PAM_J
 
@@ -28,6 +29,25 @@ constexpr int AA_MAXT = 24;             // taps per axis at most (down-scaling b
 #include "pam_crop_kernel.inc"
 #undef CROP_KERNEL
 #undef CROP_FLIP
+// The pose checkpoints' own crop geometry (pam_box_cs.hpp, pam_crop_affine_kernel.inc): the box widened to the input's aspect about its
+// centre and enlarged, sampled with ONE scale and a zero border -- forms NEXT to the two above, whose instructions stay what they were.
+#define CROP_KERNEL k_preprocess_crops_affine
+#define CROP_FLIP 0
+#include "pam_crop_affine_kernel.inc"
+#undef CROP_KERNEL
+#undef CROP_FLIP
+#define CROP_KERNEL k_preprocess_crops_affine_flip
+#define CROP_FLIP 1
+#include "pam_crop_affine_kernel.inc"
+#undef CROP_KERNEL
+#undef CROP_FLIP
+// the whole effective-box table without a crop (a rank of the crop-sharded predict() crops its share but filters every row)
+__global__ __launch_bounds__(256) void k_box_cs(int n, const float* __restrict__ boxes, int ow, int oh, float box_scale, float* __restrict__ eff) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const PamBoxCs e = pam_box_cs_fn(boxes[i * 4 + 0], boxes[i * 4 + 1], boxes[i * 4 + 2], boxes[i * 4 + 3], ow, oh, box_scale);
+    eff[i * 4 + 0] = e.x; eff[i * 4 + 1] = e.y; eff[i * 4 + 2] = e.w; eff[i * 4 + 3] = e.h;
+}
 
 struct Best { float v; int i; };
 __device__ __forceinline__ Best better(Best a, Best b) {    // larger value wins; ties -> smaller flat index (np.argmax)
@@ -690,6 +710,41 @@ extern "C" int pam_preprocess_crops_flip(void* stream, int n, int n_total, const
     hipLaunchKernelGGL(k_preprocess_crops_flip, grid, dim3(256), 0, (hipStream_t)stream, n, (const uint8_t* const*)dev_frames,
                        frame_h, frame_w, dev_view_of, dev_boxes, out_h, out_w, out_c, (uint16_t*)dev_out_bf16, antialias ? 1 : 0);
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+}
+
+extern "C" int pam_preprocess_crops_affine(void* stream, int n, int n_total, int flip, const void* const* dev_frames, int frame_h, int frame_w,
+                                           const int32_t* dev_view_of, const float* dev_boxes, float box_scale, int out_h, int out_w,
+                                           int out_c, void* dev_out_bf16, int antialias, float* dev_eff_xywh) {
+    if (n < 0 || n_total < (flip ? 2 : 1) * (long long)n || !dev_frames || !dev_view_of || !dev_boxes || !dev_out_bf16 || out_h <= 0 ||
+        out_w <= 0 || (out_c != 3 && out_c != 8) || !dev_eff_xywh || !(box_scale > 0.0f))
+        return PAM_E_ARG;
+    if (n == 0) return PAM_OK;
+    dim3 grid((out_h * out_w + 255) / 256, n_total);
+    if (flip)
+        hipLaunchKernelGGL(k_preprocess_crops_affine_flip, grid, dim3(256), 0, (hipStream_t)stream, n, (const uint8_t* const*)dev_frames,
+                           frame_h, frame_w, dev_view_of, dev_boxes, box_scale, out_h, out_w, out_c, (uint16_t*)dev_out_bf16,
+                           antialias ? 1 : 0, dev_eff_xywh);
+    else
+        hipLaunchKernelGGL(k_preprocess_crops_affine, grid, dim3(256), 0, (hipStream_t)stream, n, (const uint8_t* const*)dev_frames,
+                           frame_h, frame_w, dev_view_of, dev_boxes, box_scale, out_h, out_w, out_c, (uint16_t*)dev_out_bf16,
+                           antialias ? 1 : 0, dev_eff_xywh);
+    return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+}
+
+extern "C" int pam_box_cs(void* stream, int n, const float* dev_boxes, int out_w, int out_h, float box_scale, float* dev_eff_xywh) {
+    if (n < 0 || !dev_boxes || !dev_eff_xywh || out_w <= 0 || out_h <= 0 || !(box_scale > 0.0f)) return PAM_E_ARG;
+    if (n == 0) return PAM_OK;
+    hipLaunchKernelGGL(k_box_cs, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, n, dev_boxes, out_w, out_h, box_scale, dev_eff_xywh);
+    return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+}
+
+extern "C" int pam_box_cs_host(int n, const float* boxes, int out_w, int out_h, float box_scale, float* eff) {
+    if (n < 0 || (n > 0 && (!boxes || !eff)) || out_w <= 0 || out_h <= 0 || !(box_scale > 0.0f)) return PAM_E_ARG;
+    for (int i = 0; i < n; ++i) {
+        const PamBoxCs e = pam_box_cs_fn(boxes[i * 4 + 0], boxes[i * 4 + 1], boxes[i * 4 + 2], boxes[i * 4 + 3], out_w, out_h, box_scale);
+        eff[i * 4 + 0] = e.x; eff[i * 4 + 1] = e.y; eff[i * 4 + 2] = e.w; eff[i * 4 + 3] = e.h;
+    }
+    return PAM_OK;
 }
 
 extern "C" int pam_decode_heatmaps(void* stream, int n, const float* dev_heatmaps, int nchw, int hm_h, int hm_w,

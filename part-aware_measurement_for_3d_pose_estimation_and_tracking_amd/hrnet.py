@@ -39,8 +39,10 @@ class HRNetPose(ForwardReplay):
     def __init__(self, c, nof_joints, checkpoint_path, model_name='HRNet', resolution=(384, 288), hrpose_args=None,
                  device=0, dtype=torch.bfloat16, use_graph=True, seed=0, max_dets=16, backend='hip', graph_bucket=4,
                  shard_crops=False, group=None, autotune=False, max_crops=32, antialias=False, flip_test=False, shift_heatmap=True,
-                 post_process=False, soft_beta=None, dark=False, blur_kernel=None, pose_nms=False, oks_thre=0.9, in_vis_thre=0.2):
+                 post_process=False, soft_beta=None, dark=False, blur_kernel=None, pose_nms=False, oks_thre=0.9, in_vis_thre=0.2,
+                 box_transform='stretch', box_scale=_lib.BOX_SCALE):
         # the decode options first: a refused combination raises before anything touches a device
+        self.box_transform, self.box_scale = _lib.check_box_transform(box_transform, box_scale)
         self.soft_beta, self.flip_test, self.shift_heatmap, self.post_process = soft_beta, flip_test, shift_heatmap, post_process
         self.dark, self.blur_kernel = dark, blur_kernel
         self.pose_nms, self.oks_thre, self.in_vis_thre = bool(pose_nms), float(oks_thre), float(in_vis_thre)
@@ -180,12 +182,28 @@ class HRNetPose(ForwardReplay):
         return torch.empty((n, self.in_channels, H, W), dtype=self.dtype, device=self.device, memory_format=torch.channels_last)
 
     # -- HIP kernels around it -----------------------------------------------------------------------------------------
-    def preprocess(self, frame_ptrs, frame_h, frame_w, view_of, boxes, out):
+    def preprocess(self, frame_ptrs, frame_h, frame_w, view_of, boxes, out, eff=None):
         """frame_ptrs: int64 device tensor of per-view frame addresses; view_of int32 (N), boxes float32 (N,4) xywh.  out may hold more
         crops than N (a replay bucket): the extra ones repeat the last crop.  Under the flip test out (``input_buffer``) holds at least
-        2N rows: N plain crops, their N mirrors, then repeats of the last mirror."""
+        2N rows: N plain crops, their N mirrors, then repeats of the last mirror.
+        box_transform='affine': the crops come from the boxes' effective boxes (pam_preprocess_crops_affine; the transform:
+        include/pam.h), which the launch leaves in eff (N,4) float32 -- the table ``head_decode`` and the OKS-NMS take in place of
+        ``boxes``; eff=None: a table of the call's own that nobody reads.  'stretch' never touches eff."""
         H, W = self.resolution
         st = torch.cuda.current_stream(self.device).cuda_stream
+        if self.box_transform == 'affine':
+            n = int(view_of.numel())
+            if eff is None:
+                eff = torch.empty((max(n, 1), 4), dtype=torch.float32, device=self.device)
+            assert eff.is_contiguous() and eff.dtype == torch.float32 and eff.numel() >= 4 * n
+            rc = self.lib.pam_preprocess_crops_affine(C.c_void_p(st), n, int(out.shape[0]), 1 if self.flip_test else 0,
+                                                      C.c_void_p(frame_ptrs.data_ptr()), int(frame_h), int(frame_w),
+                                                      C.c_void_p(view_of.data_ptr()), C.c_void_p(boxes.data_ptr()), float(self.box_scale),
+                                                      H, W, int(out.shape[1]), C.c_void_p(out.data_ptr()), 1 if self.antialias else 0,
+                                                      C.c_void_p(eff.data_ptr()))
+            if rc != 0:
+                raise _lib.PamError('pam_preprocess_crops_affine failed: %d' % rc)
+            return
         fn = self.lib.pam_preprocess_crops_flip if self.flip_test else self.lib.pam_preprocess_crops_ex
         rc = fn(C.c_void_p(st), int(view_of.numel()), int(out.shape[0]), C.c_void_p(frame_ptrs.data_ptr()),
                 int(frame_h), int(frame_w), C.c_void_p(view_of.data_ptr()),
@@ -226,7 +244,17 @@ class HRNetPose(ForwardReplay):
     #                  decode above (it runs after whichever ran).  Off: predict() issues exactly the launches it issued without it.
     _soft_beta, _flip_test, _post_process, _dark, _blur_kernel, shift_heatmap = None, False, False, False, None, True
     pose_nms, oks_thre, in_vis_thre = False, 0.9, 0.2
-    #   lens           (set_lens) the rig's lens table: behind the last decode of a predict() call -- and behind pose_nms, whose OKS areas
+    #   box_transform  'stretch' (the default, what every golden of this repository was made with): the raw box resized to the input
+    #                  whatever its shape.  'affine': the geometry the published HRNet / Simple Baselines / DARK checkpoints were trained
+    #                  and evaluated with (_box2cs + get_affine_transform + warpAffine + transform_preds): the box widened to the input's
+    #                  aspect about its centre, enlarged by box_scale, sampled with one scale and a zero border; the decode maps heat-map
+    #                  cells back through the same effective box and pose_nms takes its areas from it (include/pam.h).  The dump's 'bbox'
+    #                  stays the caller's box.  Constructor arguments (validated there: _lib.check_box_transform); the forwards keep their
+    #                  size.  'stretch': every entry point makes exactly the calls it made without the option.
+    #   box_scale      _box2cs's enlargement, 1.25.  Boxes that already carry a margin (pam_track_boxes' TRACK_BOX_GROW 1.25) are
+    #                  enlarged again: the two factors multiply.
+    box_transform, box_scale = 'stretch', _lib.BOX_SCALE
+    #   lens          (set_lens) the rig's lens table: behind the last decode of a predict() call -- and behind pose_nms, whose OKS areas
     #                  come from raw-image boxes -- the TRACKER's float64 copy of the keypoints is undistorted in place on the device
     #                  (pam_undistort_keypoints).  The host keypoints and the dump's dicts stay in raw-image pixels.  None: predict()
     #                  issues exactly the launches it issued without it.
@@ -400,6 +428,11 @@ class HRNetPose(ForwardReplay):
         ptrs = m[o_ptr:o_ptr + 2 * V].view(torch.int64)
         det = torch.empty((V, S, 17, 3), dtype=torch.float64, device=self.device)
         kp = torch.empty((n, 17, 3), dtype=torch.float32, device=self.device)
+        # box_transform='affine': the call's effective boxes, written by the crop launches (every row by pam_box_cs first when the crops
+        # are sharded: a rank crops its share and filters all) and read by the decode and the filter in place of bx
+        affine = self.box_transform == 'affine'
+        eff = torch.empty((n, 4), dtype=torch.float32, device=self.device) if affine else None
+        dbx = eff if affine else bx
         lo, hi = 0, n
         if self.world > 1:                                # this rank's share of the call's crops (ordered by view, then person)
             from .distributed import crop_partition, check_same_call
@@ -422,13 +455,19 @@ class HRNetPose(ForwardReplay):
             """The device side of this call (crop -> conv stack -> head + arg-max per batch, the exchange, the copy of the keypoints to
             pinned host memory); DumpResults runs it again when a gate of one of its forwards gave up (clear_void first)."""
             kpl = kp
+            if affine and self.world > 1:
+                _lib.box_cs_dev(torch.cuda.current_stream(self.device).cuda_stream, bx, self.resolution[1], self.resolution[0],
+                                self.box_scale, eff)
             for s in range(lo, hi, batch_size):
                 e = min(hi, s + batch_size)
                 k = e - s
                 mp = min(batch_size, (k + self.graph_bucket - 1) // self.graph_bucket * self.graph_bucket) if batch_size >= self.graph_bucket else k
                 x = self.input_buffer(mp)                    # mp > k: the crop kernel repeats the last crop into the bucket's spare rows
-                self.preprocess(ptrs, fh, fw, view_of[s:e], bx[s:e], x)
-                self.head_decode(self.features(x), view_of[s:e], slot_of[s:e], bx[s:e], det, kp[s:e], n=k)
+                if affine:
+                    self.preprocess(ptrs, fh, fw, view_of[s:e], bx[s:e], x, eff=eff[s:e])
+                else:
+                    self.preprocess(ptrs, fh, fw, view_of[s:e], bx[s:e], x)
+                self.head_decode(self.features(x), view_of[s:e], slot_of[s:e], dbx[s:e], det, kp[s:e], n=k)
             if self.world > 1:
                 from .distributed import gather_crop_keypoints
                 kpl = gather_crop_keypoints(kp[lo:hi].contiguous(), n, self.world, self.rank, self.group)
@@ -437,7 +476,7 @@ class HRNetPose(ForwardReplay):
             if nms:
                 # behind the last decode of the call (the assembled buffer on every rank when the crops are sharded), from the ORIGINAL
                 # counts: a redo after a void forward decodes and filters again
-                _lib.pose_nms(torch.cuda.current_stream(self.device).cuda_stream, det, n_det, view_of, slot_of, bx, nms_dev[0][:V],
+                _lib.pose_nms(torch.cuda.current_stream(self.device).cuda_stream, det, n_det, view_of, slot_of, dbx, nms_dev[0][:V],
                               nms_dev[0][V:], nms_dev[1], score=nms_dev[2], score_strides=(S, 1), oks_thre=self.oks_thre,
                               in_vis_thre=self.in_vis_thre)
                 nms_host[0].copy_(nms_dev[0], non_blocking=True)
@@ -459,7 +498,7 @@ class HRNetPose(ForwardReplay):
         out.attach_pending(det, nms_dev[0][:V] if nms else n_det, host, issue(), views, boxes, cnt)
         if nms:
             out._nms = (nms_host[0], nms_host[1], V, S)
-        out._net, out._issue = self, issue
+        out._net, out._issue, out.device_eff = self, issue, eff
         import weakref
         self._kp_last[1] = weakref.ref(out)
         return out

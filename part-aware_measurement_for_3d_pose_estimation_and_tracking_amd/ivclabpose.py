@@ -29,6 +29,15 @@ def one_euro_from_matcher(m):
     return {} if blk is True else {str(k).lower(): v for k, v in dict(blk).items()}
 
 
+def box_transform_options(p):
+    """The optional keys BOX_TRANSFORM / BOX_SCALE of a POSE_MODELS.HRPOSE block (not in the reference's YAMLs) -> (box_transform,
+    box_scale) as HRNetPose takes them; absent keys give ('stretch', 1.25), a BOX_TRANSFORM other than 'stretch' / 'affine' or a
+    BOX_SCALE that is not > 0 is a ValueError (_lib.check_box_transform)."""
+    from . import _lib
+    opt = lambda k: p.get(k) if isinstance(p, dict) else getattr(p, k, None)
+    return _lib.check_box_transform(opt('BOX_TRANSFORM'), opt('BOX_SCALE'))
+
+
 class Camera(object):
     """Calibrated view: P, K, RT (float32), F[other] (float32), RK_INV (float32), position (float64).
     distCoef (not in the reference, whose lens methods are identity stubs): (k1, k2, p1, p2, k3) of the camera's lens, OpenCV / Panoptic
@@ -159,13 +168,17 @@ class ivclabpose(object):
             # ivclabpose.py:107-111: gpu_args = every visible GPU.  One process drives ONE of them (`device`); several GPUs = several
             # ranks of a torch.distributed job, and HRNetPose.predict shards each call's crops over them (see HRNetPose.__init__).
             gpu_args = _Args(gpus=list(range(torch.cuda.device_count())), device=torch.device('cuda:%d' % device))
+            # optional keys BOX_TRANSFORM ('stretch' | 'affine') / BOX_SCALE: the crop geometry; 'affine' = the published checkpoints' own
+            # (_box2cs + get_affine_transform: aspect fix about the centre, x BOX_SCALE 1.25, zero border; decode and OKS-NMS through the
+            # same effective box).  Absent: the raw box stretched to the input, as before.  Another value is refused (ValueError).
+            box_transform, box_scale = box_transform_options(self.pose_detector)
             self.pose_model = HRNetPose(_cfg(self.pose_detector, 'C'), _cfg(self.pose_detector, 'NUM_JOINTS'),
                                         _cfg(self.pose_detector, 'CHECKPOINT_FILE'),
                                         model_name=_cfg(self.pose_detector, 'MODEL_NAME'),
                                         resolution=tuple(_cfg(self.pose_detector, 'RESOLUTION')), hrpose_args=gpu_args,
                                         device=device, max_dets=max_dets,
                                         shard_crops=torch.distributed.is_available() and torch.distributed.is_initialized(),
-                                        autotune=autotune)
+                                        autotune=autotune, box_transform=box_transform, box_scale=box_scale)
             # optional key (not in the reference's YAMLs): SOFT_ARGMAX_BETA > 0 switches the decode from the hard arg-max (parity mode)
             # to the soft-arg-max of pam_head_decode_soft with that inverse temperature
             sb = self.pose_detector.get('SOFT_ARGMAX_BETA') if isinstance(self.pose_detector, dict) else getattr(self.pose_detector, 'SOFT_ARGMAX_BETA', None)

@@ -36,7 +36,7 @@ class FramePipeline(object):
                  rank=0, group=None, use_graph=True, hrnet=True, seed=0, shard='views', overlap_tracker=False, net=None, exchange='torch',
                  pose_streams=1, autotune=True, prewarm=False, width=48, resolution=(384, 288), flip_test=False, shift_heatmap=True,
                  post_process=False, model_name='HRNet', crop_cap=None, detect_every=1, dark=False, blur_kernel=None, pose_nms=False,
-                 oks_thre=0.9, in_vis_thre=0.2, lens=None, one_euro=None, overlay=None):
+                 oks_thre=0.9, in_vis_thre=0.2, lens=None, one_euro=None, overlay=None, box_transform='stretch', box_scale=_lib.BOX_SCALE):
         """shard: 'views' -- rank owns whole camera views (pose_step / track_step take view-local inputs); 'crops' -- the
         frame's crops are dealt out evenly over the ranks (pose_step_crops / track_step_crops take global view indices).
         overlap_tracker (either mode): exchange + tracker kernel + fetch of frame t run on their own stream, under the conv
@@ -78,7 +78,14 @@ class FramePipeline(object):
         overlay: dict(view3d=None | dict(size=(width, height), azimuth=, elevation=, up=), emitted_only=True) switches ``overlay_step``
         on: the tracks drawn into this rank's CUDA frames -- and into a free-viewpoint 3D canvas when view3d is given -- straight from
         the device-resident state (pam_overlay_tracks + pam_overlay_draw_counted; the rules: include/pam.h), the One-Euro poses when
-        one_euro is on.  Needs shard='views'.  None: no step, no buffer, the launches of before."""
+        one_euro is on.  Needs shard='views'.  None: no step, no buffer, the launches of before.
+        box_transform / box_scale: that network's crop geometry (HRNetPose): 'affine' crops every box of pose_step, pose_step_boxes,
+        pose_step_auto and pose_step_crops through the pose checkpoints' centre/scale transform (include/pam.h); the crop launch leaves
+        the frame's effective boxes in a device table beside the other per-frame buffers (``eff_table``, sized for the bucket cap, one per
+        replay slot) and decode and pose_nms read that table in place of the boxes.  pam_crop_table and pam_track_boxes are unchanged and
+        still deliver raw clamped boxes: on a track-box frame TRACK_BOX_GROW 1.25 and BOX_SCALE 1.25 MULTIPLY (a box 1.56 x the
+        keypoints' extent); both defaults are left alone.  A shared `net` keeps its own setting.  'stretch': the launches of before."""
+        box_transform, box_scale = _lib.check_box_transform(box_transform, box_scale)
         if overlay is not None and shard == 'crops':
             raise ValueError("overlay needs shard='views': a rank draws the frames of the views it owns")
         lens = _lib.check_lens(lens, len(calib_cameras))
@@ -117,7 +124,8 @@ class FramePipeline(object):
                                                           max_crops=len(calib_cameras) * max_dets, flip_test=flip_test,
                                                           shift_heatmap=shift_heatmap, post_process=post_process, dark=dark,
                                                           blur_kernel=blur_kernel, pose_nms=pose_nms, oks_thre=oks_thre,
-                                                          in_vis_thre=in_vis_thre) if hrnet else None)
+                                                          in_vis_thre=in_vis_thre, box_transform=box_transform,
+                                                          box_scale=box_scale) if hrnet else None)
         self.shard = shard
         # exchange: 'torch' = torch.distributed (RCCL when the backend is nccl, gloo in the CPU tests); 'abi' = pam_allgather_keypoints,
         # the library's own RCCL call on the decode stream (view sharding only)
@@ -170,6 +178,12 @@ class FramePipeline(object):
         if self.bucketed and self.net is not None:
             self.crop_cap = self.net.bucket(self.crop_cap)
         self._tables, self._tb, self._table_info, self.table_n_det = None, None, None, None
+        # box_transform='affine': the effective boxes of a frame, written by its crop launch and read by its decode and filter; one table
+        # per replay slot (two frames in flight), rows for the largest frame this rank can see, rounded up to the bucket as crop_cap is
+        # (built here when the network has the option on, else at the first frame of a shared net whose owner switches it on later)
+        self.eff_table = None
+        if self.net is not None and self.net.box_transform == 'affine':
+            self._eff_rows(0, 0)
         self._ct_host = torch.zeros(4, dtype=torch.int32).pin_memory()
         self._ct_fetched = False
         self._ev_slot_read, self._table_no, self._table_slot = [None, None], 0, 0
@@ -313,7 +327,12 @@ class FramePipeline(object):
         k = (self._frame_no & 1) if self.pose_streams is not None else 0
         n = int(views.numel())
         x = self.net.input_buffer(self.net.bucket(n) if self.bucketed else n, k)     # a bucket's spare rows repeat the last crop, undecoded
-        self.net.preprocess(frame_ptrs, self.frame_h, self.frame_w, views, boxes, x)
+        if self.net.box_transform == 'affine':
+            eff = self._eff_rows(k, n)
+            self.net.preprocess(frame_ptrs, self.frame_h, self.frame_w, views, boxes, x, eff=eff)
+            boxes = eff                                  # decode and filter go through the effective boxes (transform_preds)
+        else:
+            self.net.preprocess(frame_ptrs, self.frame_h, self.frame_w, views, boxes, x)
         if after_crop is not None:
             after_crop()                                # the frames have been read: a feeder may mark its buffers reusable here
         if time_events is not None:
@@ -330,6 +349,18 @@ class FramePipeline(object):
             self._nms_live = True
         if self.lens is not None:
             self.undistort_local(self.nms_n_det if self.pose_nms else n_det)
+
+    def _eff_rows(self, k, n):
+        """The first n rows of replay slot k's effective-box table (box_transform='affine'); the tables hold the largest frame this rank
+        can see -- crop_cap or every view x max_dets, rounded up to the bucket as crop_cap is -- and one grows for a longer caller's table."""
+        if self.eff_table is None:
+            rows = max(self.crop_cap, self.C * self.max_dets)
+            rows = self.net.bucket(rows) if self.bucketed else rows
+            self.eff_table = [torch.zeros((rows, 4), dtype=torch.float32, device=self.device)
+                              for _ in range(len(self.pose_streams) if self.pose_streams is not None else 1)]
+        if n > self.eff_table[k].shape[0]:
+            self.eff_table[k] = torch.zeros((n, 4), dtype=torch.float32, device=self.device)
+        return self.eff_table[k][:n]
 
     def undistort_local(self, n_det):
         """Lens distortion out of this rank's rows, in place in ``self.det_local`` (decode, write_local), behind whatever the current
