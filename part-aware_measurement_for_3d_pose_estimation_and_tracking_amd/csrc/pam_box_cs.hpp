@@ -1,4 +1,4 @@
-// The pose checkpoints' box transform, ONE definition for the crop kernel, the table kernel and the host entry (pam_image.hip).
+// The pose checkpoints' box transform, ONE definition for the crop kernel, the table kernel and the host entry (pam_crop.hip).
 // Official HRNet / Simple Baselines / DARK test code: _box2cs (centre + scale from the box: the box widened to the input's aspect ratio
 // about its centre, then enlarged by 1.25), get_affine_transform without rotation (a uniform scale about the centre) and transform_preds
 // (heat-map cells back through the same enlarged box).  All three are this function: the EFFECTIVE box (xe, ye, We, He) is what the crop

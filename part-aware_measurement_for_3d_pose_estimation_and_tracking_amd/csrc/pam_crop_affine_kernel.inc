@@ -1,5 +1,8 @@
-// The affine crop kernel's text, included once per form by pam_image.hip with CROP_KERNEL (the kernel's name) and CROP_FLIP defined, as
-// pam_crop_kernel.inc is; row layout, bucket padding and the mirrored store are that file's.
+// The affine crop kernel's text, included once per form by pam_crop.hip with CROP_KERNEL (the kernel's name) and CROP_FLIP defined.
+// CROP_FLIP 0: rows n_src .. (grid) repeat row n_src - 1.  CROP_FLIP 1: rows [0, n_src) plain, rows [n_src, 2 n_src) the same samples stored
+// at column ow - 1 - ox, rows from 2 n_src on repeat row 2 n_src - 1 (crop_row / store_pixel of pam_crop.hip, in this file's own statements).
+// It is no template behind two wrappers as the stretch form is: behind one, the same text compiled to another prologue and the launch
+// at 20 crops measured 0.4 % above the range of the parent's own rounds (DESIGN.md, section 10p).
 // The box each row samples is the EFFECTIVE box of pam_box_cs.hpp, computed inline from the raw box (uniform per workgroup); thread 0 of
 // a plain row's first workgroup stores it to eff[row] for the decode and the OKS-NMS.  Rows >= n_src of eff are never written.
 // Sampling is warpAffine's convention: integer coordinates are pixel centres, output pixel (u, v) reads the frame at
@@ -39,7 +42,7 @@ __global__ __launch_bounds__(256) void CROP_KERNEL(int n_src, const uint8_t* con
                 const int y = y0 + k;
                 if (y < 0 || y >= H) continue;     // a row outside the frame: its two taps stay 0
                 const uint8_t* r = img + ((size_t)y * W) * 3;
-                // both pixels and the two bytes behind them inside the row: ONE unaligned 8-byte load (pam_crop_kernel.inc); else byte
+                // both pixels and the two bytes behind them inside the row: ONE unaligned 8-byte load (load_two_pixels in pam_crop.hip); else byte
                 // loads of the pixels that exist
                 if (x0 >= 0 && x0 + 2 < W) {
                     struct __attribute__((packed)) U8 { uint32_t x, y; };

@@ -4,7 +4,7 @@
 The conv stack is the hand-written HIP executor of hrnet_hip.py (MFMA kernels of csrc/, bf16 channels-last, BatchNorm folded), replayed
 from a hipGraph per crop count (replay.ForwardReplay).  The PyTorch module of hrnet_model.py / poseresnet.py is the weight container the
 executor packs (official state-dict key layout, so the published checkpoints load) and the fp32 checker; no forward runs through it.
-Crop / resize / normalise and the head + arg-max decode are HIP kernels of libpam_hip.so (csrc/pam_image.hip).
+Crop / resize / normalise and the head + arg-max decode are HIP kernels of libpam_hip.so (csrc/pam_crop.hip, csrc/pam_head.hip).
 Parity with the authors' modified backend is UNPINNED (no source, weights or tests in the reference): decode follows
 upstream simple-HRNet (hard arg-max, linear map through the box)."""
 import ctypes as C
@@ -104,7 +104,7 @@ class HRNetPose(ForwardReplay):
         self.model = None
         # crop resize: False = plain bilinear (cv2.resize INTER_LINEAR semantics; the default: exact for boxes up to the network input, and what
         # every golden of this repository was made with); True = upstream simple-HRNet's PIL / torchvision Resize, which filters with a triangle
-        # that widens with the down-scaling factor (HD Panoptic boxes taller than 384 pixels) -- csrc/pam_image.hip
+        # that widens with the down-scaling factor (HD Panoptic boxes taller than 384 pixels) -- csrc/pam_crop.hip
         self.antialias = bool(antialias)
         self._init_replay(use_graph, graph_bucket, max_crops)
         if self.world > 1:

@@ -1,4 +1,4 @@
-"""Float64 restatement of the DARK decode (csrc/pam_image.hip: k_dark_finish; contract in include/pam.h, pam_head_decode_dark) with
+"""Float64 restatement of the DARK decode (csrc/pam_head.hip: k_dark_finish; contract in include/pam.h, pam_head_decode_dark) with
 derived bounds, NumPy only: dark64 (the offsets at given arg-max cells, a per-case bound and a `decided` mask), official_dark (an
 independent statement of the published steps on scipy.ndimage, sharing no code with dark64) and the inputs of tests/test_gpu_dark.py,
 so that the CPU tests (tests/test_dark_ref.py) judge the same data the GPU tests run on.

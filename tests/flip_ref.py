@@ -1,4 +1,4 @@
-"""Float64 restatement of the flip test (csrc/pam_image.hip: k_head_argmax_flip, k_argmax_finish_flip) with derived bounds, NumPy only:
+"""Float64 restatement of the flip test (csrc/pam_head.hip: k_head_argmax_flip, k_argmax_finish_flip) with derived bounds, NumPy only:
 the merge of a plain and a mirrored-back heat-map (merge64), the quarter-pixel offset of the official get_final_preds (quarter64), an
 independent torch statement of the official steps (official_merge / official_offsets) and the inputs of tests/test_gpu_flip.py, so that
 the CPU tests (tests/test_flip_ref.py) judge the same data the GPU tests run on.  Bounds come from image_ref.head64 (the float32 FMA

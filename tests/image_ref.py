@@ -1,4 +1,4 @@
-"""Float64 restatements of the image-side kernels (csrc/pam_image.hip) with DERIVED per-element tolerances, NumPy only, no GPU:
+"""Float64 restatements of the image-side kernels (csrc/pam_crop.hip, csrc/pam_head.hip) with DERIVED per-element tolerances, NumPy only, no GPU:
 the crop kernel (preprocess64 / crop_check), the final 1x1 convolution (head64), the hard and soft arg-max decodes (argmax_check,
 soft64) and the box mapping (decode64).  Nothing in a tolerance here is tuned against the kernels: each term is a rounding bound of a
 number format or the sensitivity of the float64 reference itself to the roundings the float32 kernel may make.  tests/test_image_ref.py

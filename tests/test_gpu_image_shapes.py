@@ -1,4 +1,4 @@
-"""GPU: the image-side kernels (csrc/pam_image.hip) through the C ABI against the float64 restatements of tests/image_ref.py, at the
+"""GPU: the image-side kernels (csrc/pam_crop.hip, csrc/pam_head.hip) through the C ABI against the float64 restatements of tests/image_ref.py, at the
 shapes of every network that ships on them: head channels 32 / 48 / 256 (HRNet-W32, HRNet-W48, PoseResNet), heat-maps 64 x 48 and
 96 x 72 plus ragged sizes, crops at 256 x 192 and 384 x 288.  Every output sits between sentinel guard bands; rows of crops that a call
 does not cover must keep their sentinel.  Tolerances are the derived ones of image_ref (FMA-chain bound, bf16 half-ulp + coordinate

@@ -7,8 +7,11 @@ kernel's .amdgpu_metadata entry must be equal after three normalisations: assemb
 (.LBB / .Lfunc_end / .Ltmp), renumbered in order of appearance because their function index moves with definition order.
 Kernels are pooled by symbol over all files of a directory, so a kernel that moved to another source file is still compared; the
 report names the file(s) it sits in.
-usage: device_code_diff.py OLD_DIR NEW_DIR      exit status 1 when a kernel differs or exists on one side only
+usage: device_code_diff.py OLD_DIR NEW_DIR [--explain]     exit status 1 when a kernel differs or exists on one side only
+--explain: under every kernel that differs, the instruction count of each side, the mnemonics whose counts changed and the descriptor /
+metadata lines that changed -- what a restructured kernel is judged by (tools/README.md).
 """
+import collections
 import pathlib
 import re
 import sys
@@ -55,7 +58,28 @@ def pool(directory):
     return out
 
 
-def main(old_dir, new_dir):
+def mnemonics(body):
+    """Counter of instruction mnemonics of a normalised body (labels and directives are no instructions)."""
+    words = (l.split()[0] for l in body.splitlines() if l.strip())
+    return collections.Counter(w for w in words if not w.endswith(":") and not w.startswith("."))
+
+
+def explain(old, new):
+    """Lines for one differing kernel: [body, descriptor, metadata] of each side."""
+    a, b = mnemonics(old[0]), mnemonics(new[0])
+    out = ["    instructions: %d -> %d" % (sum(a.values()), sum(b.values()))]
+    moved = ["%s %d -> %d" % (m, a[m], b[m]) for m in sorted(a.keys() | b.keys()) if a[m] != b[m]]
+    out.append("    mnemonic counts: " + (", ".join(moved) if moved else "all equal (order or registers only)"))
+    for part, x, y in (("descriptor", old[1], new[1]), ("metadata", old[2], new[2])):
+        xs, ys = x.splitlines(), y.splitlines()
+        for l in [l for l in xs if l not in ys]:
+            out.append("    %s old: %s" % (part, l.strip()))
+        for l in [l for l in ys if l not in xs]:
+            out.append("    %s new: %s" % (part, l.strip()))
+    return out
+
+
+def main(old_dir, new_dir, verbose=False):
     a, b = pool(old_dir), pool(new_dir)
     bad = 0
     for k in sorted(a.keys() | b.keys()):
@@ -66,9 +90,12 @@ def main(old_dir, new_dir):
         elif a[k][1] != b[k][1]:
             bad += 1
             print("%s: %s differs (%s)" % (where, k, ", ".join(p for p, x, y in zip(("body", "descriptor", "metadata"), a[k][1], b[k][1]) if x != y)))
+            if verbose:
+                print("\n".join(explain(a[k][1], b[k][1])))
     print("%d kernels in old, %d in new, %d compared, %d differ" % (len(a), len(b), len(a.keys() | b.keys()), bad))
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    sys.exit(main(*sys.argv[1:3]))
+    dirs = [x for x in sys.argv[1:] if x != "--explain"]
+    sys.exit(main(dirs[0], dirs[1], "--explain" in sys.argv[1:]))
