@@ -19,11 +19,34 @@ def _cfg(obj, key):
     return obj[key] if isinstance(obj, dict) else getattr(obj, key)
 
 
+def _opt(block, key, default=None):
+    """An optional key of a config block (a dict or an attribute bag; the block itself may be missing)."""
+    if block is None:
+        return default
+    return block.get(key, default) if isinstance(block, dict) else getattr(block, key, default)
+
+
+# The optional keys of a POSE_MODELS.HRPOSE block that set a decode option of HRNetPose (none of them in the reference's YAMLs):
+# (key, attribute, conversion, set when the key is absent).  Applied in this order: the property setters refuse combinations
+# (HRNetPose._decode_option), so which error a bad YAML gets depends on it.
+#   SOFT_ARGMAX_BETA > 0: the soft-arg-max of pam_head_decode_soft with that inverse temperature in place of the hard arg-max (parity
+#   mode; 0 leaves it off)
+#   SHIFT_HEATMAP / POST_PROCESS / FLIP_TEST: the official names (TEST.* of the HRNet and Simple Baselines configs), off when absent: the
+#   protocol the published checkpoints were evaluated under
+#   BLUR_KERNEL / DARK: the DARK decode (Zhang et al., CVPR 2020); BLUR_KERNEL absent: 17 for maps of 96 rows or more, otherwise 11
+#   OKS_NMS / OKS_THRE / IN_VIS_THRE (TEST.OKS_THRE / TEST.IN_VIS_THRE; OKS_NMS switches the step on): every pose rescored and each
+#   view's duplicates removed on the device before the tracker (pam_pose_nms)
+POSE_OPTIONS = (('SOFT_ARGMAX_BETA', 'soft_beta', lambda v: float(v) or None, False), ('SHIFT_HEATMAP', 'shift_heatmap', bool, False),
+                ('POST_PROCESS', 'post_process', bool, True), ('BLUR_KERNEL', 'blur_kernel', int, False), ('DARK', 'dark', bool, True),
+                ('FLIP_TEST', 'flip_test', bool, True), ('OKS_NMS', 'pose_nms', bool, True), ('OKS_THRE', 'oks_thre', float, False),
+                ('IN_VIS_THRE', 'in_vis_thre', float, False))
+
+
 def one_euro_from_matcher(m):
     """The optional block ONE_EURO {FREQ, MINCUTOFF, BETA, DCUTOFF} of a PERSON_MATCHERS.ITERATIVE block (not in the reference's YAMLs,
     whose filters are built with fixed values and never called) -> the dict IterativeTracker(one_euro=) takes, keys in lower case, a
     missing key left to its default (_lib.ONE_EURO_3D); None when the block is absent."""
-    blk = m.get('ONE_EURO') if isinstance(m, dict) else getattr(m, 'ONE_EURO', None)
+    blk = _opt(m, 'ONE_EURO')
     if blk is None or blk is False:
         return None
     return {} if blk is True else {str(k).lower(): v for k, v in dict(blk).items()}
@@ -34,8 +57,7 @@ def box_transform_options(p):
     box_scale) as HRNetPose takes them; absent keys give ('stretch', 1.25), a BOX_TRANSFORM other than 'stretch' / 'affine' or a
     BOX_SCALE that is not > 0 is a ValueError (_lib.check_box_transform)."""
     from . import _lib
-    opt = lambda k: p.get(k) if isinstance(p, dict) else getattr(p, k, None)
-    return _lib.check_box_transform(opt('BOX_TRANSFORM'), opt('BOX_SCALE'))
+    return _lib.check_box_transform(_opt(p, 'BOX_TRANSFORM'), _opt(p, 'BOX_SCALE'))
 
 
 class Camera(object):
@@ -133,13 +155,11 @@ class ivclabpose(object):
         # the detector on every K-th frame and takes the boxes of the frames in between from the tracks (PersonBoxesFromTracks);
         # TRACK_BOX_GROW / TRACK_BOX_PAD = that box rule's growth and pad in pixels
         from . import _lib
-        dopt = lambda k: (person_detector.get(k) if isinstance(person_detector, dict) else getattr(person_detector, k, None)) if person_detector is not None else None
-        self.detect_every = int(dopt('DETECT_EVERY') or 1)
+        self.detect_every = int(_opt(person_detector, 'DETECT_EVERY') or 1)
         self.track_box_rule = dict(_lib.TRACK_BOX_RULE)
-        if dopt('TRACK_BOX_GROW') is not None:
-            self.track_box_rule['grow'] = float(dopt('TRACK_BOX_GROW'))
-        if dopt('TRACK_BOX_PAD') is not None:
-            self.track_box_rule['pad_px'] = float(dopt('TRACK_BOX_PAD'))
+        for key, name in (('TRACK_BOX_GROW', 'grow'), ('TRACK_BOX_PAD', 'pad_px')):
+            if _opt(person_detector, key) is not None:
+                self.track_box_rule[name] = float(_opt(person_detector, key))
         self.frames_scheduled = 0
         if self.person_detector is None:
             print("Person Detector : Close.")
@@ -151,7 +171,7 @@ class ivclabpose(object):
             # the reference's cfg / weight / names files are not distributed with it: a missing cfg or names file means
             # the standard YOLOv3-416 COCO layout (person = class 0), missing weights mean a seeded random network.
             # ARCH (optional key, not in the reference): 'yolov3' | 'yolov3-tiny' | 'yolov3-spp', the standard network built when the cfg file is missing
-            arch = (d.get('ARCH') if isinstance(d, dict) else getattr(d, 'ARCH', None)) or 'yolov3'
+            arch = _opt(d, 'ARCH') or 'yolov3'
             self.bbox_detector = YOLOv3(cfg if cfg and os.path.exists(cfg) else None,
                                         weight if weight and os.path.exists(weight) else None,
                                         names if names and os.path.exists(names) else None,
@@ -179,30 +199,10 @@ class ivclabpose(object):
                                         device=device, max_dets=max_dets,
                                         shard_crops=torch.distributed.is_available() and torch.distributed.is_initialized(),
                                         autotune=autotune, box_transform=box_transform, box_scale=box_scale)
-            # optional key (not in the reference's YAMLs): SOFT_ARGMAX_BETA > 0 switches the decode from the hard arg-max (parity mode)
-            # to the soft-arg-max of pam_head_decode_soft with that inverse temperature
-            sb = self.pose_detector.get('SOFT_ARGMAX_BETA') if isinstance(self.pose_detector, dict) else getattr(self.pose_detector, 'SOFT_ARGMAX_BETA', None)
-            if sb:
-                self.pose_model.soft_beta = float(sb)
-            # optional keys under the official names (TEST.FLIP_TEST / SHIFT_HEATMAP / POST_PROCESS of the HRNet and Simple Baselines
-            # configs; absent from the reference's YAMLs, off when absent): the protocol the published checkpoints were evaluated under
-            opt = lambda k: self.pose_detector.get(k) if isinstance(self.pose_detector, dict) else getattr(self.pose_detector, k, None)
-            if opt('SHIFT_HEATMAP') is not None:
-                self.pose_model.shift_heatmap = bool(opt('SHIFT_HEATMAP'))
-            self.pose_model.post_process = bool(opt('POST_PROCESS'))
-            # optional keys DARK / BLUR_KERNEL: the DARK decode (Zhang et al., CVPR 2020), the test protocol of the DARK-trained checkpoints;
-            # BLUR_KERNEL absent: 17 for maps of 96 rows or more, otherwise 11
-            if opt('BLUR_KERNEL') is not None:
-                self.pose_model.blur_kernel = int(opt('BLUR_KERNEL'))
-            self.pose_model.dark = bool(opt('DARK'))
-            self.pose_model.flip_test = bool(opt('FLIP_TEST'))
-            # optional keys OKS_NMS / OKS_THRE / IN_VIS_THRE (TEST.OKS_THRE / TEST.IN_VIS_THRE of the official configs; OKS_NMS switches the
-            # step on): every pose rescored and each view's duplicates removed on the device before the tracker (pam_pose_nms)
-            self.pose_model.pose_nms = bool(opt('OKS_NMS'))
-            if opt('OKS_THRE') is not None:
-                self.pose_model.oks_thre = float(opt('OKS_THRE'))
-            if opt('IN_VIS_THRE') is not None:
-                self.pose_model.in_vis_thre = float(opt('IN_VIS_THRE'))
+            for key, attr, conv, when_absent in POSE_OPTIONS:
+                value = _opt(self.pose_detector, key)
+                if value is not None or when_absent:
+                    setattr(self.pose_model, attr, conv(value))
             print("Pose Detector : ", _cfg(self.pose_detector, 'NAME'))
         if self.person_matcher is None:
             print("Person Matcher : Close.")

@@ -6,7 +6,6 @@ Memory: guarded_mem's arena hands out bf16 activations and counts unwritten int1
 so the bands here are local (``Banded``, with guarded_mem's band width and alignment) and "every byte is written" is shown by
 running under two different fills: a byte that is never written holds a different value in the two runs, so it cannot equal the
 reference in both."""
-import contextlib
 import ctypes as C
 import os
 
@@ -17,6 +16,7 @@ import pam
 from pam import _lib
 import guarded_mem as GM
 import jpeg_ref as J
+from recorded_calls import recorded_calls
 
 pytestmark = pytest.mark.gpu
 BAND = 2 * GM.GUARD              # bytes on each side
@@ -239,21 +239,6 @@ def test_reconstruct_refuses_what_it_cannot_run_before_any_launch(torch, lib):
         assert call(**kw) == -1, kw
     assert lib.pam_jpeg_reconstruct(None, 1, None) == -1
     torch.cuda.synchronize()
-
-
-@contextlib.contextmanager
-def recorded_calls():
-    """Every call into libpam_hip.so, by name, in order (the worker threads' calls included)."""
-    lib, calls, saved = _lib.load(), [], {}
-    for name in _lib.EXPORTS:
-        fn = getattr(lib, name)
-        saved[name] = fn
-        setattr(lib, name, (lambda f, nm: lambda *a: (calls.append(nm), f(*a))[1])(fn, name))
-    try:
-        yield calls
-    finally:
-        for name, fn in saved.items():
-            setattr(lib, name, fn)
 
 
 N_FRAMES = 23

@@ -3,14 +3,13 @@
 1e-9 px), the host dicts and ``pts`` are the off run's bit for bit (raw-image pixels), the calls into the library are the off run's plus
 one pam_undistort_keypoints -- behind pam_pose_nms when that is on -- and the off run makes the calls it made before the option existed.
 HRNet-W32 at 256 x 192, random weights, 5 crops."""
-import contextlib
-
 import numpy as np
 import pytest
 import torch
 
 import lens_ref as L
 from pam import synth
+from recorded_calls import recorded_calls
 
 pytestmark = pytest.mark.gpu
 
@@ -28,22 +27,6 @@ def w32():
             net.features(net.input_buffer(n))
     torch.cuda.synchronize()
     return net
-
-
-@contextlib.contextmanager
-def recorded_calls():
-    """Every call into libpam_hip.so, by name, in order."""
-    from pam import _lib
-    lib, calls, saved = _lib.load(), [], {}
-    for name in _lib.EXPORTS:
-        fn = getattr(lib, name)
-        saved[name] = fn
-        setattr(lib, name, (lambda f, nm: lambda *a: (calls.append(nm), f(*a))[1])(fn, name))
-    try:
-        yield calls
-    finally:
-        for name, fn in saved.items():
-            setattr(lib, name, fn)
 
 
 def _model(w32, dist):

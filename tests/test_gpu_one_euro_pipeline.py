@@ -2,34 +2,18 @@
 sharding and crop sharding, the tracker on the caller's stream and on its own -- gives the bits IterativeTracker(one_euro=True) gives,
 on its host-list path (the facade) and on its device path (tracking_dev); the facade's pts3d_filtered follows the 9-tuple's ids; and
 with the option off every entry point makes the calls into the library it made before the option existed."""
-import contextlib
-
 import numpy as np
 import pytest
 import torch
 
 import golden_io as G
-from pam import _lib, synth
+from pam import synth
+from recorded_calls import recorded_calls
 
 pytestmark = pytest.mark.gpu
 
 MD, NF = 8, 60
 SETUP = ('pam_create', 'pam_out_layout', 'pam_set_cameras', 'pam_set_lens', 'pam_set_input_guard', 'pam_set_one_euro', 'pam_last_error')
-
-
-@contextlib.contextmanager
-def recorded_calls():
-    """Every call into libpam_hip.so, by name, in order."""
-    lib, calls, saved = _lib.load(), [], {}
-    for name in _lib.EXPORTS:
-        fn = getattr(lib, name)
-        saved[name] = fn
-        setattr(lib, name, (lambda f, nm: lambda *a: (calls.append(nm), f(*a))[1])(fn, name))
-    try:
-        yield calls
-    finally:
-        for name, fn in saved.items():
-            setattr(lib, name, fn)
 
 
 def _facade(one_euro):

@@ -3,7 +3,6 @@ precomputed, images from disk) draws with pam_overlay_draw and saves through pam
 path by count and name, and every one is byte for byte what the restatements give for that frame: tests/overlay_ref.py's drawing of the
 loop's result into the decoded input frame, encoded by tests/jpeg_enc_ref.py (which is held to Pillow).  With the key off none of the
 new entry points is called and the files are the host path's."""
-import contextlib
 import os
 import pickle
 
@@ -11,29 +10,15 @@ import numpy as np
 import pytest
 
 import pam
-from pam import _lib, synth
+from pam import synth
 from pam.dataset import GetConfig, LoadFilenames, LoadImages
 import jpeg_enc_ref as E
 import overlay_ref as R
+from recorded_calls import recorded_calls
 
 pytestmark = pytest.mark.gpu
 N_FRAMES, W, H = 5, 360, 288
 NEW_CALLS = ('pam_overlay_draw', 'pam_jpeg_forward', 'pam_jpeg_encode', 'pam_jpeg_encode_bound', 'pam_jpeg_quality_tables')
-
-
-@contextlib.contextmanager
-def recorded_calls():
-    """Every call into libpam_hip.so, by name, in order (the worker threads' calls included)."""
-    lib, calls, saved = _lib.load(), [], {}
-    for name in _lib.EXPORTS:
-        fn = getattr(lib, name)
-        saved[name] = fn
-        setattr(lib, name, (lambda f, nm: lambda *a: (calls.append(nm), f(*a))[1])(fn, name))
-    try:
-        yield calls
-    finally:
-        for name, fn in saved.items():
-            setattr(lib, name, fn)
 
 
 @pytest.fixture(scope='module')

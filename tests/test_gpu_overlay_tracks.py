@@ -4,7 +4,6 @@ step; the poses the restatement is given come from the fetched record, so their 
 a tests/guarded_mem.py arena: a row the kernel did not write, or a store outside the table, fails.  Then the edges of the rule, the
 counted draw between sentinel bands against tests/overlay_ref.py's raster, and FramePipeline.overlay_step frame by frame, 3D canvas and
 written JPEG files included."""
-import contextlib
 import ctypes as C
 import os
 
@@ -16,27 +15,13 @@ import guarded_mem as GM
 import overlay_tracks_ref as T
 from pam import _lib, synth
 from pam import visualization as V
+from recorded_calls import recorded_calls
 
 pytestmark = pytest.mark.gpu
 
 ROWS = T.ROWS
 NEW_CALLS = ('pam_overlay_tracks', 'pam_overlay_draw_counted')
 NULL = np.array(T.NULL_ROW, dtype=np.int32)
-
-
-@contextlib.contextmanager
-def recorded_calls():
-    """Every call into libpam_hip.so, by name, in order."""
-    lib, calls, saved = _lib.load(), [], {}
-    for name in _lib.EXPORTS:
-        fn = getattr(lib, name)
-        saved[name] = fn
-        setattr(lib, name, (lambda f, nm: lambda *a: (calls.append(nm), f(*a))[1])(fn, name))
-    try:
-        yield calls
-    finally:
-        for name, fn in saved.items():
-            setattr(lib, name, fn)
 
 
 class Rig(object):

@@ -2,8 +2,6 @@
 lists in which a box appears twice in two of the views (identical crops decode to bit-identical keypoints: OKS 1) against
 tests/pose_nms_ref.apply on the option-off run, the tracker against the run on the de-duplicated list with the option off, and the option
 off against the calls it made before.  HRNet-W32 at 256 x 192, random weights, 6 crops."""
-import contextlib
-
 import numpy as np
 import pytest
 import torch
@@ -11,6 +9,7 @@ import torch
 import boxes_ref as B
 import pose_nms_ref as R
 from pam import synth
+from recorded_calls import recorded_calls
 
 pytestmark = pytest.mark.gpu
 
@@ -57,22 +56,6 @@ def frames_of(t):
 
 def person_list(rows, frames):
     return [[dict(image_id=0, category_id=1, score=s, bbox=list(b), data=frames[v], feature=[]) for b, s in view] for v, view in enumerate(rows)]
-
-
-@contextlib.contextmanager
-def recorded_calls():
-    """Every call into libpam_hip.so, by name, in order."""
-    from pam import _lib
-    lib, calls, saved = _lib.load(), [], {}
-    for name in _lib.EXPORTS:
-        fn = getattr(lib, name)
-        saved[name] = fn
-        setattr(lib, name, (lambda f, nm: lambda *a: (calls.append(nm), f(*a))[1])(fn, name))
-    try:
-        yield calls
-    finally:
-        for name, fn in saved.items():
-            setattr(lib, name, fn)
 
 
 def reference(det_off, n_in, rows):
