@@ -500,16 +500,28 @@ class Handle(object):
         return dict(n_tracks=n, n_fresh=int(m[1]), ids=rows[:, 0].copy(), fresh=rows[:, 1].astype(bool), samples=rows[:, 2].copy(),
                     pose=p[:n].copy())
 
-    def track_boxes(self, stream, frame_id, frame_w, frame_h, boxes, count, ids=None, info=None, scene=0, grow=1.25, pad_px=8.0,
-                    min_size_px=8.0, max_gap=3):
+    def track_box_buffers(self, max_det=None):
+        """(boxes, count, ids, info) for track_boxes: zeroed (C, max_det, 5) float32, (2C,) int32, (C, max_det) int32 and (2,) int32
+        tensors on the handle's device; max_det: rows per view, the handle's max_dets by default."""
+        import torch
+        dev, md = 'cuda:%d' % self.device, int(self.max_dets if max_det is None else max_det)
+        return (torch.zeros((self.C, md, 5), dtype=torch.float32, device=dev), torch.zeros(2 * self.C, dtype=torch.int32, device=dev),
+                torch.zeros((self.C, md), dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev))
+
+    def track_boxes(self, stream, frame_id, frame_w, frame_h, boxes, count, ids=None, info=None, scene=0, **rule):
         """Person boxes of ``frame_id`` from the tracker state behind whatever is queued on ``stream`` (pam_track_boxes).  boxes
-        (C, max_det, 5) float32, count (2C,) int32, ids (C, max_det) int32 or None, info (2,) int32: contiguous device tensors, written
-        in the detector's layout (``YOLOv3.detect_dev``)."""
+        (C, max_det, 5) float32, count (2C,) int32, ids (C, max_det) int32 or None, info (2,) int32: contiguous device tensors
+        (track_box_buffers), written in the detector's layout (``YOLOv3.detect_dev``).  rule: grow, pad_px, min_size_px, max_gap; a
+        key that is not given has TRACK_BOX_RULE's value."""
+        if set(rule) - set(TRACK_BOX_RULE):
+            raise TypeError('track_boxes: unknown rule key(s) %s (%s)' % (sorted(set(rule) - set(TRACK_BOX_RULE)), ', '.join(TRACK_BOX_RULE)))
+        rule = dict(TRACK_BOX_RULE, **rule)
         max_det = int(boxes.shape[1])
         assert tuple(boxes.shape) == (self.C, max_det, 5) and boxes.is_contiguous() and count.numel() == 2 * self.C and info.numel() >= 2
         assert ids is None or (ids.numel() == self.C * max_det and ids.is_contiguous())
-        self._chk(self.lib.pam_track_boxes(self._h, C.c_void_p(stream), int(scene), int(frame_id), int(frame_w), int(frame_h), float(grow),
-                                           float(pad_px), float(min_size_px), int(max_gap), max_det, C.c_void_p(boxes.data_ptr()),
+        self._chk(self.lib.pam_track_boxes(self._h, C.c_void_p(stream), int(scene), int(frame_id), int(frame_w), int(frame_h),
+                                           float(rule['grow']), float(rule['pad_px']), float(rule['min_size_px']), int(rule['max_gap']),
+                                           max_det, C.c_void_p(boxes.data_ptr()),
                                            C.c_void_p(count.data_ptr()), C.c_void_p(ids.data_ptr()) if ids is not None else None,
                                            C.c_void_p(info.data_ptr())))
 

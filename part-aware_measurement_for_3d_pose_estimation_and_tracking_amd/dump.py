@@ -3,6 +3,8 @@ device, in the tracker's input layout."""
 import numpy as np
 import torch
 
+from .stages import PoseNmsOut
+
 
 class DumpResults(list):
     """``dump_results`` of the reference (list per view of person dicts) + the same keypoints still on the device.
@@ -70,8 +72,7 @@ class DumpResults(list):
         if self._nms is None:
             return None
         ki, _, V, S = self._nms
-        a = ki.numpy() if torch.is_tensor(ki) else ki
-        return [[int(s) for s in a[V + v * S:V + v * S + int(a[v])]] for v in range(V)]
+        return PoseNmsOut.kept(ki.numpy() if torch.is_tensor(ki) else ki, V, S)
 
     @poses_host.setter
     def poses_host(self, value):

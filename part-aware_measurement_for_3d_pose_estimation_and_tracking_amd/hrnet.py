@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, poseresnet
+from . import _lib, poseresnet, stages
 from .dump import DumpResults
 from .replay import ForwardReplay
 # Names that callers outside the package reach as hrnet.X, one line per home.  bench.py: PoseHighResolutionNet, init_random,
@@ -463,29 +463,21 @@ class HRNetPose(ForwardReplay):
                 k = e - s
                 mp = min(batch_size, (k + self.graph_bucket - 1) // self.graph_bucket * self.graph_bucket) if batch_size >= self.graph_bucket else k
                 x = self.input_buffer(mp)                    # mp > k: the crop kernel repeats the last crop into the bucket's spare rows
-                if affine:
-                    self.preprocess(ptrs, fh, fw, view_of[s:e], bx[s:e], x, eff=eff[s:e])
-                else:
-                    self.preprocess(ptrs, fh, fw, view_of[s:e], bx[s:e], x)
+                self.preprocess(ptrs, fh, fw, view_of[s:e], bx[s:e], x, eff=eff[s:e] if affine else None)
                 self.head_decode(self.features(x), view_of[s:e], slot_of[s:e], dbx[s:e], det, kp[s:e], n=k)
             if self.world > 1:
                 from .distributed import gather_crop_keypoints
                 kpl = gather_crop_keypoints(kp[lo:hi].contiguous(), n, self.world, self.rank, self.group)
                 # the tracker's device-side input, rebuilt from the gathered rows: (view, slot) <- (y, x, score) as float64
                 det[view_of.long(), slot_of.long()] = kpl[:, :, [1, 0, 2]].double()
-            if nms:
-                # behind the last decode of the call (the assembled buffer on every rank when the crops are sharded), from the ORIGINAL
-                # counts: a redo after a void forward decodes and filters again
-                _lib.pose_nms(torch.cuda.current_stream(self.device).cuda_stream, det, n_det, view_of, slot_of, dbx, nms_dev[0][:V],
-                              nms_dev[0][V:], nms_dev[1], score=nms_dev[2], score_strides=(S, 1), oks_thre=self.oks_thre,
-                              in_vis_thre=self.in_vis_thre)
-                nms_host[0].copy_(nms_dev[0], non_blocking=True)
-                nms_host[1].copy_(nms_dev[1], non_blocking=True)
-            if lens is not None:
-                # last of all, on the tracker's buffer only (kp, the host's rows, stays raw): the filter above wanted raw-image coordinates,
-                # and a redo decodes again before it comes here, so the in-place step never meets its own output
-                _lib.undistort_keypoints(torch.cuda.current_stream(self.device).cuda_stream, det, nms_dev[0][:V] if nms else n_det, lens,
-                                         self.lens_info)
+            # behind the last decode of the call (the assembled buffer on every rank when the crops are sharded): the filter from the
+            # ORIGINAL counts -- a redo after a void forward decodes and filters again -- with its outputs' copies right behind it, then
+            # the lens step on the tracker's buffer only (kp, the host's rows, stays raw; a redo decodes again before it comes here, so
+            # the in-place step never meets its own output)
+            stages.after_decode(torch.cuda.current_stream(self.device).cuda_stream, det, n_det, (view_of, slot_of, dbx),
+                                nms=(nms_dev[0][:V], nms_dev[0][V:], nms_dev[1], dict(score=nms_dev[2], score_strides=(S, 1), oks_thre=self.oks_thre,
+                                                                                      in_vis_thre=self.in_vis_thre)) if nms else None,
+                                nms_fetch=tuple(zip(nms_host, nms_dev)) if nms else (), lens=(lens, self.lens_info, None) if lens is not None else None)
             # The reference's contract is host lists -- but nothing needs them before the caller looks: the device -> host copy of the
             # keypoints is only ENQUEUED here (pinned buffer, this stream) and the per-person dicts are built at the first access of the
             # dump (DumpResults).  A loop that passes the dump straight on to PersonTrack_Project3DPose waits for the GPU once per frame

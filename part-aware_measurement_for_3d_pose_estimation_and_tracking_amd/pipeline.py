@@ -9,7 +9,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, stages
 from .distributed import CropGather, ViewGather
 from .hrnet import HRNetPose
 
@@ -108,10 +108,10 @@ class FramePipeline(object):
         self.handle = _lib.Handle(self.C, self.params, max_dets=max_dets, max_tracks=max_tracks, n_scenes=1, device=device)
         self.handle.set_cameras(np.stack([c.P for c in calib_cameras]), np.stack([c.F for c in calib_cameras]),
                                 np.stack([c.RK_INV for c in calib_cameras]), np.stack([c.position for c in calib_cameras]))
-        self.one_euro, self._oe_fetched = _lib.one_euro_config(one_euro), False
-        if self.one_euro is not None:
-            self.handle.set_one_euro(self.one_euro)
-            self._oe_dev, self._oe_host = self.handle.one_euro_buffers(), self.handle.one_euro_buffers(pinned=True)
+        # the side outputs that travel with the record (stages.py; results() adds them in this order): the One-Euro rows, the crop
+        # table's info words (below), the filter's counts (below)
+        self.one_euro = _lib.one_euro_config(one_euro)
+        self._oe = stages.OneEuro(self.handle, self.one_euro) if self.one_euro is not None else None
         self.lens, self.lens_info = None, None
         if lens is not None:
             self.handle.set_lens(lens)
@@ -177,27 +177,21 @@ class FramePipeline(object):
             raise ValueError('crop_cap must be >= 1')
         if self.bucketed and self.net is not None:
             self.crop_cap = self.net.bucket(self.crop_cap)
-        self._tables, self._tb, self._table_info, self.table_n_det = None, None, None, None
+        self._tables, self._tb, self.table_n_det = None, None, None
         # box_transform='affine': the effective boxes of a frame, written by its crop launch and read by its decode and filter; one table
         # per replay slot (two frames in flight), rows for the largest frame this rank can see, rounded up to the bucket as crop_cap is
         # (built here when the network has the option on, else at the first frame of a shared net whose owner switches it on later)
         self.eff_table = None
         if self.net is not None and self.net.box_transform == 'affine':
             self._eff_rows(0, 0)
-        self._ct_host = torch.zeros(4, dtype=torch.int32).pin_memory()
-        self._ct_fetched = False
+        self._ct = stages.CropTableInfo()
         self._ev_slot_read, self._table_no, self._table_slot = [None, None], 0, 0
         # the OKS-NMS behind the decode: [n_det | keep_from] int32 and the new scores, one set (the launch sits behind wait_track, so the
         # track step of the frame before has read its counts), and a pinned copy of the int32 part that travels with the record's fetch
         self.pose_nms, self.oks_thre, self.in_vis_thre = bool(pose_nms), float(oks_thre), float(in_vis_thre)
-        self.nms_n_det, self.nms_keep_from, self.nms_pose_score, self._nms_live, self._nms_fetched = None, None, None, False, False
-        if self.pose_nms:
-            nv = max(1, len(self.mine))
-            self._nms_i = torch.zeros(nv + nv * max_dets, dtype=torch.int32, device=self.device)
-            self._nms_i[nv:].fill_(-1)
-            self.nms_n_det, self.nms_keep_from = self._nms_i[:nv], self._nms_i[nv:].view(nv, max_dets)
-            self.nms_pose_score = torch.zeros((nv, max_dets), dtype=torch.float64, device=self.device)
-            self._nms_host = torch.zeros(nv + nv * max_dets, dtype=torch.int32).pin_memory()
+        self._nms = stages.PoseNmsOut(max(1, len(self.mine)), max_dets, self.device) if self.pose_nms else None
+        self.nms_n_det, self.nms_keep_from, self.nms_pose_score = \
+            (self._nms.n_det, self._nms.keep_from, self._nms.pose_score) if self.pose_nms else (None, None, None)
         self.overlay = None
         if overlay is not None:
             unknown = set(overlay) - {'view3d', 'emitted_only'}
@@ -205,17 +199,11 @@ class FramePipeline(object):
                 raise ValueError('overlay: unknown key(s) %s (view3d, emitted_only)' % sorted(unknown))
             self.overlay = dict(emitted_only=bool(overlay.get('emitted_only', True)), view3d=None)
             self.ev_overlay = (torch.cuda.Event(), torch.cuda.Event())      # frames ready -> draw, draw done -> consumer
-            v3 = overlay.get('view3d')
-            if v3 is not None:
-                from . import visualization as V
-                v3 = dict(v3)
-                size = tuple(int(x) for x in v3.pop('size', (640, 480)))
-                up = v3.pop('up', (0, 0, 1))
-                P3 = V.view3d_camera(calib_cameras, size, up=up, **v3)
-                self.view3d_P = torch.from_numpy(P3.reshape(1, 3, 4)).to(self.device)
-                self.view3d_background = V.view3d_background(calib_cameras, P3, size, up=up, device=self.device)
-                self.view3d_canvas = None
-                self.overlay['view3d'] = dict(size=size, P=P3)
+            if overlay.get('view3d') is not None:
+                from .visualization import view3d_setup
+                v3 = view3d_setup(calib_cameras, overlay['view3d'], self.device, what="overlay['view3d']")
+                self.view3d_P, self.view3d_background, self.view3d_canvas = v3['P_dev'], v3['background'], None
+                self.overlay['view3d'] = dict(size=v3['size'], P=v3['P'])
 
     def _pick_track_stream(self, tries=8, spin_us=400, avoid=None):
         """A stream for the exchange + tracker that REALLY runs beside the caller's (pose) stream.  HIP streams are multiplexed onto a few
@@ -234,15 +222,6 @@ class FramePipeline(object):
         pose = torch.cuda.current_stream(self.device)
         out = torch.zeros(4, dtype=torch.int64, device=self.device)
         lib = self.handle.lib
-
-        def both(s, us):
-            torch.cuda.synchronize(self.device)
-            t0 = time.perf_counter()
-            for st, o in ((pose, out), (s, out[2:])):
-                if lib.pam_clock_probe(C.c_void_p(st.cuda_stream), C.c_void_p(o.data_ptr()), us) != 0:
-                    raise _lib.PamError('pam_clock_probe failed')
-            torch.cuda.synchronize(self.device)
-            return time.perf_counter() - t0
         others = [o for o in (avoid or []) if o is not None]
 
         def pair(x, y, us):
@@ -257,9 +236,8 @@ class FramePipeline(object):
         for _ in range(tries):
             s = torch.cuda.Stream(self.device)
             cands.append(s)
-            both(s, 20)                                  # first use: the stream gets its hardware queue here
-            if min(both(s, spin_us) for _ in range(3)) < 1.5e-6 * spin_us and \
-                    all(min(pair(o, s, spin_us) for _ in range(3)) < 1.5e-6 * spin_us for o in others):
+            pair(pose, s, 20)                            # first use: the stream gets its hardware queue here
+            if all(min(pair(o, s, spin_us) for _ in range(3)) < 1.5e-6 * spin_us for o in [pose] + others):
                 return s, True
         return cands[0], False
 
@@ -327,12 +305,10 @@ class FramePipeline(object):
         k = (self._frame_no & 1) if self.pose_streams is not None else 0
         n = int(views.numel())
         x = self.net.input_buffer(self.net.bucket(n) if self.bucketed else n, k)     # a bucket's spare rows repeat the last crop, undecoded
-        if self.net.box_transform == 'affine':
-            eff = self._eff_rows(k, n)
-            self.net.preprocess(frame_ptrs, self.frame_h, self.frame_w, views, boxes, x, eff=eff)
+        eff = self._eff_rows(k, n) if self.net.box_transform == 'affine' else None
+        self.net.preprocess(frame_ptrs, self.frame_h, self.frame_w, views, boxes, x, eff=eff)
+        if eff is not None:
             boxes = eff                                  # decode and filter go through the effective boxes (transform_preds)
-        else:
-            self.net.preprocess(frame_ptrs, self.frame_h, self.frame_w, views, boxes, x)
         if after_crop is not None:
             after_crop()                                # the frames have been read: a feeder may mark its buffers reusable here
         if time_events is not None:
@@ -342,13 +318,13 @@ class FramePipeline(object):
             time_events[1].record(torch.cuda.current_stream(self.device))
         self.wait_track()                               # the previous frame's exchange / tracker read the buffer decode writes
         self.net.head_decode(f, views, slot_of, boxes, det, n=n)
+        nms = None
         if self.pose_nms:
-            _lib.pose_nms(torch.cuda.current_stream(self.device).cuda_stream, det, n_det, views, slot_of, boxes, self.nms_n_det,
-                          self.nms_keep_from, self.nms_pose_score, max_dets=self.max_dets, score=score[0], score_strides=score[1],
-                          views=score[2], oks_thre=self.oks_thre, in_vis_thre=self.in_vis_thre)
-            self._nms_live = True
-        if self.lens is not None:
-            self.undistort_local(self.nms_n_det if self.pose_nms else n_det)
+            nms = (self.nms_n_det, self.nms_keep_from, self.nms_pose_score, dict(score=score[0], score_strides=score[1], views=score[2],
+                                                                                 oks_thre=self.oks_thre, in_vis_thre=self.in_vis_thre))
+            self._nms.live = True
+        stages.after_decode(torch.cuda.current_stream(self.device).cuda_stream, det, n_det, (views, slot_of, boxes), nms=nms,
+                            lens=(self.lens, self.lens_info, self._lens_views) if self.lens is not None else None, max_dets=self.max_dets)
 
     def _eff_rows(self, k, n):
         """The first n rows of replay slot k's effective-box table (box_transform='affine'); the tables hold the largest frame this rank
@@ -371,6 +347,15 @@ class FramePipeline(object):
         _lib.undistort_keypoints(torch.cuda.current_stream(self.device).cuda_stream, self.det_local, n_det, self.lens, self.lens_info,
                                  max_dets=self.max_dets, views=self._lens_views)
 
+    def _no_crops(self, n, after_crop):
+        """The one exit of a pose step that has nothing to run (no crop, no view of this rank, no network): a feeder's release and the
+        next frame's detection are due on such frames too.  -> whether the step is over."""
+        if n and self.net is not None:
+            return False
+        if after_crop is not None:
+            after_crop()
+        return True
+
     @contextlib.contextmanager
     def frame(self):
         """Everything of ONE frame (pose_step*, write_*, track_step*) goes inside.  With two pose streams the frame runs on the stream of
@@ -390,18 +375,17 @@ class FramePipeline(object):
         """HRNet side for this rank's crops.  view_local: int32 (N,) index into self.mine; writes self.det_local.
         pose_nms: n_det (one int32 device count per view of this rank, what track_step would have been given) is required and
         ``self.nms_n_det`` is what track_step takes instead; scores: (len(mine), max_dets) float32 device table of box scores (None: 1.0)."""
-        self._table_info, self._nms_live = None, False
+        self._ct.info = None
+        if self._nms is not None:
+            self._nms.live = False
         if self.pose_nms and self.net is not None and n_det is None:
             raise ValueError('pose_step with pose_nms needs n_det: the filter starts from the per-view counts')
         if self.lens is not None and self.net is not None and n_det is None:
             raise ValueError('pose_step with a lens table needs n_det: the step undistorts the rows below the per-view counts')
-        if int(view_local.numel()) == 0 or self.net is None:
-            if after_crop is not None:
-                after_crop()
+        if self._no_crops(int(view_local.numel()), after_crop):
             if self.pose_nms and self.net is not None:  # nothing decoded, nothing kept
                 self.wait_track()
-                self.nms_n_det.zero_(); self.nms_keep_from.fill_(-1)
-                self._nms_live = True
+                self._nms.nothing_kept()
             return
         self._pose(frame_ptrs, view_local, slot_of, boxes, self.det_local, time_events, after_crop, n_det=n_det,
                    score=(scores, (self.max_dets, 1), None))
@@ -418,42 +402,53 @@ class FramePipeline(object):
         if det_local is not None and det_local.data_ptr() != self.det_local.data_ptr():
             self.write_local(det_local)
 
-        def issue(st):
+        def frame_kernel(st):
             recv = self.gather.exchange(n_det_local, self.net.void_word if self.net is not None else None)
             self.handle.frame_dev_views(st, frame_id, recv.data_ptr(), self.gather.rows.data_ptr())
-            self._one_euro_step(st, frame_id, fetch)
+        self._track(frame_id, fetch, frame_kernel)
+
+    def _behind_tracker(self, issue, ev_in, ev_out, rejoin):
+        """issue(torch stream) on the tracker's stream, behind the last tracker step.  ev_in: the event through which the tracker's stream
+        first waits for what the current stream holds (None: it does not wait); ev_out is recorded behind the work.  rejoin: the current
+        stream then waits for ev_out, and the hop is taken only while a step is pending there; otherwise ev_out is left for a later
+        waiter (wait_track).  Without a tracker stream (or a pending step, under rejoin) the work is issued on the current stream.
+        -> whether the hop was taken."""
+        cur = torch.cuda.current_stream(self.device)
+        if self.track_stream is None or (rejoin and not self._track_pending):
+            issue(cur)
+            return False
+        if ev_in is not None:
+            ev_in.record(cur)
+        with torch.cuda.stream(self.track_stream):
+            if ev_in is not None:
+                self.track_stream.wait_event(ev_in)
+            issue(self.track_stream)
+            ev_out.record(self.track_stream)
+        if rejoin:
+            cur.wait_event(ev_out)
+        return True
+
+    def _track(self, frame_id, fetch, frame_kernel):
+        """The body of track_step and track_step_crops: frame_kernel(stream pointer) -- the exchange and the frame kernel -- then the
+        One-Euro launch, and with ``fetch`` the record's copy with the side outputs that travel with it (results()); on the tracker's
+        stream, behind the pose stream, when there is one."""
+        def issue(stream):
+            st = stream.cuda_stream
+            frame_kernel(st)
+            if self._oe is not None:
+                self._oe.step(st, frame_id, fetch)
             if fetch:
                 self.handle.fetch(st, self.out_i.numpy(), self.out_d.numpy())
-                self._ct_fetched = self._table_info is not None
-                if self._ct_fetched:                     # the crop table's info words travel with the record (results())
-                    self._ct_host.copy_(self._table_info, non_blocking=True)
-                self._nms_fetched = self._nms_live
-                if self._nms_fetched:                    # ... and so do the filter's counts and keep table
-                    self._nms_host.copy_(self._nms_i, non_blocking=True)
-        if self.track_stream is None:
-            issue(self.stream_ptr())
+                self._ct.fetch()
+                if self._nms is not None:
+                    self._nms.fetch()
+        if not self._behind_tracker(issue, self.ev_pose, self.ev_track, rejoin=False):
             return
-        self.ev_pose.record(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(self.track_stream):
-            self.track_stream.wait_event(self.ev_pose)
-            issue(self.track_stream.cuda_stream)
-            self.ev_track.record(self.track_stream)
-            if self._table_info is not None:             # this frame's table set (its n_det) has been read: pose_step_boxes may refill it
-                k = self._table_slot
-                self._ev_slot_read[k] = self._ev_slot_read[k] or torch.cuda.Event()
-                self._ev_slot_read[k].record(self.track_stream)
+        if self._ct.info is not None:                    # this frame's table set (its n_det) has been read: pose_step_boxes may refill it
+            k = self._table_slot
+            self._ev_slot_read[k] = self._ev_slot_read[k] or torch.cuda.Event()
+            self._ev_slot_read[k].record(self.track_stream)
         self._track_pending = True
-
-    def _one_euro_step(self, st, frame_id, fetch):
-        """one_euro: the filter launch behind the frame kernel that was just issued on stream ``st`` (the torch stream that is current
-        there), and with ``fetch`` its two buffers on their way to pinned host memory, in front of the record's copy."""
-        if self.one_euro is None:
-            return
-        pose, meta = self._oe_dev
-        self.handle.one_euro(st, frame_id, pose, meta)
-        self._oe_fetched = bool(fetch)
-        if fetch:
-            self._oe_host[0].copy_(pose, non_blocking=True); self._oe_host[1].copy_(meta, non_blocking=True)
 
     def overlay_step(self, frames):
         """overlay=: the tracks as the last track_step left them, drawn into ``frames`` -- this rank's CUDA frames, one contiguous uint8
@@ -469,25 +464,16 @@ class FramePipeline(object):
         if len(frames) != len(self.mine):
             raise ValueError('overlay_step takes one frame per view of this rank (%d), got %d' % (len(self.mine), len(frames)))
         views, extra = [int(c) for c in self.mine], None
-        cur = torch.cuda.current_stream(self.device)
         if self.overlay['view3d'] is not None:
             self.view3d_canvas = torch.empty_like(self.view3d_background)      # (allocated on the consumer's stream, filled on the draw's)
             frames, views, extra = frames + [self.view3d_canvas], views + [-1], self.view3d_P
-        pose = self._oe_dev[0] if self.one_euro is not None else None
+        pose = self._oe.dev[0] if self._oe is not None else None
 
         def issue(st):
             if extra is not None:
                 self.view3d_canvas.copy_(self.view3d_background)
             draw_tracks_device(self.handle, frames, views=views, extra=extra, pose=pose, emitted_only=self.overlay['emitted_only'], stream=st)
-        if self.track_stream is None or not self._track_pending:
-            issue(cur)
-            return frames
-        self.ev_overlay[0].record(cur)
-        with torch.cuda.stream(self.track_stream):
-            self.track_stream.wait_event(self.ev_overlay[0])
-            issue(self.track_stream)
-            self.ev_overlay[1].record(self.track_stream)
-        cur.wait_event(self.ev_overlay[1])
+        self._behind_tracker(issue, self.ev_overlay[0], self.ev_overlay[1], rejoin=True)
         return frames
 
     # -- person boxes that never visit the host ------------------------------------------------------------------------------
@@ -503,10 +489,7 @@ class FramePipeline(object):
                                  xywh=torch.zeros((cap, 4), dtype=torch.float32, device=dev),
                                  n_det=torch.zeros(nv, dtype=torch.int32, device=dev), info=torch.zeros(4, dtype=torch.int32, device=dev))
                             for _ in range(2)]
-            self._tb = dict(boxes=torch.zeros((self.C, self.max_dets, 5), dtype=torch.float32, device=dev),
-                            count=torch.zeros(2 * self.C, dtype=torch.int32, device=dev),
-                            ids=torch.zeros((self.C, self.max_dets), dtype=torch.int32, device=dev),
-                            info=torch.zeros(2, dtype=torch.int32, device=dev))
+            self._tb = self.handle.track_box_buffers()
             self._mine_dev = torch.tensor(list(self.mine) or [0], dtype=torch.int32, device=dev)
             self.ev_boxes = torch.cuda.Event()
 
@@ -519,17 +502,9 @@ class FramePipeline(object):
         overlap_tracker says: a frame whose boxes come from here cannot start its crops before the previous frame's k_frame has ended,
         which costs the overlap of k_frame under this frame's forward (the record's fetch still overlaps)."""
         self._box_buffers()
-        b = self._tb
-        kw = dict(_lib.TRACK_BOX_RULE); kw.update(rule)
-        if self.track_stream is not None and self._track_pending:
-            with torch.cuda.stream(self.track_stream):
-                self.handle.track_boxes(self.track_stream.cuda_stream, frame_id, self.frame_w, self.frame_h, b['boxes'], b['count'], b['ids'],
-                                        b['info'], **kw)
-                self.ev_boxes.record(self.track_stream)
-            torch.cuda.current_stream(self.device).wait_event(self.ev_boxes)
-        else:
-            self.handle.track_boxes(self.stream_ptr(), frame_id, self.frame_w, self.frame_h, b['boxes'], b['count'], b['ids'], b['info'], **kw)
-        return b['boxes'], b['count'], b['ids']
+        self._behind_tracker(lambda st: self.handle.track_boxes(st.cuda_stream, frame_id, self.frame_w, self.frame_h, *self._tb, **rule),
+                             None, self.ev_boxes, rejoin=True)
+        return self._tb[:3]
 
     def pose_step_boxes(self, frame_ptrs, boxes, count, views=None, time_events=None, after_crop=None, use_scores=True):
         """pose_step on boxes that are on the device in the detector's layout (YOLOv3.detect_dev, track_boxes): boxes (G, max_det, 5)
@@ -538,12 +513,11 @@ class FramePipeline(object):
         one), and crop, forward and decode run for crop_cap rows through the kernels pose_step uses.  ``self.table_n_det`` (device, one
         count per view of this rank) is the n_det_local for track_step -- ``self.nms_n_det`` under pose_nms, whose box scores are column 4
         of `boxes`, read in place (use_scores=False: 1.0)."""
-        self._nms_live = False
+        if self._nms is not None:
+            self._nms.live = False
         if self.shard != 'views':
             raise ValueError("pose_step_boxes needs shard='views': crop sharding builds its select index from a host box list")
-        if not len(self.mine) or self.net is None:
-            if after_crop is not None:
-                after_crop()
+        if self._no_crops(len(self.mine), after_crop):
             return
         self._box_buffers()
         k = self._table_slot = self._table_no & 1       # two sets: the track step of the frame before may still be reading the other one
@@ -554,7 +528,7 @@ class FramePipeline(object):
             cur.wait_event(self._ev_slot_read[k])       # the track step of two frames ago has read this set's counts
         _lib.crop_table(cur.cuda_stream, boxes, count, self.frame_w, self.frame_h, self.max_dets, T['view_of'], T['slot_of'], T['xywh'],
                         T['n_det'], T['info'], views=views)
-        self.table_n_det, self._table_info = T['n_det'], T['info']
+        self.table_n_det, self._ct.info = T['n_det'], T['info']
         score = (boxes.data_ptr() + 16, (5 * int(boxes.shape[1]), 5), views) if (self.pose_nms and use_scores) else (None, (0, 0), None)
         self._pose(frame_ptrs, T['view_of'], T['slot_of'], T['xywh'], self.det_local, time_events, after_crop, n_det=T['n_det'], score=score)
 
@@ -605,35 +579,17 @@ class FramePipeline(object):
     def pose_step_crops(self, frame_ptrs, view_of, slot_of, boxes, time_events=None, after_crop=None):
         """HRNet side for this rank's share of the frame's crops; view_of indexes ALL views (frame_ptrs has C entries).
         Decodes straight into the exchange buffer at (view, slot)."""
-        if int(view_of.numel()) == 0 or self.net is None:
-            if after_crop is not None:
-                after_crop()                             # (a feeder's release / the next frame's detection are due on empty frames too)
+        if self._no_crops(int(view_of.numel()), after_crop):
             return
         self._pose(frame_ptrs, view_of, slot_of, boxes, self.crop_gather.send, time_events, after_crop)
 
     def track_step_crops(self, frame_id, n_det, select, fetch=True):
         """n_det (C,) int32 and select (CropGather.select_index) are the same on every rank (they follow from the frame's box
         list); the keypoint rows come from ``crop_gather.send`` of the rank that owns each crop."""
-        vw = self.net.void_word if self.net is not None else None
-        if self.track_stream is None:
-            det = self.crop_gather.gather(select, vw)
-            st = self.stream_ptr()
+        def frame_kernel(st):
+            det = self.crop_gather.gather(select, self.net.void_word if self.net is not None else None)
             self.handle.frame_dev(st, frame_id, n_det.data_ptr(), det.data_ptr())
-            self._one_euro_step(st, frame_id, fetch)
-            if fetch:
-                self.handle.fetch(st, self.out_i.numpy(), self.out_d.numpy())
-            return
-        self.ev_pose.record(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(self.track_stream):
-            self.track_stream.wait_event(self.ev_pose)
-            det = self.crop_gather.gather(select, vw)
-            st = self.track_stream.cuda_stream
-            self.handle.frame_dev(st, frame_id, n_det.data_ptr(), det.data_ptr())
-            self._one_euro_step(st, frame_id, fetch)
-            if fetch:
-                self.handle.fetch(st, self.out_i.numpy(), self.out_d.numpy())
-            self.ev_track.record(self.track_stream)
-        self._track_pending = True
+        self._track(frame_id, fetch, frame_kernel)
 
     def results(self, strict=True):
         """Synchronise and decode the last fetched record.  strict: a non-zero status word (capacity overflow, infeasible
@@ -656,16 +612,7 @@ class FramePipeline(object):
         if strict and (rec['status'] | rec['status_sticky']) != 0:
             raise _lib.PamError('tracker status 0x%x on frame %d, 0x%x over the run (1 track slots, 2 hypothesis slots, 4 infeasible '
                                 'assignment, 8 clamped detection count)' % (rec['status'], rec['frame_id'], rec['status_sticky']))
-        if self._oe_fetched:
-            f = _lib.Handle.decode_one_euro(self._oe_host[0].numpy(), self._oe_host[1].numpy(), 0)
-            if f['n_tracks'] != rec['n_tracks'] or f['ids'].tolist() != [t['track_id'] for t in rec['tracks']]:
-                raise _lib.PamError('the One-Euro rows do not follow the record (ids %s)' % (f['ids'].tolist(),))
-            rec['pose3d_filtered'] = f['pose']
-            rec['filter_meta'] = dict(n_fresh=f['n_fresh'], ids=f['ids'], fresh=f['fresh'], samples=f['samples'])
-        if self._ct_fetched:
-            w = self._ct_host.numpy()
-            rec['crop_table'] = dict(rows=int(w[0]), wanted=int(w[1]), status=int(w[2]))
-        if self._nms_fetched:
-            a, nv = self._nms_host.numpy(), int(self.nms_n_det.numel())
-            rec['pose_nms'] = dict(n_det=[int(x) for x in a[:nv]], keep_from=a[nv:].reshape(nv, self.max_dets).copy())
+        for side in (self._oe, self._ct, self._nms):     # pose3d_filtered / filter_meta, crop_table, pose_nms
+            if side is not None and side.fetched:
+                side.add_to(rec)
         return rec

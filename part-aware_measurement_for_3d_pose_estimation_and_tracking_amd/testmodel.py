@@ -85,17 +85,10 @@ def view3d_setup(model, block):
     """DATASET.VIEW3D {SIZE: [width, height], AZIMUTH, ELEVATION, UP, MARGIN} (every key optional) -> what overlay_on_device needs for the
     free-viewpoint 3D view: the look-at matrix on the device and the background canvas, both made once."""
     import torch
-    from pam.visualization import view3d_camera, view3d_background
-    block = dict(block) if hasattr(block, 'keys') else {}
-    unknown = set(k.upper() for k in block) - {'SIZE', 'AZIMUTH', 'ELEVATION', 'UP', 'MARGIN'}
-    if unknown:
-        raise ValueError('DATASET.VIEW3D: unknown key(s) %s (SIZE, AZIMUTH, ELEVATION, UP, MARGIN)' % sorted(unknown))
-    kw = {k.lower(): v for k, v in block.items()}
-    size = tuple(int(x) for x in kw.pop('size', (640, 480)))
-    up = tuple(float(x) for x in kw.pop('up', (0, 0, 1)))
+    from pam.visualization import view3d_setup as setup
     device = torch.device('cuda', model.device) if isinstance(model.device, int) else torch.device(model.device)
-    P = view3d_camera(model.cameras, size, up=up, **{k: float(v) for k, v in kw.items()})
-    return dict(P=torch.from_numpy(P.reshape(1, 3, 4)).to(device), background=view3d_background(model.cameras, P, size, up=up, device=device))
+    v3 = setup(model.cameras, block, device, what='DATASET.VIEW3D')
+    return dict(P=v3['P_dev'], background=v3['background'])
 
 
 def overlay_on_device(model, imagelist, result, tracks=False, view3d=None):
@@ -110,7 +103,7 @@ def overlay_on_device(model, imagelist, result, tracks=False, view3d=None):
     frames = [im if torch.is_tensor(im) else torch.from_numpy(np.ascontiguousarray(im)).to(device) for im in imagelist]
     if tracks or view3d is not None:
         trk = model.tracker
-        pose = trk._oe_dev[0] if getattr(trk, 'one_euro', None) is not None else None
+        pose = trk._oe.dev[0] if getattr(trk, '_oe', None) is not None else None
         canvas = [view3d['background'].clone()] if view3d is not None else []          # a new one per frame: the writer reads the last
         if tracks:
             draw_tracks_device(trk.handle, frames + canvas, extra=view3d['P'] if canvas else None, pose=pose)

@@ -6,7 +6,7 @@ cycle -- runs in one fused HIP kernel launch (csrc/pam_frame.hip, k_frame); this
 calls ``pam_frame`` and decodes the output record."""
 import numpy as np
 
-from . import _lib
+from . import _lib, stages
 
 NUM_JOINTS = 17
 
@@ -78,7 +78,7 @@ class IterativeTracker(object):
         self.tracks = []
         self.last = None
         self._guard = None           # set_input_guard: the pose network whose void word the frame kernel reads
-        self.one_euro = _lib.one_euro_config(one_euro)
+        self.one_euro, self._oe = _lib.one_euro_config(one_euro), None      # _oe: the stage (stages.OneEuro) of the open handle
         if n_views is not None:
             self._open(n_views)
 
@@ -93,10 +93,7 @@ class IterativeTracker(object):
         self._rec_keep, self._rec_i, self._rec_d = self.handle.pinned_record()
         if self._guard is not None:
             self.handle.set_input_guard(self._guard.void_word.data_ptr())
-        if self.one_euro is not None:
-            self.handle.set_one_euro(self.one_euro)
-            self._oe_dev = self.handle.one_euro_buffers()
-            self._oe_host = self.handle.one_euro_buffers(pinned=True)
+        self._oe = stages.OneEuro(self.handle, self.one_euro) if self.one_euro is not None else None
 
     def set_input_guard(self, net):
         """net: the HRNetPose whose decode feeds this tracker (None removes the guard).  While its ``void_word`` is raised -- a device-side
@@ -133,14 +130,12 @@ class IterativeTracker(object):
         import torch
         if self.handle is None:
             raise _lib.PamError('predict_boxes before set_cameras')
-        dev, C, md = torch.device('cuda:%d' % self.device), self.cam_num, self.max_tracks
+        C = self.cam_num
         if getattr(self, '_tb', None) is None or self._tb[0].shape[0] != C:
-            self._tb = (torch.zeros((C, md, 5), dtype=torch.float32, device=dev), torch.zeros(2 * C, dtype=torch.int32, device=dev),
-                        torch.zeros((C, md), dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev))
+            self._tb = self.handle.track_box_buffers(self.max_tracks)
         boxes, count, ids, info = self._tb
-        kw = dict(_lib.TRACK_BOX_RULE); kw.update(rule)
-        st = torch.cuda.current_stream(dev)
-        self.handle.track_boxes(st.cuda_stream, frame_id, int(frame_hw[1]), int(frame_hw[0]), boxes, count, ids, info, **kw)
+        st = torch.cuda.current_stream(torch.device('cuda:%d' % self.device))
+        self.handle.track_boxes(st.cuda_stream, frame_id, int(frame_hw[1]), int(frame_hw[0]), boxes, count, ids, info, **rule)
         b, n, i = boxes.cpu().numpy(), count.cpu().numpy(), ids.cpu().numpy()          # (the copies wait for the kernel)
         return [np.concatenate([b[v, :n[v]].astype(np.float64), i[v, :n[v], None].astype(np.float64)], axis=1) for v in range(C)]
 
@@ -176,18 +171,13 @@ class IterativeTracker(object):
     def _filter_issue(self, stream, frame_id):
         """pam_one_euro behind the frame step on ``stream`` and its two buffers on their way to pinned host memory, in front of the
         caller's host wait.  The launch is idempotent per frame (include/pam.h), so it may follow every attempt of a retried frame."""
-        (pose, meta), (hp, hm) = self._oe_dev, self._oe_host
-        self.handle.one_euro(stream, frame_id, pose, meta)
-        hp.copy_(pose, non_blocking=True); hm.copy_(meta, non_blocking=True)
+        self._oe.step(stream, frame_id)
 
     def _filter_attach(self):
         """The fetched filter rows into the decoded record's tracks (same order: both follow the state's list)."""
         if self.one_euro is None or (self.last['status'] & _lib.ST_INPUT_VOID):        # (a void frame's record lists no tracks)
             return
-        f = _lib.Handle.decode_one_euro(self._oe_host[0].numpy(), self._oe_host[1].numpy(), 0)
-        self.last['one_euro'] = f
-        if f['n_tracks'] != self.last['n_tracks'] or any(int(i) != r['track_id'] for i, r in zip(f['ids'], self.last['tracks'])):
-            raise _lib.PamError('the One-Euro rows do not follow the record (ids %s)' % (f['ids'].tolist(),))
+        f = self.last['one_euro'] = self._oe.rows(self.last)
         for k, r in enumerate(self.last['tracks']):
             r['pose3d_filtered'], r['filter_fresh'], r['filter_samples'] = f['pose'][k], bool(f['fresh'][k]), int(f['samples'][k])
 

@@ -317,3 +317,20 @@ def view3d_background(cameras, P, size, up=(0, 0, 1), spacing=1.0, device=None, 
             raise _lib.PamError('pam_overlay_draw failed (%d)' % rc)
         torch.cuda.current_stream(device).synchronize()          # set-up: the table may go once the launch has read it
     return canvas
+
+
+def view3d_setup(cameras, block, device, what='view3d'):
+    """The free-viewpoint 3D view, made once.  block: dict(size=(width, height), azimuth, elevation, up, margin), keys in either letter
+    case, every one optional (view3d_camera's defaults; size (640, 480)); anything without keys is the empty block -> dict(size,
+    P = view3d_camera's float32 (3, 4), P_dev = the same as a (1, 3, 4) tensor on ``device``, background = view3d_background's canvas).
+    what: how an error names the block."""
+    import torch
+    kw = {str(k).lower(): v for k, v in (dict(block) if hasattr(block, 'keys') else {}).items()}
+    unknown = set(kw) - {'size', 'azimuth', 'elevation', 'up', 'margin'}
+    if unknown:
+        raise ValueError('%s: unknown key(s) %s (size, azimuth, elevation, up, margin)' % (what, sorted(unknown)))
+    size = tuple(int(x) for x in kw.pop('size', (640, 480)))
+    up = tuple(float(x) for x in kw.pop('up', (0, 0, 1)))
+    P = view3d_camera(cameras, size, up=up, **{k: float(v) for k, v in kw.items()})
+    return dict(size=size, P=P, P_dev=torch.from_numpy(P.reshape(1, 3, 4)).to(device),
+                background=view3d_background(cameras, P, size, up=up, device=device))

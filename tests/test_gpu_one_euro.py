@@ -147,7 +147,7 @@ def test_idempotence_reset_and_switching_off():
         for _ in range(2):                                    # the same frame again, twice: identical buffers ...
             hb.one_euro(st, t, pose2, meta2)
             hb.sync(st)
-            assert torch.equal(pose2.cpu(), b.tracker._oe_host[0]) and torch.equal(meta2.cpu(), b.tracker._oe_host[1]), t
+            assert torch.equal(pose2.cpu(), b.tracker._oe.host[0]) and torch.equal(meta2.cpu(), b.tracker._oe.host[1]), t
         for x, y in zip(a.tracker.tracks, b.tracker.tracks):  # ... and identical results on every later frame
             assert x.track_id == y.track_id and x.filter_samples == y.filter_samples and x.filter_fresh == y.filter_fresh
             assert x.pose3d_filtered.tobytes() == y.pose3d_filtered.tobytes(), t

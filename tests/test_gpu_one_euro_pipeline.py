@@ -98,10 +98,10 @@ def test_option_off_makes_the_calls_of_before(s2):
     on, cfg, conf = _facade({'BETA': 0.4})
     off, _, _ = _facade(None)
     cams, C = on.cameras, len(on.cameras)
-    assert off.tracker.one_euro is None and not hasattr(off.tracker, '_oe_dev') and off.tracker.handle.one_euro_cfg is None
+    assert off.tracker.one_euro is None and off.tracker._oe is None and off.tracker.handle.one_euro_cfg is None
     mk = lambda **kw: FramePipeline(cams, cfg, conf, (1080, 1920), max_dets=MD, max_tracks=16, hrnet=False, **kw)
     p_off, p_on, c_off, c_on = mk(), mk(one_euro=True), mk(shard='crops'), mk(shard='crops', one_euro=True)
-    assert p_off.one_euro is None and not hasattr(p_off, '_oe_dev')                           # off: nothing allocated
+    assert p_off.one_euro is None and p_off._oe is None                           # off: nothing allocated
     t_off = IterativeTracker(off.tracker.args, max_dets=MD, max_tracks=16)
     t_on = IterativeTracker(off.tracker.args, max_dets=MD, max_tracks=16, one_euro=dict(freq=30))
     dev = p_off.device

@@ -304,7 +304,7 @@ def pipeline_case(one_euro, overlap, tmp_path):
         rec = p.results()
         tracks = rec['tracks']
         if one_euro:
-            filtered = p._oe_dev[0].cpu().numpy()[0]
+            filtered = p._oe.dev[0].cpu().numpy()[0]
             tracks = [dict(tr, pose3d=filtered[i]) for i, tr in enumerate(tracks)]
         ref = T.table(tracks, views, ROWS * 16)
         assert ref['margin'] > 1e-6
@@ -328,7 +328,7 @@ def test_pipeline_overlay_step_draws_the_filtered_poses_behind_the_tracker_strea
     p, rec = pipeline_case(True, True, tmp_path)
     assert p.track_stream is not None
     raw = T.table(rec['tracks'], [dict(P=np.asarray(p.cams[0].P, dtype=np.float32), w=W1, h=H1)], ROWS * 16)
-    filt = T.table([dict(tr, pose3d=p._oe_dev[0].cpu().numpy()[0][i]) for i, tr in enumerate(rec['tracks'])],
+    filt = T.table([dict(tr, pose3d=p._oe.dev[0].cpu().numpy()[0][i]) for i, tr in enumerate(rec['tracks'])],
                    [dict(P=np.asarray(p.cams[0].P, dtype=np.float32), w=W1, h=H1)], ROWS * 16)
     assert not np.array_equal(raw['prims'], filt['prims'])                     # the filter moved what was drawn
 

@@ -168,7 +168,7 @@ def test_frame_pipeline_filters_behind_the_decode_and_the_option_off_is_the_old_
     mk = lambda **kw: FramePipeline(cams, cfg, conf, (H, W), max_dets=8, net=w32, crop_cap=8, **kw)
     off, on, clean = mk(), mk(pose_nms=True), mk()
     assert w32.pose_nms is False and on.pose_nms and not off.pose_nms and off.nms_n_det is None     # a shared net keeps its own setting
-    assert not hasattr(off, '_nms_i') and not hasattr(off, '_nms_host') and off.nms_pose_score is None   # off: nothing allocated
+    assert off._nms is None and off.nms_pose_score is None   # off: nothing allocated
     dev = off.device
     boxes, count = detector_list(DUP)
     cboxes, ccount = detector_list(CLEAN)
