@@ -29,7 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pam.h"
-#include "pam_kernel.hpp"
+#include "pam_resident.hpp"
 
 // Diagnostic build only (tools/stamp_block2.py compiles this file with -DPAM_DIAG): per-wave s_memtime stamps into a buffer of their
 // own that no kernel reads; the shipped library contains no stamp code.
@@ -43,14 +43,8 @@ extern "C" int pam_block2_debug_stamps(void* dev_buf) { g_bb2_stamps = (unsigned
 
 namespace {
 
-constexpr int PA = 96;                     // bytes per activation slot (48 bf16)
-constexpr int NST = 14;                    // k-steps per convolution (432 = 13.5 x 32, zero weights in the tail)
-constexpr int SUB = 48 * 64;               // one k-step's weight image: [48 rows][64 B], 16-byte pieces swizzled (as k_bblock's)
-constexpr int WIMG = NST * SUB;            // 43 008 B per convolution = 42 DMA pieces
-constexpr int MW1 = 6, MW2 = 5;            // M tiles (16 slots) per wave, conv1 / conv2
-constexpr int TST = 8 * 16 * PA;           // byte distance between a wave's consecutive M tiles (tile = wave + 8 i)
-constexpr int WPIECES = 1 + 2 * WIMG / 1024;   // bias piece + both weight images = 85 pieces of 1 KiB
-constexpr int XSLOTS_MAX = 800;            // (160 KB - 85 KB) / 96
+// 96-byte slots, 14 k-step images of [48 rows][64 B], 6 / 5 M tiles per wave for conv1 / conv2 (csrc/pam_resident.hpp)
+constexpr int PA = Block48::PA, NST = Block48::NST, WIMG = Block48::WIMG, MW1 = Block48::MW1, MW2 = Block48::MW2, TST = Block48::TST;
 
 struct BB2Args {
     const uint16_t* in; const char* wpack; uint16_t* out;
@@ -62,38 +56,6 @@ struct BB2Args {
 };
 
 __device__ __attribute__((aligned(64))) const uint32_t g_bb2_zero[16] = {0};
-
-// One convolution of a wave: MT M tiles x 3 N tiles, K walked once, fragments of k-step st + 1 read under the MFMAs of k-step st.
-// wl: this lane's row of k-step 0 in the weight image; xl: this lane's slot of the wave's first M tile; koff[st]: byte offset of the
-// lane's 8-channel slice of k-step st (tap shift + channel) in the activation image.  top(st) runs ahead of k-step st's reads (conv1:
-// the wait for the rest of W1, and W2's DMAs one per k-step).
-template <int MT, typename Top>
-__device__ __forceinline__ void conv_pass(f32x4 (&acc)[MW1][3], const char* wl, const char* xl, const unsigned (&koff)[NST], Top top) {
-    bf16x8 af[2][3], bf[2][MT];
-    auto ld = [&](int st, bf16x8* a_, bf16x8* b_) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) a_[j] = *(const bf16x8*)(wl + st * SUB + j * 1024);
-#ifdef PAM_KO_PIXREADS                                     // timing knock-out (wrong results): pixel fragments read every third k-step only
-        if (st % 3 == 0)
-#endif
-#pragma unroll
-        for (int i = 0; i < MT; ++i) b_[i] = *(const bf16x8*)(xl + koff[st] + i * TST);
-    };
-    ld(0, af[0], bf[0]);
-#pragma unroll
-    for (int st = 0; st < NST; ++st) {
-        const int cur = st & 1, nxt = cur ^ 1;
-        top(st);
-        if (st + 1 < NST) ld(st + 1, af[nxt], bf[nxt]);
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[cur][j]), __builtin_bit_cast(bf16x8_t, bf[cur][i]), acc[i][j], 0, 0, 0);
-        spread<3 * MT, MT + 3>();
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
 
 __global__ __launch_bounds__(512) void k_bblock2_48(BB2Args a) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -153,7 +115,8 @@ __global__ __launch_bounds__(512) void k_bblock2_48(BB2Args a) {
     unsigned koff[NST];
     mk_koff(PWx, koff);
     const char* xl = Xb + (wave * 16 + l15) * PA;
-    const char* wl = W1 + l15 * 64 + ((g ^ ((0x78 >> ((l15 >> 2) * 2)) & 3)) * 16);     // 0x78 = the piece swizzle sigma = (0, 2, 3, 1), 2 bits each
+    const char* wl = W1 + l15 * 64 + ((g ^ KStep48::sigma(l15)) * 16);
+    auto xaddr = [&](int i, int st) { return xl + koff[st] + i * TST; };
     const int nt1 = ((a.TR + 2) * PWx + 15) >> 4, nt2 = (a.TR * PWi + 15) >> 4;          // M tiles that carry real slots
     const int mt1 = (nt1 - wave + 7) >> 3, mt2 = (nt2 - wave + 7) >> 3;                    // ... of this wave (tile = wave + 8 i)
 
@@ -181,10 +144,10 @@ __global__ __launch_bounds__(512) void k_bblock2_48(BB2Args a) {
         if (st >= 4 && st < 9) wdma(45 + wave + 8 * (st - 4));
     };
     // wave-uniform choice of the instantiation: a wave multiplies only the M tiles that carry real slots (3 at least)
-    if (mt1 > 5) conv_pass<6>(acc, wl, xl, koff, top1);
-    else if (mt1 == 5) conv_pass<5>(acc, wl, xl, koff, top1);
-    else if (mt1 == 4) conv_pass<4>(acc, wl, xl, koff, top1);
-    else conv_pass<3>(acc, wl, xl, koff, top1);
+    if (mt1 > 5) resident_pass<KStep48, 6>(acc, wl, xaddr, top1);
+    else if (mt1 == 5) resident_pass<KStep48, 5>(acc, wl, xaddr, top1);
+    else if (mt1 == 4) resident_pass<KStep48, 4>(acc, wl, xaddr, top1);
+    else resident_pass<KStep48, 3>(acc, wl, xaddr, top1);
     BB2_STAMP(3);
 
     // intermediate = ReLU(conv1 + b1) as bf16 on a grid of pitch PWi, zero where the position lies outside the image: packed and
@@ -249,10 +212,10 @@ __global__ __launch_bounds__(512) void k_bblock2_48(BB2Args a) {
         for (int i = 0; i < MW2; ++i) { acc[i][0] = b0; acc[i][1] = b1; acc[i][2] = b2; }
     }
     auto top2 = [](int) {};
-    if (mt2 > 4) conv_pass<5>(acc, wl + WIMG, xl, koff, top2);
-    else if (mt2 == 4) conv_pass<4>(acc, wl + WIMG, xl, koff, top2);
-    else if (mt2 == 3) conv_pass<3>(acc, wl + WIMG, xl, koff, top2);
-    else conv_pass<2>(acc, wl + WIMG, xl, koff, top2);
+    if (mt2 > 4) resident_pass<KStep48, 5>(acc, wl + WIMG, xaddr, top2);
+    else if (mt2 == 4) resident_pass<KStep48, 4>(acc, wl + WIMG, xaddr, top2);
+    else if (mt2 == 3) resident_pass<KStep48, 3>(acc, wl + WIMG, xaddr, top2);
+    else resident_pass<KStep48, 2>(acc, wl + WIMG, xaddr, top2);
     BB2_STAMP(6);
 #ifdef PAM_KO_SERIAL
     {
@@ -278,9 +241,7 @@ __global__ __launch_bounds__(512) void k_bblock2_48(BB2Args a) {
             ov[2 * j] = relu_bf16x2(pack_bf16x2(acc[i][j][0] + r0, acc[i][j][1] + r1));
             ov[2 * j + 1] = relu_bf16x2(pack_bf16x2(acc[i][j][2] + r2f, acc[i][j][3] + r3));
         }
-        uint16_t* d = a.out + ooff[i];
-        *(u32x4*)(d + 8 * g) = (u32x4){ov[0], ov[1], ov[2], ov[3]};
-        *(u32x2*)(d + 32 + 4 * g) = (u32x2){ov[4], ov[5]};
+        KStep48::store12(a.out + ooff[i], g, ov);
     }
     BB2_STAMP(7);
 }
@@ -586,47 +547,23 @@ bool pick_tile96(int N, int H, int W, int& TR, int& TC) {
     return true;
 }
 
-// Tile of the resident-weights block for an N x H x W tensor: the (TR, TC) that minimises rounds of workgroups x time of an item.
-// An item's time: a fixed prologue (the X tile and the first weights must land before the first MFMA: ~8 M tiles' worth) plus, per
-// convolution, the M tiles of the busiest SIMD (tile t -> wave t % 8 -> SIMD t % 4; a wave multiplies the instantiated count that
-// holds its tiles: 3-6 for conv1, 2-5 for conv2).
-int simd_tiles(int nt, int lo) {
-    int worst = 0;
-    for (int s = 0; s < 4; ++s) {
-        int sum = 0;
-        for (int w = s; w < 8; w += 4) { int m = nt > w ? (nt - w + 7) >> 3 : 0; sum += m < lo ? lo : m; }
-        if (sum > worst) worst = sum;
+struct Launch48 : Block48 {
+    using Args = BB2Args;
+    static constexpr auto kernel = k_bblock2_48;
+    static constexpr bool REACH = false;                 // the junk M tiles' reads end in the weights behind the X tile
+    static void diag(Args& a) {
+#ifdef PAM_DIAG
+        a.stamps = g_bb2_stamps;
+#endif
     }
-    return worst;
-}
-bool pick_tile(int N, int H, int W, int& TR, int& TC) {
-    static thread_local int cN = 0, cH = 0, cW = 0, cTR = 0, cTC = 0;     // the search is ~H x W steps: keep the last answer
-    if (N == cN && H == cH && W == cW) { TR = cTR; TC = cTC; return true; }
-    long best = -1;
-    for (int tr = 1; tr <= H; ++tr)
-        for (int tc = 1; tc <= W; ++tc) {
-            const int s1 = (tr + 2) * (tc + 4), s2 = tr * (tc + 2), xs = (tr + 4) * (tc + 4);
-            if (s1 > 16 * 8 * MW1 || s2 > 16 * 8 * MW2 || xs > XSLOTS_MAX) continue;
-            const long items = (long)N * ((H + tr - 1) / tr) * ((W + tc - 1) / tc);
-            const long per = 8 + simd_tiles((s1 + 15) / 16, 3) + simd_tiles((s2 + 15) / 16, 2);
-            const long cost = ((items + 255) / 256) * per * 4096 + items;     // whole rounds of 256 workgroups; ties -> fewer items
-            if (best < 0 || cost < best) { best = cost; TR = tr; TC = tc; }
-        }
-    if (best < 0) return false;
-    cN = N; cH = H; cW = W; cTR = TR; cTC = TC;
-    return true;
-}
+};
 
 }  // namespace
-
-// C = 32 (HRNet-W32): k_bblock2_32, csrc/pam_block32.hip
-bool pam_bb32_pick_tile(int N, int H, int W, int& TR, int& TC);
-int pam_bb32_launch(void* stream, const void* in, const void* wpack, void* out, int N, int H, int W, int tile_rows, int tile_cols);
 
 extern "C" int pam_basic_block2_tile(int C, int N, int H, int W, int32_t* out2) {
     if ((C != 32 && C != 48 && C != 96) || N < 1 || H < 1 || W < 1 || !out2) return PAM_E_ARG;
     int tr = 0, tc = 0;
-    if (!(C == 32 ? pam_bb32_pick_tile(N, H, W, tr, tc) : C == 48 ? pick_tile(N, H, W, tr, tc) : pick_tile96(N, H, W, tr, tc))) return PAM_E_ARG;
+    if (!(C == 32 ? resident_pick_tile<Block32>(N, H, W, tr, tc) : C == 48 ? resident_pick_tile<Block48>(N, H, W, tr, tc) : pick_tile96(N, H, W, tr, tc))) return PAM_E_ARG;
     out2[0] = tr; out2[1] = tc;
     return PAM_OK;
 }
@@ -665,21 +602,5 @@ extern "C" int pam_basic_block2_nhwc_bf16(void* stream, const void* in, const vo
     if ((size_t)N * H * W * C * 2 >= (1ull << 31)) return PAM_E_ARG;
     if (C == 32) return pam_bb32_launch(stream, in, wpack, out, N, H, W, tile_rows, tile_cols);
     if (C == 96) return launch_bb96(stream, in, wpack, out, N, H, W, tile_rows, tile_cols);
-    BB2Args a;
-    a.in = (const uint16_t*)in; a.wpack = (const char*)wpack; a.out = (uint16_t*)out;
-    a.N = N; a.H = H; a.W = W;
-    if (tile_rows > 0 && tile_cols > 0) { a.TR = tile_rows; a.TC = tile_cols; }
-    else if (!pick_tile(N, H, W, a.TR, a.TC)) return PAM_E_ARG;
-    if ((a.TR + 2) * (a.TC + 4) > 16 * 8 * MW1 || a.TR * (a.TC + 2) > 16 * 8 * MW2 || (a.TR + 4) * (a.TC + 4) > XSLOTS_MAX) return PAM_E_ARG;
-    a.tiles_y = (H + a.TR - 1) / a.TR; a.tiles_x = (W + a.TC - 1) / a.TC;
-    a.nitems = N * a.tiles_y * a.tiles_x;
-    a.inv_pwx = 1.0f / (float)(a.TC + 4); a.inv_pwi = 1.0f / (float)(a.TC + 2);
-    a.xbytes = ((a.TR + 4) * (a.TC + 4) * PA + 1023) / 1024 * 1024;
-    const size_t lds = (size_t)a.xbytes + (size_t)WPIECES * 1024;
-    if (!pam_max_dynamic_lds((const void*)k_bblock2_48, 160 * 1024)) return PAM_E_HIP;
-#ifdef PAM_DIAG
-    a.stamps = g_bb2_stamps;
-#endif
-    pam_launch(k_bblock2_48, dim3(a.nitems), dim3(512), lds, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+    return resident_block_launch<Launch48>(stream, in, wpack, out, N, H, W, tile_rows, tile_cols);
 }

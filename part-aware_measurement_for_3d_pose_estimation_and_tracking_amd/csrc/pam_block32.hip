@@ -17,19 +17,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pam.h"
-#include "pam_kernel.hpp"
+#include "pam_resident.hpp"
 
 namespace {
 
-constexpr int PA = 64;                     // bytes per activation slot (32 bf16)
-constexpr int NST = 9;                     // k-steps per convolution (one per tap)
-constexpr int SUB = 32 * 64;               // one k-step's weight image: [32 rows][64 B]
-constexpr int WIMG = NST * SUB;            // 18 432 B per convolution = 18 DMA pieces
-constexpr int MW1 = 6, MW2 = 5;            // M tiles (16 slots) per wave, conv1 / conv2
-constexpr int TST = 8 * 16 * PA;           // byte distance between a wave's consecutive M tiles (tile = wave + 8 i)
-constexpr int WPIECES = 1 + 2 * WIMG / 1024;   // bias piece + both weight images = 37 pieces of 1 KiB
-constexpr int LDS_MAX = 160 * 1024;
-constexpr int XSLOTS_MAX = (LDS_MAX - WPIECES * 1024) / PA;
+// 64-byte slots, 9 k-step images of [32 rows][64 B], 6 / 5 M tiles per wave for conv1 / conv2, 37 DMA pieces of bias + weights (csrc/pam_resident.hpp)
+constexpr int PA = Block32::PA, NST = Block32::NST, WIMG = Block32::WIMG, MW1 = Block32::MW1, MW2 = Block32::MW2, TST = Block32::TST, WPIECES = Block32::WPIECES;
 
 struct BB32Args {
     const uint16_t* in; const char* wpack; uint16_t* out;
@@ -41,34 +34,6 @@ __device__ __attribute__((aligned(64))) const uint32_t g_bb32_zero[16] = {0};
 
 // byte offset of piece `logical` of slot s in a swizzled activation image
 __device__ __forceinline__ unsigned slot_piece(int s, int logical) { return (unsigned)(s * PA + ((logical ^ ((s >> 2) & 3)) << 4)); }
-
-// One convolution of a wave: MT M tiles x 2 N tiles, K walked once, fragments of k-step st + 1 read under the MFMAs of k-step st.
-// wl: this lane's row of k-step 0 in the weight image (swizzled piece included); xl: the slot base of the wave's first M tile;
-// koff[st]: byte offset of the lane's 8-channel slice of k-step st (tap shift, swizzled piece) from xl.
-template <int MT, typename Top>
-__device__ __forceinline__ void conv_pass32(f32x4 (&acc)[MW1][2], const char* wl, const char* xl, const unsigned (&koff)[NST], Top top) {
-    bf16x8 af[2][2], bf[2][MT];
-    auto ld = [&](int st, bf16x8* a_, bf16x8* b_) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) a_[j] = *(const bf16x8*)(wl + st * SUB + j * 1024);
-#pragma unroll
-        for (int i = 0; i < MT; ++i) b_[i] = *(const bf16x8*)(xl + koff[st] + i * TST);
-    };
-    ld(0, af[0], bf[0]);
-#pragma unroll
-    for (int st = 0; st < NST; ++st) {
-        const int cur = st & 1, nxt = cur ^ 1;
-        top(st);
-        if (st + 1 < NST) ld(st + 1, af[nxt], bf[nxt]);
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[cur][j]), __builtin_bit_cast(bf16x8_t, bf[cur][i]), acc[i][j], 0, 0, 0);
-        spread<2 * MT, MT + 2>();
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
 
 __global__ __launch_bounds__(512) void k_bblock2_32(BB32Args a) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -116,6 +81,7 @@ __global__ __launch_bounds__(512) void k_bblock2_32(BB32Args a) {
     mk_koff(PWx, koff);
     const char* xl = Xb + b0 * PA;
     const char* wl = W1 + l15 * 64 + ((g ^ (l15 >> 2)) << 4);
+    auto xaddr = [&](int i, int st) { return xl + koff[st] + i * TST; };
     const int nt1 = ((a.TR + 2) * PWx + 15) >> 4, nt2 = (a.TR * PWi + 15) >> 4;          // M tiles that carry real slots
     const int mt1 = (nt1 - wave + 7) >> 3, mt2 = (nt2 - wave + 7) >> 3;                    // ... of this wave (tile = wave + 8 i)
 
@@ -137,10 +103,10 @@ __global__ __launch_bounds__(512) void k_bblock2_32(BB32Args a) {
             if (p < WPIECES) wdma(p);
         }
     };
-    if (mt1 > 5) conv_pass32<6>(acc, wl, xl, koff, top1);
-    else if (mt1 == 5) conv_pass32<5>(acc, wl, xl, koff, top1);
-    else if (mt1 == 4) conv_pass32<4>(acc, wl, xl, koff, top1);
-    else conv_pass32<3>(acc, wl, xl, koff, top1);
+    if (mt1 > 5) resident_pass<KStep32, 6>(acc, wl, xaddr, top1);
+    else if (mt1 == 5) resident_pass<KStep32, 5>(acc, wl, xaddr, top1);
+    else if (mt1 == 4) resident_pass<KStep32, 4>(acc, wl, xaddr, top1);
+    else resident_pass<KStep32, 3>(acc, wl, xaddr, top1);
 
     // intermediate = ReLU(conv1 + b1) as bf16 on a grid of pitch PWi, zero where the position lies outside the image
     u32x4 mid[MW1];
@@ -183,10 +149,10 @@ __global__ __launch_bounds__(512) void k_bblock2_32(BB32Args a) {
         for (int i = 0; i < MW2; ++i) { acc[i][0] = c0; acc[i][1] = c1; }
     }
     auto top2 = [](int) {};
-    if (mt2 > 4) conv_pass32<5>(acc, wl + WIMG, xl, koff, top2);
-    else if (mt2 == 4) conv_pass32<4>(acc, wl + WIMG, xl, koff, top2);
-    else if (mt2 == 3) conv_pass32<3>(acc, wl + WIMG, xl, koff, top2);
-    else conv_pass32<2>(acc, wl + WIMG, xl, koff, top2);
+    if (mt2 > 4) resident_pass<KStep32, 5>(acc, wl + WIMG, xaddr, top2);
+    else if (mt2 == 4) resident_pass<KStep32, 4>(acc, wl + WIMG, xaddr, top2);
+    else if (mt2 == 3) resident_pass<KStep32, 3>(acc, wl + WIMG, xaddr, top2);
+    else resident_pass<KStep32, 2>(acc, wl + WIMG, xaddr, top2);
 #pragma unroll
     for (int i = 0; i < MW2; ++i) {
         if (ooff[i] < 0) continue;
@@ -201,62 +167,15 @@ __global__ __launch_bounds__(512) void k_bblock2_32(BB32Args a) {
     }
 }
 
-// busiest SIMD's M tiles (tile t -> wave t % 8 -> SIMD t % 4; a wave multiplies at least `lo` tiles): the same cost model as k_bblock2_48's
-int simd_tiles32(int nt, int lo) {
-    int worst = 0;
-    for (int s = 0; s < 4; ++s) {
-        int sum = 0;
-        for (int w = s; w < 8; w += 4) { int m = nt > w ? (nt - w + 7) >> 3 : 0; sum += m < lo ? lo : m; }
-        if (sum > worst) worst = sum;
-    }
-    return worst;
-}
-
-bool fits32(int tr, int tc) {
-    return tr >= 1 && tc >= 1 && (tr + 2) * (tc + 4) <= 16 * 8 * MW1 && tr * (tc + 2) <= 16 * 8 * MW2 && (tr + 4) * (tc + 4) <= XSLOTS_MAX;
-}
+struct Launch32 : Block32 {
+    using Args = BB32Args;
+    static constexpr auto kernel = k_bblock2_32;
+    static constexpr bool REACH = true;                  // the X tile has ~120 KB: a small tile's junk reads can pass W2's end
+    static void diag(Args&) {}
+};
 
 }  // namespace
 
-// Tile of the 32-channel block for N x H x W: the (TR, TC) that minimises whole rounds of 256 workgroups x time of an item (fixed part
-// + the busiest SIMD's M tiles of both convolutions), ties -> fewer items -- pam_basic_block2_tile's rule at C = 48.
-bool pam_bb32_pick_tile(int N, int H, int W, int& TR, int& TC) {
-    static thread_local int cN = 0, cH = 0, cW = 0, cTR = 0, cTC = 0;
-    if (N == cN && H == cH && W == cW) { TR = cTR; TC = cTC; return true; }
-    long best = -1;
-    for (int tr = 1; tr <= H; ++tr)
-        for (int tc = 1; tc <= W; ++tc) {
-            if (!fits32(tr, tc)) continue;
-            const int s1 = (tr + 2) * (tc + 4), s2 = tr * (tc + 2);
-            const long items = (long)N * ((H + tr - 1) / tr) * ((W + tc - 1) / tc);
-            const long per = 8 + simd_tiles32((s1 + 15) / 16, 3) + simd_tiles32((s2 + 15) / 16, 2);
-            const long cost = ((items + 255) / 256) * per * 4096 + items;
-            if (best < 0 || cost < best) { best = cost; TR = tr; TC = tc; }
-        }
-    if (best < 0) return false;
-    cN = N; cH = H; cW = W; cTR = TR; cTC = TC;
-    return true;
-}
-
 int pam_bb32_launch(void* stream, const void* in, const void* wpack, void* out, int N, int H, int W, int tile_rows, int tile_cols) {
-    BB32Args a;
-    a.in = (const uint16_t*)in; a.wpack = (const char*)wpack; a.out = (uint16_t*)out;
-    a.N = N; a.H = H; a.W = W;
-    if (tile_rows > 0 && tile_cols > 0) { a.TR = tile_rows; a.TC = tile_cols; }
-    else if (!pam_bb32_pick_tile(N, H, W, a.TR, a.TC)) return PAM_E_ARG;
-    if (!fits32(a.TR, a.TC)) return PAM_E_ARG;
-    a.tiles_y = (H + a.TR - 1) / a.TR; a.tiles_x = (W + a.TC - 1) / a.TC;
-    a.nitems = N * a.tiles_y * a.tiles_x;
-    a.inv_pwx = 1.0f / (float)(a.TC + 4); a.inv_pwi = 1.0f / (float)(a.TC + 2);
-    a.xbytes = ((a.TR + 4) * (a.TC + 4) * PA + 1023) / 1024 * 1024;
-    // junk M tiles of conv1 read up to 2 rows + 2 slots past the wave's last tile (a wave multiplies 3 tiles at least): keep those reads
-    // inside the allocation
-    const int mt_max = ((((a.TR + 2) * (a.TC + 4) + 15) >> 4) + 7) >> 3;
-    const size_t reach = (size_t)(16 * 8 * (mt_max < 3 ? 3 : mt_max) + 2 * (a.TC + 4) + 3) * PA;
-    size_t lds = (size_t)a.xbytes + (size_t)WPIECES * 1024;
-    if (reach > lds) lds = reach;
-    if (lds > (size_t)LDS_MAX) return PAM_E_ARG;
-    if (!pam_max_dynamic_lds((const void*)k_bblock2_32, LDS_MAX)) return PAM_E_HIP;
-    pam_launch(k_bblock2_32, dim3(a.nitems), dim3(512), lds, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+    return resident_block_launch<Launch32>(stream, in, wpack, out, N, H, W, tile_rows, tile_cols);
 }

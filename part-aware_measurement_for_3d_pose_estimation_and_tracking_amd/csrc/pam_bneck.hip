@@ -246,18 +246,7 @@ __global__ __launch_bounds__(512, 1) void k_bneck(BnArgs a) {
 template <bool HAS2, bool DOWN>
 int launch_bneck(hipStream_t s, const BnArgs& a) {
     if (!pam_max_dynamic_lds((const void*)k_bneck<HAS2, DOWN>, LDS_BYTES)) return PAM_E_HIP;
-    int ncu = 256;
-    {
-        static thread_local int cached_dev = -1, cached_cu = 256;
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            if (dev != cached_dev) {
-                hipDeviceProp_t pr;
-                if (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) { cached_cu = pr.multiProcessorCount; cached_dev = dev; }
-            }
-            ncu = cached_cu;
-        }
-    }
+    const int ncu = pam_cu_count();
     const int grid = a.ntiles < ncu ? a.ntiles : ncu;
     pam_launch(k_bneck<HAS2, DOWN>, dim3(grid), dim3(512), LDS_BYTES, s, a);
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;

@@ -24,14 +24,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pam.h"
-#include "pam_kernel.hpp"
+#include "pam_resident.hpp"
 
 namespace {
 
-constexpr int PA = 96;                     // bytes per input slot (48 bf16)
-constexpr int NST = 14;                    // k-steps of 32 (432 = 13.5 x 32, zero weights in the tail)
-constexpr int SUB = 48 * 64;               // one k-step's weight image: [48 rows][64 B]
-constexpr int WIMG = NST * SUB;            // 43 008 B per 48-channel slab = 42 DMA pieces
+constexpr int PA = KStep48::PA, NST = KStep48::NST, WIMG = KStep48::WIMG;      // 96-byte slots; a 48-channel slab = 14 k-step images = 42 DMA pieces
 constexpr int WPW = 6;                     // DMA pieces per wave and slab (42 pieces over 8 waves; a wave short of one re-sends the last)
 constexpr int BIASB = 2048;                // float32 bias of the workgroup's slabs (at most 8 x 48)
 constexpr int MTMAX = 3;                   // M tiles per wave at most
@@ -45,33 +42,6 @@ struct D48Args {
 };
 
 __device__ __attribute__((aligned(64))) const uint32_t g_d48_zero[16] = {0};
-
-// One slab of a wave: MT M tiles x 3 N tiles, K walked once, fragments of k-step st + 1 read under the MFMAs of k-step st.
-// wl: this lane's row of k-step 0 in the slab's weight image; xl[i]: this lane's window corner of M tile i; koff[st]: byte offset of the
-// lane's 8-channel slice of k-step st (tap shift in the parity-planar patch + channel).
-template <int MT>
-__device__ __forceinline__ void slab_pass(f32x4 (&acc)[MTMAX][3], const char* wl, const char* const (&xl)[MTMAX], const unsigned (&koff)[NST]) {
-    bf16x8 af[2][3], bf[2][MT];
-    auto ld = [&](int st, bf16x8* a_, bf16x8* b_) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) a_[j] = *(const bf16x8*)(wl + st * SUB + j * 1024);
-#pragma unroll
-        for (int i = 0; i < MT; ++i) b_[i] = *(const bf16x8*)(xl[i] + koff[st]);
-    };
-    ld(0, af[0], bf[0]);
-#pragma unroll
-    for (int st = 0; st < NST; ++st) {
-        const int cur = st & 1, nxt = cur ^ 1;
-        if (st + 1 < NST) ld(st + 1, af[nxt], bf[nxt]);
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[cur][j]), __builtin_bit_cast(bf16x8_t, bf[cur][i]), acc[i][j], 0, 0, 0);
-        if constexpr (MT >= 2) spread<3 * MT, MT + 3>();
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
 
 __global__ __launch_bounds__(512) void k_down48(D48Args a) {
     extern __shared__ __attribute__((aligned(1024))) char smem[];
@@ -155,8 +125,8 @@ __global__ __launch_bounds__(512) void k_down48(D48Args a) {
         const int oy = ty0 + r2, ox = tx0 + c2;
         ooff[i] = (in_tile && oy < a.Ho && ox < a.Wo) ? (long)(((size_t)n * a.Ho + oy) * a.Wo + ox) : -1;
     }
-    const int sw = (0x78 >> ((l15 >> 2) * 2)) & 3;                      // the weight images' piece swizzle sigma = (0, 2, 3, 1)
-    const unsigned wlo = (unsigned)(l15 * 64 + ((g ^ sw) * 16));
+    const unsigned wlo = (unsigned)(l15 * 64 + ((g ^ KStep48::sigma(l15)) * 16));
+    auto xaddr = [&](int i, int st) { return xl[i] + koff[st]; };
 
     asm volatile("s_barrier" ::: "memory");                              // patch, bias and slab 0 are in LDS (everybody's share)
 
@@ -181,9 +151,9 @@ __global__ __launch_bounds__(512) void k_down48(D48Args a) {
         }
         const char* wl = Wb + (s & 1) * WIMG + wlo;
         // wave-uniform choice of the instantiation: a wave multiplies only the M tiles that carry positions
-        if (mt >= 3) slab_pass<3>(acc, wl, xl, koff);
-        else if (mt == 2) slab_pass<2>(acc, wl, xl, koff);
-        else if (mt == 1) slab_pass<1>(acc, wl, xl, koff);
+        if (mt >= 3) resident_pass<KStep48, 3>(acc, wl, xaddr, [](int) {});
+        else if (mt == 2) resident_pass<KStep48, 2>(acc, wl, xaddr, [](int) {});
+        else if (mt == 1) resident_pass<KStep48, 1>(acc, wl, xaddr, [](int) {});
         if (s + 1 < a.spw) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // this wave's pieces of slab s + 1 (issued a slab ago) have landed
             asm volatile("s_barrier" ::: "memory");                       // everybody is done reading buffer s & 1; slab s + 1 is complete
@@ -206,22 +176,9 @@ __global__ __launch_bounds__(512) void k_down48(D48Args a) {
                 ov[2 * j] = pack_bf16x2(v0, v1); ov[2 * j + 1] = pack_bf16x2(v2, v3);
                 if (j < 2 ? relu_lo : relu_hi) { ov[2 * j] = relu_bf16x2(ov[2 * j]); ov[2 * j + 1] = relu_bf16x2(ov[2 * j + 1]); }
             }
-            uint16_t* d = a.out + ooff[i] * a.out_cs + cb;
-            *(u32x4*)(d + 8 * g) = (u32x4){ov[0], ov[1], ov[2], ov[3]};
-            *(u32x2*)(d + 32 + 4 * g) = (u32x2){ov[4], ov[5]};
+            KStep48::store12(a.out + ooff[i] * a.out_cs + cb, g, ov);
         }
     }
-}
-
-// worst number of M tiles on one SIMD (tile t -> wave t % 8; waves w and w + 4 share a SIMD)
-int d48_simd_tiles(int ntile) {
-    int worst = 0;
-    for (int s = 0; s < 4; ++s) {
-        int sum = 0;
-        for (int w = s; w < 8; w += 4) sum += ntile > w ? (ntile - w + 7) >> 3 : 0;
-        if (sum > worst) worst = sum;
-    }
-    return worst;
 }
 
 // Tile and slab grouping of a layer: the cheapest (rounds of 256 workgroups) x (time of a workgroup), where a workgroup's time is its
@@ -242,7 +199,7 @@ bool d48_pick(int N, int Ho, int Wo, int nslab, int& TR, int& TC, int& G) {
                 const int spw = nslab / gsz;
                 if (spw * 48 * 4 > BIASB) continue;
                 const long fill = ((long)xs * PA + (long)spw * WIMG) / 24;
-                const long mfma = (long)d48_simd_tiles(nt) * 3 * NST * 16 * spw;
+                const long mfma = (long)simd_tiles(nt, 0) * 3 * NST * 16 * spw;
                 const long t = 5000 + (fill > mfma ? fill + mfma / 4 : mfma + fill / 4) + 500L * spw;
                 const long wgs = items * gsz;
                 const long cost = ((wgs + 255) / 256) * t * 4096 + wgs;

@@ -261,18 +261,7 @@ extern "C" int pam_fuse_sum_nhwc_bf16(void* stream, const void* base, int n_plai
     if (nt >= (1ll << 30)) return PAM_E_ARG;
     a.ntiles = (int)nt;
     a.inv_otw = 1.0f / (float)a.OTW;
-    int ncu = 256;
-    {
-        static thread_local int cached_dev = -1, cached_cu = 256;
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            if (dev != cached_dev) {
-                hipDeviceProp_t pr;
-                if (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) { cached_cu = pr.multiProcessorCount; cached_dev = dev; }
-            }
-            ncu = cached_cu;
-        }
-    }
+    const int ncu = pam_cu_count();
     // every workgroup walks the same number of tiles: 360 tiles -> 180 workgroups x 2 (not 256 of which 104 walk two); the CUs left over
     // take the other outputs' sums, which run on the branch streams at the same time
     int grid = max_workgroups > 0 && max_workgroups < ncu ? max_workgroups : ncu;

@@ -95,6 +95,19 @@ static inline void pam_launch(void (*kernel)(A), dim3 grid, dim3 block, size_t l
     hipLaunchKernelGGL(kernel, grid, block, lds, s, a);
 }
 
+// Compute units of the current device, for the kernels whose grid is one persistent workgroup per CU.  The answer is kept per thread and
+// asked again when the thread's current device changes; 256 (an MI355X) where HIP cannot name the device.
+static inline int pam_cu_count() {
+    static thread_local int cached_dev = -1, cached_cu = 256;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    if (dev != cached_dev) {
+        hipDeviceProp_t pr;
+        if (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) { cached_cu = pr.multiProcessorCount; cached_dev = dev; }
+    }
+    return cached_cu;
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to a DEVICE's copy of a function: set it once per (function, device) -- a process that
 // drives a second GPU would otherwise launch with > 64 KB of LDS without the attribute and fail.  Returns false on a HIP error.
 static inline bool pam_max_dynamic_lds(const void* func, int bytes) {

@@ -297,18 +297,7 @@ extern "C" int pam_stem_fused_nhwc_bf16(void* stream, const void* in, const void
     if (nt >= (1ll << 30)) return PAM_E_ARG;
     a.ntiles = (int)nt;
     if (!pam_max_dynamic_lds((const void*)k_stem_fused, LDS_BYTES + 768)) return PAM_E_HIP;
-    int ncu = 256;
-    {
-        static thread_local int cached_dev = -1, cached_cu = 256;
-        int dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            if (dev != cached_dev) {
-                hipDeviceProp_t pr;
-                if (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) { cached_cu = pr.multiProcessorCount; cached_dev = dev; }
-            }
-            ncu = cached_cu;
-        }
-    }
+    const int ncu = pam_cu_count();
     const int grid = a.ntiles < ncu ? a.ntiles : ncu;
     pam_launch(k_stem_fused, dim3(grid), dim3(512), LDS_BYTES + 768, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
