@@ -650,10 +650,15 @@ int pam_bottleneck_tail_nhwc_bf16(void* stream, const void* y2, const void* x0, 
  * bias_s)): base / out / plain_t (N, H, W, C) NHWC bf16, C in {48, 96, 192} (plain_t may be channel slices: plain_cstrides, NULL = C);
  * src_s (N, H >> shift_s, W >> shift_s, up_channels[s]) with ascending shifts, up_channels % 32 == 0, H and W multiples of 2^shift;
  * up_wimg[s]: the 1x1 weights (C x up_channels[s]) as MFMA A fragments, bf16 [C / 16][up_channels / 32][64 lanes][8]: lane l of fragment
- * (j, ks) holds W[16 j + (l & 15)][32 ks + 8 (l >> 4) .. + 7]; up_bias[s]: float32 [C] or NULL.  n_plain <= 2, 1 <= n_up <= 3.  Persistent
- * workgroups (at most one per CU, at most max_workgroups when that is > 0: several outputs of a module then share the chip) keep all the
- * 1x1 weights in LDS and walk tiles of tile_a x tile_b pixels of the coarsest source (<= 0: the library's choice, 1 x 3); the products
- * never reach HBM; sum order = base, plain terms, up terms (the order of pam_upsample_add_nhwc_bf16 with the terms in branch order).  Results are
+ * (j, ks) holds W[16 j + (l & 15)][32 ks + 8 (l >> 4) .. + 7]; up_bias[s]: float32 [C] or NULL.  n_plain <= 2, 1 <= n_up <= 3.  The k loops
+ * are unrolled per source, so up_channels[s] must be C << up_shifts[s] and the shifts one of (1), (1, 2), (1, 2, 3) for C = 48, (1), (1, 2),
+ * (2) for C = 96, (1) for C = 192 (every HRNet fuse layer; anything else: PAM_E_ARG).  One small workgroup (C / 16 waves, each with its
+ * channel tile's 1x1 weights of all sources in registers) per unit of 16 pixels of an anchor level L, i.e. 16 blocks of 2^L x 2^L output
+ * pixels; the products never reach HBM; sum order = base, plain terms, up terms (the order of pam_upsample_add_nhwc_bf16 with the terms in
+ * branch order).  tile_a, tile_b and max_workgroups are HINTS, any value gives the same results: tile_a > 0 asks for the anchor level
+ * L = tile_a (clamped to min(2, coarsest shift)); tile_b is not used.  With tile_a <= 0 the library chooses the level and, for the sizes
+ * where it is still the faster one (C = 192 outside 65 .. one unit per CU, C = 96 under two sources above 768 units), the earlier
+ * persistent kernel (one workgroup per CU at most, weights in LDS), which alone honours max_workgroups > 0 as a cap.  Results are
  * bit-identical to pam_conv2d_nhwc_bf16 (1x1) per source followed by pam_upsample_add_nhwc_bf16. */
 int pam_conv3x3s2_c48_tile(int N, int H, int W, int Cout, int32_t* out3);
 /* the same convolution for Cin = 96 / 192 (k_down_s: the streamed 3x3 kernel with a stride-2, parity-planar patch; no residual).

@@ -146,13 +146,16 @@ class HipHRNet(ConvEngine):
                                 # 96-channel branch on the streamed-weights fused block (k_bblock2_96) -- csrc/pam_block2.hip
     c96_slab = 48               # 96 -> 96 layers that are NOT fused: k_conv3x3s with 48-channel slabs (0 = k_conv3x3)
     stamp = None                # diagnostics (tools/fwd_stamps.py): callable(tag) issued on the current stream at points of the schedule
-    fs_cap = (0, 0, 0, 0)       # workgroups of output i's fused sum at most (0 = one per CU): the sums of a module's outputs run side by side
+    fs_cap = (0, 0, 0, 0)       # max_workgroups of output i's fused sum (0 = none).  A hint since DESIGN section 10s: only the persistent kernel,
+                                # which the library still takes for a few sizes, caps its grid by it; the register-weights kernel ignores it
     fused_sums = False          # round 5: True = the fuse layers' 1x1 up-convolutions inside the sum launch (k_fuse_sum: 203 launches instead of 221,
-                                # bit-identical); False = one merged 1x1 launch per source branch + k_upsample_add.  Measured at 20 crops,
-                                # interleaved A/B: -1.5 ... +0.3 % per forward -- the 1x1 launches ran beside the other branches' blocks and
-                                # were hidden, while the sums sit behind the module's join on the critical path and a persistent
-                                # one-workgroup-per-CU kernel (the weights take 64-147 KB of LDS) streams slower than k_upsample_add's
-                                # many small workgroups (20.9 vs 7.9 us for output 0 of a stage-4 module).  Off by default.
+                                # bit-identical); False = one merged 1x1 launch per source branch + k_upsample_add.  The 1x1 launches ran
+                                # beside the other branches' blocks and were hidden, while the sums sit behind the module's join on the
+                                # critical path.  Until DESIGN section 10s the sum was a persistent one-workgroup-per-CU kernel with the
+                                # weights in LDS (20.9 vs k_upsample_add's 7.9 us for output 0 of a stage-4 module) and the fused form was
+                                # within -1.5 ... +0.3 % of the un-fused one at 20 crops; now small independent workgroups keep the
+                                # weights in registers (15.3 us for that output, 7.5 us for stage 2's; section 10s has the forward's A/B).
+                                # Off by default; config_for turns it on by crop count.
     knock_conv2 = 0             # diagnostics: 1 = the second convolution of every un-fused BasicBlock is not issued
     knock_up = 0                # diagnostics: 1 = the coarsest branch's merged 1x1 up-convolution is not issued (its output stays uninitialised)
     knock_out = 0               # diagnostics: bit b = skip the BasicBlocks of branch b (what a free branch would be worth: tools/ab_flags.py)

@@ -89,12 +89,12 @@ if a.only in ('', 'sum'):
             h, w, c, shifts, npl, cnt, ' + '.join('%.1f' % t for t in tc_), tu, sum(tc_) + tu, tf)
         if a.sweep:
             res = []
-            for ta, tb in ((1, 3), (2, 3), (4, 3), (4, 6), (8, 12), (2, 9), (4, 9), (8, 6)):
+            # tile = (anchor level L of the register-weights kernel, unused); L is clamped to min(2, coarsest shift)
+            for ta, tb in [(L, 0) for L in range(1, min(2, shifts[-1]) + 1)]:
                 try:
                     res.append((timeit(lambda: e.fuse_sum(op, base, plain, srcs, tile=(ta, tb)), 10), ta, tb))
                 except Exception:
                     pass
             res.sort()
-            line += '   best: ' + ', '.join('%.1f us @ %dx%d' % r for r in res[:4])
-            line += '   capped: ' + ', '.join('%d wg %.1f us' % (q, timeit(lambda: e.fuse_sum(op, base, plain, srcs, max_wg=q), 10)) for q in (64, 128, 192))
+            line += '   best: ' + ', '.join('%.1f us @ L%d' % (t, L) for t, L, p in res)
         print(line, flush=True)
