@@ -646,20 +646,27 @@ int pam_bottleneck_tail_nhwc_bf16(void* stream, const void* y2, const void* x0, 
  * slab_groups <= 0: the library's choice (pam_conv3x3s2_c48_tile writes {rows, cols, groups}); slab_groups = workgroups an item's slabs
  * are spread over (divides Cout / 48).  Results are bit-identical to pam_conv2d_nhwc_bf16 (same K order per output element).
  *
- * pam_fuse_sum_nhwc_bf16 (csrc/pam_fuse.hip, k_fuse_sum): out = [ReLU](base + sum_t plain_t + sum_s nearest_up_{2^shift_s}(W_s . src_s +
+ * pam_fuse_sum_nhwc_bf16 (csrc/pam_fuse.hip: one front, two kernels, k_fuse_sum and k_fuse_sum_lds): out = [ReLU](base + sum_t plain_t + sum_s nearest_up_{2^shift_s}(W_s . src_s +
  * bias_s)): base / out / plain_t (N, H, W, C) NHWC bf16, C in {48, 96, 192} (plain_t may be channel slices: plain_cstrides, NULL = C);
  * src_s (N, H >> shift_s, W >> shift_s, up_channels[s]) with ascending shifts, up_channels % 32 == 0, H and W multiples of 2^shift;
  * up_wimg[s]: the 1x1 weights (C x up_channels[s]) as MFMA A fragments, bf16 [C / 16][up_channels / 32][64 lanes][8]: lane l of fragment
  * (j, ks) holds W[16 j + (l & 15)][32 ks + 8 (l >> 4) .. + 7]; up_bias[s]: float32 [C] or NULL.  n_plain <= 2, 1 <= n_up <= 3.  The k loops
- * are unrolled per source, so up_channels[s] must be C << up_shifts[s] and the shifts one of (1), (1, 2), (1, 2, 3) for C = 48, (1), (1, 2),
- * (2) for C = 96, (1) for C = 192 (every HRNet fuse layer; anything else: PAM_E_ARG).  One small workgroup (C / 16 waves, each with its
+ * are unrolled per source, so up_channels[s] must be C << up_shifts[s] and (C, shifts) a row of the table FUSE_COMBOS of
+ * csrc/pam_fuse_plan.hpp: (1), (1, 2), (1, 2, 3) for C = 48, (1), (1, 2), (2) for C = 96, (1) for C = 192 (every HRNet fuse layer;
+ * anything else: PAM_E_ARG at every size, looked up before a kernel is chosen).  k_fuse_sum: one small workgroup (C / 16 waves, each with its
  * channel tile's 1x1 weights of all sources in registers) per unit of 16 pixels of an anchor level L, i.e. 16 blocks of 2^L x 2^L output
  * pixels; the products never reach HBM; sum order = base, plain terms, up terms (the order of pam_upsample_add_nhwc_bf16 with the terms in
- * branch order).  tile_a, tile_b and max_workgroups are HINTS, any value gives the same results: tile_a > 0 asks for the anchor level
+ * branch order; the three kernels share one statement of it, sum8_* of csrc/pam_kernel.hpp).  tile_a, tile_b and max_workgroups are
+ * HINTS, any value gives the same results: tile_a > 0 asks for the anchor level
  * L = tile_a (clamped to min(2, coarsest shift)); tile_b is not used.  With tile_a <= 0 the library chooses the level and, for the sizes
  * where it is still the faster one (C = 192 outside 65 .. one unit per CU, C = 96 under two sources above 768 units), the earlier
- * persistent kernel (one workgroup per CU at most, weights in LDS), which alone honours max_workgroups > 0 as a cap.  Results are
- * bit-identical to pam_conv2d_nhwc_bf16 (1x1) per source followed by pam_upsample_add_nhwc_bf16. */
+ * persistent kernel k_fuse_sum_lds (one workgroup per CU at most, weights in LDS), which alone honours max_workgroups > 0 as a cap.
+ * Results are bit-identical to pam_conv2d_nhwc_bf16 (1x1) per source followed by pam_upsample_add_nhwc_bf16.
+ * pam_fuse_sum_plan: the same decision (csrc/pam_fuse_plan.hpp) asked without a launch: PAM_OK exactly when pam_fuse_sum_nhwc_bf16 would
+ * accept these integers with every pointer given and plain_cstrides NULL, else PAM_E_ARG (a NULL out8 too) with out8 left alone.
+ * out8 = {kernel (1 = k_fuse_sum, 2 = k_fuse_sum_lds), L (0 for kernel 2), log2 of the unit's rows | tile rows TA of the coarsest
+ * source, log2 of the unit's columns | TB, units | tiles per image down, across, workgroups, dynamic LDS bytes}.  n_cu <= 0: the current
+ * device's compute units (256 where there is no device).  Touches no device memory and works on a machine without a GPU. */
 int pam_conv3x3s2_c48_tile(int N, int H, int W, int Cout, int32_t* out3);
 /* the same convolution for Cin = 96 / 192 (k_down_s: the streamed 3x3 kernel with a stride-2, parity-planar patch; no residual).
  * pam_conv3x3s2_slab: the slab width BN (64 or 48 output channels) the library takes for this shape, 0 = not taken (generic kernel);
@@ -677,6 +684,8 @@ int pam_fuse_sum_nhwc_bf16(void* stream, const void* base, int n_plain, const vo
                            const void* const* up_src, const int32_t* up_shifts, const int32_t* up_channels, const void* const* up_wimg,
                            const float* const* up_bias, void* out, int N, int H, int W, int C, int relu, int tile_a, int tile_b,
                            int max_workgroups);
+int pam_fuse_sum_plan(int N, int H, int W, int C, int n_plain, int n_up, const int32_t* up_shifts, const int32_t* up_channels,
+                      int tile_a, int tile_b, int max_workgroups, int n_cu, int32_t* out8);
 
 /* ---- round 5: device-side ordering of the forward's branch streams (csrc/pam_sync.hip; the module-end exchange of hrnet_model.py, HighResolutionModule inside
  * the absent HRNet backend, /root/reference/src/ivclabpose.py:210).  pam_flag_signal: one agent-scope atomic add on *dev_counter behind

@@ -4,6 +4,13 @@
 // down_ij = the result of the strided-convolution chain from the finer branch j (already at out_i's resolution: a "plain" term);
 // the coarser branches j > i enter through a 1x1 convolution at THEIR resolution, up-sampled by pixel replication.
 //
+// ONE FRONT, TWO KERNELS.  The entry point at the end of the file checks the pointers, asks fuse_plan() (pam_fuse_plan.hpp: the argument
+// check, the table FUSE_COMBOS of instantiated (C, shifts), which kernel, level, units or tiles, grid, LDS layout -- every shape rule, as
+// pure integer arithmetic that pam_fuse_sum_plan and a test without a GPU ask too), fills the chosen kernel's argument struct from the
+// plan and launches: k_fuse_sum (register weights, below) or, for the sizes where it was not beaten, the earlier k_fuse_sum_lds
+// (persistent, weights in LDS; further down).  Both compute the sum of sum8_start / sum8_add / sum8_finish (pam_kernel.hpp), which is
+// k_upsample_add's: bit-identical to pam_conv2d_nhwc_bf16 (1x1) + pam_upsample_add_nhwc_bf16.
+//
 // Until round 5 the 1x1 products were launches of their own (18 per forward on the generic gather kernel: 2 % of the MFMA roof, 12 % of
 // the HBM roof, each on some branch's tail in front of the module's join) whose results went to HBM and came back into k_upsample_add.
 // k_fuse_sum: MANY SMALL, INDEPENDENT workgroups of NT = C / 16 waves (3, 6 or 12); wave j owns the output-channel tile j and holds the
@@ -18,11 +25,11 @@
 // its output rectangle 16 bytes per lane (a lane-by-lane walk of the pixels under the anchor pixel, 8 bytes per access and no LDS, lost
 // by 1.3 - 3.3 us at 20 crops and was taken out).  No persistent walk, no specialised wave, no dependence between workgroups: the
 // latencies hide behind the other workgroups of the CU.  Nothing but base, plain terms, sources, weights and out touches memory.
-// Bit-identical to pam_conv2d_nhwc_bf16 (1x1) + pam_upsample_add_nhwc_bf16.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pam.h"
 #include "pam_kernel.hpp"
+#include "pam_fuse_plan.hpp"
 
 namespace {
 
@@ -171,24 +178,15 @@ __global__ __launch_bounds__(C / 16 * 64, 2) void k_fuse_sum(FSArgs a) {
             const int ry = pl[k] >> 16, rx = (pl[k] >> 8) & 255, c8 = pl[k] & 255;
             const int ra = ((ry >> L) << a.ub_log) | (rx >> L), dy = ry & BL, dx = rx & BL;
             float v[8];
+            sum8_start(v, vb[k]);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = bf16_to_f32((uint16_t)vb[k][e]);
-#pragma unroll
-            for (int t = 0; t < NPL; ++t) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] += bf16_to_f32((uint16_t)vp[t][k][e]);
-            }
-            auto add = [&](int tile) {
-                const bf16x8 q = *(const bf16x8*)(terms + (tile * 16 + ra) * C + c8 * 8);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] += bf16_to_f32((uint16_t)q[e]);
-            };
+            for (int t = 0; t < NPL; ++t) sum8_add(v, vp[t][k]);
+            auto add = [&](int tile) { sum8_add(v, *(const bf16x8*)(terms + (tile * 16 + ra) * C + c8 * 8)); };
             add(fs_tile_of<SH0, L>(dy, dx));
             if constexpr (NUP > 1) add(NTL0 + fs_tile_of<SH1, L>(dy, dx));
             if constexpr (NUP > 2) add(NTL0 + NTL1 + fs_tile_of<SH2, L>(dy, dx));
             bf16x8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (short)f32_to_bf16(a.relu ? fmaxf(v[e], 0.0f) : v[e]);
+            sum8_finish(v, a.relu, o);
             if (po[k] >= 0) *(bf16x8*)(a.out + (long)po[k] * C + c8 * 8) = o;
         }
     }
@@ -205,23 +203,28 @@ int launch_fs(hipStream_t s, const FSArgs& a, unsigned grid) {
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
 }
 
-// one (C, shifts): the anchor levels 1 .. min(2, the coarsest shift).  Level 3 is not built: 135 units at 20 crops leave half the CUs
-// idle, and a lane-by-lane walk of its 64 pixels did not fit the registers of two waves per SIMD without scratch.
-template <int C, int NUP, int SH0, int SH1, int SH2>
+// row I of FUSE_COMBOS: the anchor levels 1 .. min(2, the coarsest shift).  Level 3 is not built: 135 units at 20 crops leave half the
+// CUs idle, and a lane-by-lane walk of its 64 pixels did not fit the registers of two waves per SIMD without scratch.
+template <int I>
 int dispatch_fs(hipStream_t s, const FSArgs& a, unsigned grid, int L) {
-    constexpr int LMAX = NUP > 2 ? SH2 : (NUP > 1 ? SH1 : SH0);
-    if (L == 1) return launch_fs<C, NUP, SH0, SH1, SH2, 1>(s, a, grid);
-    if constexpr (LMAX >= 2)
-        if (L == 2) return launch_fs<C, NUP, SH0, SH1, SH2, 2>(s, a, grid);
+    constexpr FuseCombo K = FUSE_COMBOS[I];
+    if (L == 1) return launch_fs<K.C, K.n_up, K.sh[0], K.sh[1], K.sh[2], 1>(s, a, grid);
+    if constexpr (K.sh[K.n_up - 1] >= 2)
+        if (L == 2) return launch_fs<K.C, K.n_up, K.sh[0], K.sh[1], K.sh[2], 2>(s, a, grid);
     return PAM_E_ARG;
 }
+// every row of the table is instantiated, and nothing else
+template <int... I>
+int dispatch_fs(std::integer_sequence<int, I...>, int combo, hipStream_t s, const FSArgs& a, unsigned grid, int L) {
+    int rc = PAM_E_ARG;
+    ((combo == I ? (void)(rc = dispatch_fs<I>(s, a, grid, L)) : (void)0), ...);
+    return rc;
+}
 
-// ---- the persistent form the sums had until DESIGN section 10s, kept for the shapes where it is still the faster one (see the entry
-// point): one 576-thread workgroup per CU at most (eight worker waves + one loader wave), the 1x1 weights of all sources resident in
+// ---- the persistent form the sums had until DESIGN section 10s, kept for the shapes where it is still the faster one (fuse_takes_lds
+// in pam_fuse_plan.hpp): one 576-thread workgroup per CU at most (eight worker waves + one loader wave), the 1x1 weights of all sources resident in
 // LDS (64 - 147 KB), tiles of TA x TB pixels of the coarsest source walked by each workgroup, the next tile's source pixels arriving by
 // LDS-DMA while this one's products run out of LDS into term tiles.  Same arithmetic, same results.
-constexpr int FL_MAXI = 5;                 // 16-byte items of the output tile per thread at most
-
 struct FLArgs {
     const uint16_t* base; uint16_t* out;
     const uint16_t* plain[2]; int plain_cs[2]; int nplain;
@@ -358,7 +361,9 @@ __global__ __launch_bounds__(576) void k_fuse_sum_lds(FLArgs a) {
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                    // the term tiles are complete
 
-        // ---- out = [ReLU](base + plain terms + replicated products), k_upsample_add's order: base, then the terms in branch order
+        // ---- out = [ReLU](base + plain terms + replicated products), k_upsample_add's order: base, then the terms in branch order.
+        // The arithmetic of sum8_start / sum8_add / sum8_finish (pam_kernel.hpp) written out: with the helpers this kernel compiles to
+        // other code (134 -> 168 VGPRs and three spilled registers), so it keeps its text, and the bit-for-bit tests hold it to them
 #pragma unroll
         for (int k = 0; k < FL_MAXI; ++k) {
             if (eo[k] < 0) continue;
@@ -390,88 +395,40 @@ __global__ __launch_bounds__(576) void k_fuse_sum_lds(FLArgs a) {
 
 template <int C>
 int launch_fl(hipStream_t s, const FLArgs& a, size_t lds, int grid) {
-    if (!pam_max_dynamic_lds((const void*)k_fuse_sum_lds<C>, 160 * 1024)) return PAM_E_HIP;
+    if (!pam_max_dynamic_lds((const void*)k_fuse_sum_lds<C>, FL_LDS_MAX)) return PAM_E_HIP;
     pam_launch(k_fuse_sum_lds<C>, dim3(grid), dim3(576), lds, s, a);
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
 }
 
-// the persistent form's host side: LDS plan, tile choice (tile_a x tile_b pixels of the coarsest source, <= 0: the largest that fits),
-// at most max_workgroups workgroups when that is > 0
-int fuse_sum_lds(void* stream, const void* base, int n_plain, const void* const* plain, const int32_t* plain_cstrides,
-                  int n_up, const void* const* up_src, const int32_t* up_shifts, const int32_t* up_channels,
-                  const void* const* up_wimg, const float* const* up_bias, void* out, int N, int H, int W, int C,
-                  int relu, int tile_a, int tile_b, int max_workgroups) {
-    if (!base || !out || N < 1 || H < 1 || W < 1 || (C != 48 && C != 96 && C != 192) || n_plain < 0 || n_plain > 2 || n_up < 1 || n_up > 3) return PAM_E_ARG;
-    if ((size_t)N * H * W >= (1ull << 31)) return PAM_E_ARG;
-    FLArgs a;
-    a.base = (const uint16_t*)base; a.out = (uint16_t*)out; a.nplain = n_plain; a.nup = n_up;
+// what FSArgs and FLArgs have in common.  The caller has checked every pointer the counts name.
+template <typename A>
+void fuse_fill(A& a, const FuseQuery& q, const void* base, const void* const* plain, const void* const* up_src, const void* const* up_wimg,
+               const float* const* up_bias, void* out, int relu) {
+    a.base = (const uint16_t*)base; a.out = (uint16_t*)out; a.nplain = q.n_plain;
     for (int t = 0; t < 2; ++t) {
-        a.plain[t] = t < n_plain ? (const uint16_t*)plain[t] : nullptr;
-        a.plain_cs[t] = (t < n_plain && plain_cstrides && plain_cstrides[t] > 0) ? plain_cstrides[t] : C;
-        if (t < n_plain && (!a.plain[t] || a.plain_cs[t] < C || a.plain_cs[t] % 8 != 0)) return PAM_E_ARG;
+        a.plain[t] = t < q.n_plain ? (const uint16_t*)plain[t] : nullptr;
+        a.plain_cs[t] = (t < q.n_plain && q.plain_cs[t] > 0) ? q.plain_cs[t] : q.C;
     }
-    int prev = 0;
     for (int s = 0; s < 3; ++s) {
-        const bool on = s < n_up;
+        const bool on = s < q.n_up;
         a.src[s] = on ? (const uint16_t*)up_src[s] : nullptr; a.wimg[s] = on ? (const char*)up_wimg[s] : nullptr;
-        a.ubias[s] = (on && up_bias) ? up_bias[s] : nullptr; a.shift[s] = on ? up_shifts[s] : 0; a.src_c[s] = on ? up_channels[s] : 0;
-        a.w_off[s] = a.w_bytes[s] = a.src_off[s] = a.term_off[s] = 0;
-        if (!on) continue;
-        // sources in ascending shift (= branch) order; the map must be a whole number of source pixels (PyTorch's up-sampling needs that too)
-        if (!a.src[s] || !a.wimg[s] || a.shift[s] <= prev || a.shift[s] > 5 || a.src_c[s] < 32 || a.src_c[s] % 32 != 0) return PAM_E_ARG;
-        if (H % (1 << a.shift[s]) != 0 || W % (1 << a.shift[s]) != 0) return PAM_E_ARG;
-        prev = a.shift[s];
+        a.ubias[s] = (on && up_bias) ? up_bias[s] : nullptr;
     }
-    a.smax = a.shift[n_up - 1];
-    a.N = N; a.H = H; a.W = W; a.relu = relu ? 1 : 0;
-    // LDS plan for a tile of TA x TB pixels of the coarsest source; false = does not fit
-    const int c8 = C / 8;
-    size_t lds = 0;
-    auto plan = [&](int TA, int TB) {
-        if ((long)(TA << a.smax) * (TB << a.smax) * c8 > 512L * FL_MAXI || (TA << a.smax) > 32767 || (TB << a.smax) > 255) return false;
-        size_t o = 0;
-        for (int s = 0; s < n_up; ++s) { a.w_off[s] = (int)o; a.w_bytes[s] = C * a.src_c[s] * 2; o += (size_t)a.w_bytes[s]; }
-        a.bias_off = (int)o; o += (size_t)n_up * C * 4; o = (o + 1023) / 1024 * 1024;
-        size_t sb = 0;
-        for (int s = 0; s < n_up; ++s) { const int d = a.smax - a.shift[s]; a.src_off[s] = (int)sb; sb += (size_t)(TA << d) * (TB << d) * a.src_c[s] * 2; sb = (sb + 1023) / 1024 * 1024; }
-        a.src_bytes = (int)sb; a.src_base = (int)o; o += 2 * sb;
-        for (int s = 0; s < n_up; ++s) { const int d = a.smax - a.shift[s]; a.term_off[s] = (int)o; o += (size_t)(TA << d) * (TB << d) * C * 2; o = (o + 15) / 16 * 16; }
-        lds = o;
-        return o <= 160 * 1024;
-    };
-    int TA = tile_a, TB = tile_b;
-    if (TA <= 0 || TB <= 0) {
-        // the largest candidate that fits (FL_MAXI items per thread, LDS) and divides the coarsest map: an iteration costs two barriers and a
-        // round of latencies whatever its size; a 16 x 24 tile of output 0 is 2 304 items
-        const int Hc = H >> a.smax, Wc = W >> a.smax;
-        const int cand[8][2] = {{8, 12}, {4, 6}, {4, 3}, {2, 3}, {1, 3}, {1, 2}, {1, 1}, {0, 0}};
-        TA = 0;
-        for (int pass = 0; pass < 2 && TA == 0; ++pass)
-            for (int k = 0; cand[k][0] && TA == 0; ++k)
-                if ((pass == 1 || (Hc % cand[k][0] == 0 && Wc % cand[k][1] == 0)) && plan(cand[k][0], cand[k][1])) { TA = cand[k][0]; TB = cand[k][1]; }
-        if (TA == 0) return PAM_E_ARG;
-    }
-    if (!plan(TA, TB)) return PAM_E_ARG;
-    a.TA = TA; a.TB = TB; a.OTH = TA << a.smax; a.OTW = TB << a.smax;
-    a.tiles_y = (H + a.OTH - 1) / a.OTH; a.tiles_x = (W + a.OTW - 1) / a.OTW;
-    const long long nt = (long long)N * a.tiles_y * a.tiles_x;
-    if (nt >= (1ll << 30)) return PAM_E_ARG;
-    a.ntiles = (int)nt;
-    a.inv_otw = 1.0f / (float)a.OTW;
-    const int ncu = pam_cu_count();
-    // every workgroup walks the same number of tiles: 360 tiles -> 180 workgroups x 2 (not 256 of which 104 walk two); the CUs left over
-    // take the other outputs' sums, which run on the branch streams at the same time
-    int grid = max_workgroups > 0 && max_workgroups < ncu ? max_workgroups : ncu;
-    const int per_wg = (a.ntiles + grid - 1) / grid;
-    grid = (a.ntiles + per_wg - 1) / per_wg;
-    switch (C) {
-        case 48: return launch_fl<48>((hipStream_t)stream, a, lds, grid);
-        case 96: return launch_fl<96>((hipStream_t)stream, a, lds, grid);
-        default: return launch_fl<192>((hipStream_t)stream, a, lds, grid);
-    }
+    a.N = q.N; a.H = q.H; a.W = q.W; a.relu = relu ? 1 : 0;
 }
 
 }  // namespace
+
+// Which kernel, level, units or tiles, grid and dynamic LDS bytes pam_fuse_sum_nhwc_bf16 would launch with: fuse_plan() asked without a
+// launch (include/pam.h).  n_cu <= 0: the current device's compute units.
+extern "C" int pam_fuse_sum_plan(int N, int H, int W, int C, int n_plain, int n_up, const int32_t* up_shifts, const int32_t* up_channels,
+                                 int tile_a, int tile_b, int max_workgroups, int n_cu, int32_t* out8) {
+    if (!out8 || (n_up > 0 && (!up_shifts || !up_channels))) return PAM_E_ARG;
+    const FusePlan p = fuse_plan(fuse_query(N, H, W, C, n_plain, nullptr, n_up, up_shifts, up_channels, tile_a, tile_b, max_workgroups,
+                                            n_cu > 0 ? n_cu : pam_cu_count()));
+    if (p.rc == PAM_OK) fuse_plan_out8(p, out8);
+    return p.rc;
+}
 
 // up_wimg[s]: the 1x1 weights W (C x src_channels[s]) as MFMA A fragments, bf16 [C / 16][src_channels / 32][64 lanes][8]: lane l of fragment
 // (j, ks) holds W[16 j + (l & 15)][32 ks + 8 (l >> 4) .. + 7].
@@ -481,71 +438,32 @@ extern "C" int pam_fuse_sum_nhwc_bf16(void* stream, const void* base, int n_plai
                                       int n_up, const void* const* up_src, const int32_t* up_shifts, const int32_t* up_channels,
                                       const void* const* up_wimg, const float* const* up_bias, void* out, int N, int H, int W, int C,
                                       int relu, int tile_a, int tile_b, int max_workgroups) {
-    if (!base || !out || N < 1 || H < 1 || W < 1 || (C != 48 && C != 96 && C != 192) || n_plain < 0 || n_plain > 2 || n_up < 1 || n_up > 3) return PAM_E_ARG;
-    if ((size_t)N * H * W >= (1ull << 31)) return PAM_E_ARG;
-    FSArgs a;
-    a.base = (const uint16_t*)base; a.out = (uint16_t*)out; a.nplain = n_plain;
-    for (int t = 0; t < 2; ++t) {
-        a.plain[t] = t < n_plain ? (const uint16_t*)plain[t] : nullptr;
-        a.plain_cs[t] = (t < n_plain && plain_cstrides && plain_cstrides[t] > 0) ? plain_cstrides[t] : C;
-        if (t < n_plain && (!a.plain[t] || a.plain_cs[t] < C || a.plain_cs[t] % 8 != 0)) return PAM_E_ARG;
+    if (!base || !out || (n_up > 0 && (!up_src || !up_shifts || !up_channels || !up_wimg))) return PAM_E_ARG;
+    for (int t = 0; t < n_plain && t < 2; ++t) if (!plain || !plain[t]) return PAM_E_ARG;
+    for (int s = 0; s < n_up && s < 3; ++s) if (!up_src[s] || !up_wimg[s]) return PAM_E_ARG;
+    const FuseQuery q = fuse_query(N, H, W, C, n_plain, plain_cstrides, n_up, up_shifts, up_channels, tile_a, tile_b, max_workgroups, pam_cu_count());
+    const FusePlan p = fuse_plan(q);
+    if (p.rc != PAM_OK) return p.rc;
+    if (p.kernel == 1) {
+        FSArgs a;
+        fuse_fill(a, q, base, plain, up_src, up_wimg, up_bias, out, relu);
+        a.ua_log = p.ua_log; a.ub_log = p.ub_log; a.units_y = p.units_y; a.units_x = p.units_x;
+        return dispatch_fs(std::make_integer_sequence<int, FUSE_NCOMBO>{}, p.combo, (hipStream_t)stream, a, p.grid, p.L);
     }
-    int prev = 0, key = 0, ksteps = 0;
-    for (int s = 0; s < 3; ++s) {
-        const bool on = s < n_up;
-        a.src[s] = on ? (const uint16_t*)up_src[s] : nullptr; a.wimg[s] = on ? (const char*)up_wimg[s] : nullptr;
-        a.ubias[s] = (on && up_bias) ? up_bias[s] : nullptr;
-        if (!on) continue;
-        const int sh = up_shifts[s], cs = up_channels[s];
-        // sources in ascending shift (= branch) order; the map must be a whole number of source pixels (PyTorch's up-sampling needs that too)
-        if (!a.src[s] || !a.wimg[s] || sh <= prev || sh > 5 || cs < 32 || cs % 32 != 0) return PAM_E_ARG;
-        if (H % (1 << sh) != 0 || W % (1 << sh) != 0) return PAM_E_ARG;
-        // the k loops are unrolled per (C, source channels): a source of shift s has C << s channels, as in every HRNet
-        if (cs != C << sh) return PAM_E_ARG;
-        prev = sh; key = key * 8 + sh; ksteps += cs / 32;
+    FLArgs a;
+    fuse_fill(a, q, base, plain, up_src, up_wimg, up_bias, out, relu);
+    a.nup = q.n_up; a.smax = q.shift[q.n_up - 1];
+    for (int s = 0; s < 3; ++s) {                // (the entries behind n_up are 0 in the query and in the plan)
+        a.shift[s] = q.shift[s]; a.src_c[s] = q.src_c[s];
+        a.w_off[s] = p.w_off[s]; a.w_bytes[s] = p.w_bytes[s]; a.src_off[s] = p.src_off[s]; a.term_off[s] = p.term_off[s];
     }
-    const int smax = prev;
-    a.N = N; a.H = H; a.W = W; a.relu = relu ? 1 : 0;
-    // the unit's rectangle of 16 anchor pixels at level L: the shape that covers the anchor map with the fewest units (ties: the squarest)
-    auto plan = [&](int L) {
-        const int HA = H >> L, WA = W >> L;
-        const int shapes[5][2] = {{2, 2}, {1, 3}, {3, 1}, {0, 4}, {4, 0}};
-        long long best = -1;
-        for (int k = 0; k < 5; ++k) {
-            const int uy = (HA + (1 << shapes[k][0]) - 1) >> shapes[k][0], ux = (WA + (1 << shapes[k][1]) - 1) >> shapes[k][1];
-            if (best < 0 || (long long)uy * ux < best) { best = (long long)uy * ux; a.ua_log = shapes[k][0]; a.ub_log = shapes[k][1]; a.units_y = uy; a.units_x = ux; }
-        }
-        return best;
-    };
-    // Which kernel (stand-alone times at 2 / 20 / 40 crops): the persistent LDS-weights form stays where it was not
-    // beaten.  C = 192 (12-wave workgroups, one per CU at a time): 18 units 8.2 us against its 7.7, 180 units 8.9 against 11.9, 360 units
-    // 16.9 against 16.8 -> register weights only for more than 64 units and no more than one per CU.  C = 96 under two sources: 540 units
-    // (level 1) 13.3 us against 14.3, 1 080 units 25.0 against 20.2 -> register weights up to 768 units.  The thresholds lie between the
-    // measured points; a caller that names a level (tile_a > 0) gets the register-weights kernel at any size.
-    if (tile_a <= 0) {
-        const long long u1 = (long long)N * plan(1);
-        if ((C == 192 && (u1 <= 64 || u1 > pam_cu_count())) || (C == 96 && n_up == 2 && u1 > 768))
-            return fuse_sum_lds(stream, base, n_plain, plain, plain_cstrides, n_up, up_src, up_shifts, up_channels, up_wimg, up_bias, out, N, H, W, C,
-                                relu, 0, 0, max_workgroups);
-    }
-    // the anchor level unless the caller names it: level 2 reads a wave's weights and the coarse sources' pixels a quarter as often, which
-    // pays from 18 k-steps of weights on (72 VGPRs) and only while there are units for half the CUs (level 1 below that: 4 times the
-    // workgroups)
-    int L = tile_a > 0 ? tile_a : ((smax >= 2 && ksteps >= 18 && (long long)N * plan(2) >= 128) ? 2 : 1);
-    L = L > smax ? smax : L; L = L > 2 ? 2 : L;
-    const long long best = plan(L);
-    const long long nu = (long long)N * best;
-    if (nu >= (1ll << 31)) return PAM_E_ARG;
-    const unsigned grid = (unsigned)nu;
-    hipStream_t st = (hipStream_t)stream;
-    switch (C * 1000 + key) {                    // key: the shifts as octal digits
-        case 48 * 1000 + 01: return dispatch_fs<48, 1, 1, 0, 0>(st, a, grid, L);
-        case 48 * 1000 + 012: return dispatch_fs<48, 2, 1, 2, 0>(st, a, grid, L);
-        case 48 * 1000 + 0123: return dispatch_fs<48, 3, 1, 2, 3>(st, a, grid, L);
-        case 96 * 1000 + 01: return dispatch_fs<96, 1, 1, 0, 0>(st, a, grid, L);
-        case 96 * 1000 + 012: return dispatch_fs<96, 2, 1, 2, 0>(st, a, grid, L);
-        case 96 * 1000 + 02: return dispatch_fs<96, 1, 2, 0, 0>(st, a, grid, L);
-        case 192 * 1000 + 01: return dispatch_fs<192, 1, 1, 0, 0>(st, a, grid, L);
-        default: return PAM_E_ARG;               // a combination no network here uses: not instantiated
+    a.bias_off = p.bias_off; a.src_bytes = p.src_bytes; a.src_base = p.src_base;
+    a.TA = p.TA; a.TB = p.TB; a.OTH = p.TA << a.smax; a.OTW = p.TB << a.smax;
+    a.tiles_y = p.tiles_y; a.tiles_x = p.tiles_x; a.ntiles = p.ntiles;
+    a.inv_otw = 1.0f / (float)a.OTW;
+    switch (q.C) {                               // fuse_lds_rows_are_96_192 (pam_fuse_plan.hpp): no other C is planned for this kernel
+        case 96: return launch_fl<96>((hipStream_t)stream, a, (size_t)p.lds_bytes, (int)p.grid);
+        case 192: return launch_fl<192>((hipStream_t)stream, a, (size_t)p.lds_bytes, (int)p.grid);
+        default: return PAM_E_ARG;
     }
 }

@@ -36,6 +36,24 @@ __device__ __forceinline__ uint32_t relu_bf16x2(uint32_t v) {     // bf16 is sig
     return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, v), (s16x2){0, 0}));
 }
 
+// The fuse-layer sum of 8 channels, the one statement of what "bit-identical" means for k_upsample_add, k_fuse_sum and k_fuse_sum_lds:
+// eight fp32 sums start from the base, every term is added in the caller's order (plain terms, then up terms in ascending shift), then
+// the optional ReLU and ONE bf16 rounding.  Which loads are in flight before which add stays each kernel's own business.  k_upsample_add
+// and k_fuse_sum call these; k_fuse_sum_lds spells the same three steps out (with the calls it needs 34 more VGPRs).
+// sum8_finish writes through a reference: returned by value, all 33 k_fuse_sum instantiations allocate their registers otherwise.
+__device__ __forceinline__ void sum8_start(float (&v)[8], bf16x8 base) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = bf16_to_f32((uint16_t)base[e]);
+}
+__device__ __forceinline__ void sum8_add(float (&v)[8], bf16x8 term) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] += bf16_to_f32((uint16_t)term[e]);
+}
+__device__ __forceinline__ void sum8_finish(const float (&v)[8], int relu, bf16x8& o) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = (short)f32_to_bf16(relu ? fmaxf(v[e], 0.0f) : v[e]);
+}
+
 __device__ __forceinline__ int fdiv_small(int x, float inv) { return (int)(((float)x + 0.5f) * inv); }   // exact for x < 2^16
 
 // Work item of workgroup v among n items.  Workgroups v, v + 8, ... share an XCD and its L2, so every XCD gets a contiguous run of

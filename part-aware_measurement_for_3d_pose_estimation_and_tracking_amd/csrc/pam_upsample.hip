@@ -24,17 +24,12 @@ __global__ __launch_bounds__(256) void k_upsample_add(UpArgs a) {
             }
         }
         float v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = bf16_to_f32((uint16_t)b[k]);
+        sum8_start(v, b);
 #pragma unroll
         for (int t = 0; t < 3; ++t)                     // same summation order as before: base, then terms in order
-            if (t < a.nterms) {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) v[k] += bf16_to_f32((uint16_t)q[t][k]);
-            }
+            if (t < a.nterms) sum8_add(v, q[t]);
         bf16x8 o;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (short)f32_to_bf16(a.relu ? fmaxf(v[k], 0.0f) : v[k]);
+        sum8_finish(v, a.relu, o);
         *(bf16x8*)(a.out + (size_t)pix * a.C + c8 * 8) = o;
     }
 }
