@@ -466,7 +466,10 @@ int pam_clock_probe(void* stream, unsigned long long* dev_out2, int microseconds
 /* ---- HRNet conv stack (a1) as hand-written MFMA kernels -------------------------------------------------------
  * pam_conv2d_nhwc_bf16: NHWC bf16 convolution (KH,KW in {1,3}; stride 1/2; Cin % 8 == 0; Cout % 48 == 0, % 64 == 0 or % 32 == 0) as an
  * implicit GEMM on v_mfma_f32_16x16x32_bf16 with fused epilogue out = act(conv + bias [+ residual]); `relu` is the activation
- * code: 0 linear, 1 ReLU, 2 leaky ReLU (slope 0.1, Darknet); + 4 = add the residual AFTER the activation (Darknet shortcut).  w_packed is
+ * code: 0 linear, 1 ReLU, 2 leaky ReLU (slope 0.1, Darknet), 3 mish (YOLOv4: in float32 on conv + bias, e = expf(x), n = e*e + 2e,
+ * x <= -0.6f ? x * (n / (n + 2)) : x - 2 * (x / (n + 2)); carried by the Darknet-only instantiations: the G = 1 forms of k_conv_igemm /
+ * k_conv3x3s and the mish forms of k_conv_stem (stride 1) / k_conv_gs below; never on k_conv3x3);
+ * + 4 = add the residual AFTER the activation (Darknet shortcut).  w_packed is
  * [Cout][Kpad] bf16, k = (ky, kx, cin) flattened, zero-padded to Kpad = roundup(KH*KW*Cin, 64); bias float32 or NULL;
  * residual NHWC bf16 of the output shape or NULL.  tile_cfg: -1 = choose automatically (w_img in the layout pam_conv3x3_layout() announces
  * at call time), -3 / -4 = the same with the layout of w_img STATED by the caller (-3 streamed: k_conv3x3s or PAM_E_ARG; -4 classic),
@@ -523,8 +526,8 @@ int pam_conv_last_kernel(void);
  *   PAM_CONV_KERNEL_IGEMM  G*1000000 + BM*1000 + BN       G = 1: general-activation epilogue (codes > 1); BM x BN = pixel x channel tile
  *   PAM_CONV_KERNEL_3X3    Cin*10 + NTW                   output-channel slab 16*NTW
  *   PAM_CONV_KERNEL_3X3S   G*100000 + Cin*100 + NTW*10 + MT   G = 1: general-activation form (tile_cfg -7); slab 16*NTW; MT M tiles per wave
- *   PAM_CONV_KERNEL_GS     NBUF*1000000 + BM*1000 + 16*NTW    chunk ring depth, pixel tile, output-channel slab
- *   PAM_CONV_KERNEL_STEM   S*100 + Cout                   stride 1 / 2, 32 or 64 output channels
+ *   PAM_CONV_KERNEL_GS     NBUF*1000000 + BM*1000 + M*500 + 16*NTW    chunk ring depth, pixel tile, M = 1: the mish form (k_conv_gs_mish), output-channel slab
+ *   PAM_CONV_KERNEL_STEM   M*1000 + S*100 + Cout          M = 1: the mish form (k_conv_stem_mish, stride 1); stride 1 / 2, 32 or 64 output channels
  * Kernel and form are recorded together, by the launcher, from the launched kernel's own template parameters. */
 int pam_conv_last_form(void);
 /* Which kernel and form (the two codes above) pam_conv2d_nhwc_bf16_ex would launch for these integer arguments and pointers (has_* = 1
@@ -775,6 +778,36 @@ int pam_maxpool_nhwc_bf16(void* stream, const void* in, void* out, int N, int H,
 #define PAM_SPP_MAX_HW 32
 int pam_spp_concat_nhwc_bf16(void* stream, const void* in, void* out, int N, int H, int W, int C, int s1, int s2, int s3);
 int pam_spp_concat_slab_nhwc_bf16(void* stream, const void* in, void* out, int N, int H, int W, int C, int s1, int s2, int s3, int slab);
+
+/* ---- YOLOv4 / YOLOv4-tiny (csrc/pam_route.hip, csrc/pam_detect.hip; the public Darknet definitions of Bochkovskiy et al. 2020, parity
+ * unpinned like YOLOv3's).
+ * pam_route_concat_nhwc_bf16 (k_route): Darknet's general `route`, one launch.  out: NHWC bf16 (N, H, W, C_out).  Source k (n_src of
+ * them, 1 .. PAM_ROUTE_MAX_SRC; src and the four tables are host arrays) is an NHWC bf16 map whose pixels are src_cstride[k] channels
+ * apart; its slice is the src_count[k] channels from channel src_offset[k] (a `groups=` / `group_id=` route, or the real channels of a
+ * channel-padded layer).  src_up2[k] != 0: the source is the (N, H/2, W/2) map, read at (y/2, x/2) (`upsample stride=2` in front of the
+ * route); else it is (N, H, W).  out[n, y, x, :] = the slices side by side in source order, compact, then +0 (all bits zero) up to C_out.
+ * A pure copy: every output bit is a source bit or zero.
+ * PAM_E_ARG, before anything is launched, for: a NULL pointer (table, source or out) or one that is not 16-byte aligned; n_src outside
+ * 1 .. PAM_ROUTE_MAX_SRC; N, H, W or C_out <= 0; C_out % 8 != 0; a stride, offset or count that is not a multiple of 8, a count <= 0, a
+ * negative offset, or offset + count > stride (the slice leaves its source); odd H or W with an x2 source; C_out smaller than the sum of
+ * the counts; N * H * W * C_out / 8 >= 2^31 (the kernel's piece index is 32-bit).  PAM_E_HIP on a launch error. */
+#define PAM_ROUTE_MAX_SRC 4
+int pam_route_concat_nhwc_bf16(void* stream, int n_src, const void* const* src, const int32_t* src_cstride, const int32_t* src_offset,
+                               const int32_t* src_count, const int32_t* src_up2, void* out, int N, int H, int W, int C_out);
+/* pam_yolo_detect_heads / _ws with YOLOv4's `scale_x_y`: scale_xy (host memory) holds one s per head, and a box centre is
+ * (sigmoid(t) * s - 0.5f * (s - 1) + cell) / grid in float32, evaluated in that order.  Everything else -- candidate order (head in the
+ * order given, which need not be coarsest first; then cell row-major; then anchor), scores, NMS, outputs, workspace
+ * (pam_yolo_detect_heads_workspace_bytes) -- is pam_yolo_detect_heads'.  With every s = 1 the bytes are those of pam_yolo_detect_heads
+ * (v * 1.0f - 0.0f is exact), which is implemented as this call with a table of ones.  PAM_E_ARG additionally for a NULL table or an s
+ * that is NaN, infinite or < 1. */
+int pam_yolo_detect_heads_sxy(void* stream, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
+                              const int32_t* chan_stride, const float* anchors, const float* scale_xy, int net_w, int net_h, int num_classes,
+                              int class_id, float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det, float* dev_out,
+                              int32_t* dev_count);
+int pam_yolo_detect_heads_sxy_ws(void* stream, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
+                                 const int32_t* chan_stride, const float* anchors, const float* scale_xy, int net_w, int net_h,
+                                 int num_classes, int class_id, float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det,
+                                 float* dev_out, int32_t* dev_count, void* dev_workspace, long long workspace_bytes);
 
 /* ---- baseline JPEG frames decoded on the device behind a host entropy pass (csrc/pam_jpeg_entropy.hpp, csrc/pam_jpeg.hip; the
  * reference decodes with one cv2.imread per camera per frame on the main thread, dataset.py:36-45).  The host does the serial half --

@@ -180,6 +180,9 @@ _SIGS = {
     'pam_yolo_detect_heads': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_float, C.c_float, _I, _I, _I, _P, _P]),
     'pam_yolo_detect_heads_ws': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_float, C.c_float, _I, _I, _I, _P, _P, _P, C.c_longlong]),
     'pam_yolo_detect_heads_workspace_bytes': (C.c_longlong, [_I, _I, _P, _P]),
+    'pam_yolo_detect_heads_sxy': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_float, C.c_float, _I, _I, _I, _P, _P]),
+    'pam_yolo_detect_heads_sxy_ws': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, C.c_float, C.c_float, _I, _I, _I, _P, _P, _P, C.c_longlong]),
+    'pam_route_concat_nhwc_bf16': (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I]),
     'pam_maxpool_nhwc_bf16': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I]),
     'pam_spp_concat_nhwc_bf16': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
     'pam_spp_concat_slab_nhwc_bf16': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I]),

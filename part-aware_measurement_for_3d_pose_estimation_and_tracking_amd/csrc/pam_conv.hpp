@@ -60,6 +60,19 @@ __device__ __forceinline__ float epi_act(float v, float r, int act) {
     return (act & 4) ? epi_act1(v, act & 3) + r : epi_act1(v + r, act & 3);
 }
 
+// Code 3 of act & 3: mish, x * tanh(softplus(x)), in the division form of Darknet's GPU code (no log, no tanh; finite for every finite x:
+// e = inf gives x, e = 0 gives -0; within 3 float32 ulp of the float64 value).  Only the Darknet-only instantiations carry it -- the
+// general-activation (GEN) forms of k_conv_igemm / k_conv3x3s and the mish forms of k_conv_stem / k_conv_gs --, through epi_act_gen;
+// epi_act1 / epi_act above, which the pose networks' instantiations compile, never see code 3.
+__device__ __forceinline__ float epi_mish(float x) {
+    const float e = expf(x), n = e * e + 2.0f * e;
+    return x <= -0.6f ? x * (n / (n + 2.0f)) : x - 2.0f * (x / (n + 2.0f));
+}
+__device__ __forceinline__ float epi_act1_gen(float v, int kind) { return kind == 3 ? epi_mish(v) : epi_act1(v, kind); }
+__device__ __forceinline__ float epi_act_gen(float v, float r, int act) {
+    return (act & 4) ? epi_act1_gen(v, act & 3) + r : epi_act1_gen(v + r, act & 3);
+}
+
 // the element-wise pack (two converts + a permute); the shared pack_bf16x2 changes these kernels' code and is left to a measured change
 __device__ __forceinline__ uint32_t pack_bf16x2_ew(float lo, float hi) {
     typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;

@@ -184,12 +184,12 @@ __global__ __launch_bounds__(512, 1) void k_conv3x3s(C3Args a) {
             uint32_t ov[2 * NTW];
 #pragma unroll
             for (int j = 0; j < NTW; ++j) {
-                if constexpr (GEN) {                     // epi_act's arithmetic: act & 3 = 0 linear / 1 ReLU / 2 leaky; act & 4: the residual is added after it
+                if constexpr (GEN) {                     // epi_act's arithmetic: act & 3 = 0 linear / 1 ReLU / 2 leaky / 3 mish; act & 4: the residual is added after it
                     const uint32_t r01 = a.res ? gres[GEN ? i : 0][2 * j] : 0u, r23 = a.res ? gres[GEN ? i : 0][2 * j + 1] : 0u;
-                    acc[i][j][0] = epi_act(acc[i][j][0], __builtin_bit_cast(float, r01 << 16), a.relu);
-                    acc[i][j][1] = epi_act(acc[i][j][1], __builtin_bit_cast(float, r01 & 0xffff0000u), a.relu);
-                    acc[i][j][2] = epi_act(acc[i][j][2], __builtin_bit_cast(float, r23 << 16), a.relu);
-                    acc[i][j][3] = epi_act(acc[i][j][3], __builtin_bit_cast(float, r23 & 0xffff0000u), a.relu);
+                    acc[i][j][0] = epi_act_gen(acc[i][j][0], __builtin_bit_cast(float, r01 << 16), a.relu);
+                    acc[i][j][1] = epi_act_gen(acc[i][j][1], __builtin_bit_cast(float, r01 & 0xffff0000u), a.relu);
+                    acc[i][j][2] = epi_act_gen(acc[i][j][2], __builtin_bit_cast(float, r23 << 16), a.relu);
+                    acc[i][j][3] = epi_act_gen(acc[i][j][3], __builtin_bit_cast(float, r23 & 0xffff0000u), a.relu);
                 }
                 ov[2 * j] = pack_bf16x2_ew(acc[i][j][0], acc[i][j][1]); ov[2 * j + 1] = pack_bf16x2_ew(acc[i][j][2], acc[i][j][3]);
                 if (!GEN && a.relu) {

@@ -171,7 +171,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& a, const int bx,
                 const bool act_on = cw0 + g * 4 * NTW + j * 4 >= a.relu_from;   // merged fuse-layer convs: only the upper channels
                 if constexpr (GEN) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = epi_act(v[r], rr[r], act_on ? a.relu : (a.relu & 4));
+                    for (int r = 0; r < 4; ++r) v[r] = epi_act_gen(v[r], rr[r], act_on ? a.relu : (a.relu & 4));
                     ov[2 * j] = pack_bf16x2_ew(v[0], v[1]); ov[2 * j + 1] = pack_bf16x2_ew(v[2], v[3]);
                 } else {                                // HRNet's codes 0 / 1; ReLU as a packed int16 max on the bf16 pairs
 #pragma unroll

@@ -30,6 +30,7 @@ struct ConvPlan {
     int BM, NBUF;        // k_conv_gs: pixel tile, chunk ring depth
     bool gen;            // the general-activation (Darknet codes) instantiation
     bool res;            // k_conv_gs: the instantiation that carries residual rows
+    bool mish;           // k_conv_gs / k_conv_stem: the instantiation whose activation is mish (code 3)
     int dbg;             // diagnostic build: k_conv3x3's knock-out / stamp bits (tile_cfg 100 .. 999)
     bool stamped;        // diagnostic build: k_conv3x3s records stamps whenever a buffer is set (pam_conv_debug_stamps)
 };
@@ -195,11 +196,11 @@ inline int gs_one_round_tile(int M, int nslab) {
     if (((M + 127) / 128) * nslab <= PLAN_CUS) return 128;
     return 256;
 }
-inline ConvPlan plan_gs(int ntw, int BM, int NBUF, bool res) {
+inline ConvPlan plan_gs(int ntw, int BM, int NBUF, bool res, bool mish = false) {
     if (ntw >= 6 && res) return plan_refused();          // the wide slab has no registers left for the residual rows
     ConvPlan p = {};
-    p.kernel = PAM_CONV_KERNEL_GS; p.form = NBUF * 1000000 + BM * 1000 + 16 * ntw;
-    p.ntw = ntw; p.BM = BM; p.NBUF = NBUF; p.res = res;
+    p.kernel = PAM_CONV_KERNEL_GS; p.form = NBUF * 1000000 + BM * 1000 + (mish ? 500 : 0) + 16 * ntw;
+    p.ntw = ntw; p.BM = BM; p.NBUF = NBUF; p.res = res; p.mish = mish;
     return p;
 }
 
@@ -290,8 +291,10 @@ inline ConvPlan conv_plan(const ConvQuery& query) {
 
     // k_conv_stem: w_img = the pre-permuted A fragments (see pam.h)
     if (stem && (Cout == 64 || Cout == 32) && (q.stride == 1 || q.stride == 2)) {
+        const bool mish = (relu & 3) == 3;               // YOLOv4's layer 0: the stride-1 forms have a mish instantiation
+        if (mish && q.stride != 1) return plan_refused();
         ConvPlan p = {};
-        p.kernel = PAM_CONV_KERNEL_STEM; p.form = q.stride * 100 + Cout; p.ntw = Cout / 16;
+        p.kernel = PAM_CONV_KERNEL_STEM; p.form = (mish ? 1000 : 0) + q.stride * 100 + Cout; p.ntw = Cout / 16; p.mish = mish;
         return p;
     }
 
@@ -319,7 +322,7 @@ inline ConvPlan conv_plan(const ConvQuery& query) {
         // at 608) or than the patch in LDS (e.g. the detector's 208-wide layers) does not fit: the generic kernel below takes it
         const int npatch = (th + 2) * (q.W + 2), pmax = (cfg == 44 || cfg == 54) ? 416 : (cfg == 43 ? 352 : 288);
         const bool fits = th * (q.W + 2) <= 16 * (cfg / 10) * (cfg % 10) && npatch <= pmax && c3_lds_bytes(Cin, ntw, npatch) <= 150 * 1024 &&
-                          Cout % (16 * ntw) == 0 && (relu <= 1 || c3_general_act(Cin));
+                          Cout % (16 * ntw) == 0 && (relu <= 1 || (c3_general_act(Cin) && (relu & 3) != 3));   // no mish (code 3) here: PoseResNet launches these widths' instantiations too
         if (fits && c3_instantiated(Cin, ntw)) {
             if (!c3_wave_shape(Cin, cfg)) return plan_refused();
             ConvPlan p = {};
@@ -336,11 +339,12 @@ inline ConvPlan conv_plan(const ConvQuery& query) {
 
     // streamed implicit GEMM (k_conv_gs): codes 0 / 1, taps in a 32-bit mask, whole 16-byte pieces per tap (Cin % 8 == 0)
     // (round 5: code 2 -- leaky, no residual -- too: the detector's 1x1 and strided layers, which the classic implicit GEMM ran at 20 us each)
-    const bool leaky_gs = relu == 2 && !q.residual && classic && q.relu_from == 0;
+    // (code 3 -- mish, no residual -- on the 64-channel-slab forms' mish instantiations: YOLOv4's backbone)
+    const bool leaky_gs = (relu == 2 || (relu == 3 && Cout % 48 != 0)) && !q.residual && classic && q.relu_from == 0;
     const bool gs_ok = (relu <= 1 || leaky_gs) && KH * KW <= 9 && Cin % 8 == 0 && (size_t)q.N * q.H * q.W * q.in_cstride * 2 < (1u << 31);
     const int slab = Cout % 48 == 0 ? 3 : 4;             // 48-channel slabs where the width allows, else 64 (Darknet's widths)
     if (leaky_gs && gs_ok && tile_cfg == -1 && conv_gs_auto(Cout, M, Kpad))
-        return plan_gs(slab, slab == 4 ? gs_one_round_tile(M, Cout / 64) : 256, 3, false);
+        return plan_gs(slab, slab == 4 ? gs_one_round_tile(M, Cout / 64) : 256, 3, false, relu == 3);
     if (tile_cfg >= 8 && tile_cfg <= 12 && !gs_ok) return plan_refused();
     if (tile_cfg >= 10 && tile_cfg <= 12) {
         // 12: 64-pixel tiles: the smallest images (12 x 9) as a few hundred short workgroups

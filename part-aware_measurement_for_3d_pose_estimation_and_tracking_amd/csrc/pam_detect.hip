@@ -2,7 +2,8 @@
 // ivclabpose.PersonDetect (/root/reference/src/ivclabpose.py:116-120,183-204; the backend itself is not in the reference
 // tree, so these follow the public Darknet YOLOv3 definition -- parity unpinned).  The Darknet-53 convolutions run on
 // the kernels behind pam_conv.hip (pam_conv_*.hip); the kernels here are the HBM-bound streaming pieces: frame resize, route(upsample, skip), YOLOv3-tiny's
-// max-pool, YOLOv3-SPP's pooling block and the box decode + greedy NMS over one to three scales.
+// max-pool, YOLOv3-SPP's pooling block and the box decode + greedy NMS over one to three scales (with YOLOv4's scale_x_y per head; the
+// general route of YOLOv4 / YOLOv4-tiny is csrc/pam_route.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/pam.h"
@@ -276,6 +277,7 @@ struct YoloArgs {
     const uint16_t* head[3];
     int gh[3], gw[3], cs[3];
     float anchors[18];          // [head][anchor][w, h] in network-input pixels
+    float sxy[3], sxy_off[3];   // [head] scale_x_y s and 0.5 (s - 1): the centre is sigmoid(t) * s - 0.5 (s - 1) + cell (s = 1: YOLOv3's, bit for bit)
     int n_heads;                // 1 .. 3: heads h >= n_heads hold no candidates (their pointer is null and never read)
     int net_w, net_h, nc, cls;
     float score_thresh, nms_thresh;
@@ -385,8 +387,9 @@ __global__ __launch_bounds__(DET_T) void k_yolo_detect(YoloArgs a) {
                     const int gw = h == 0 ? a.gw[0] : (h == 1 ? a.gw[1] : a.gw[2]), gh = h == 0 ? a.gh[0] : (h == 1 ? a.gh[1] : a.gh[2]);
                     const int gy = cell / gw, gx = cell - gy * gw;
                     const uint16_t* p = ptr[k];
-                    const float bx = (sigmoidf_(bf16_to_f32(p[0])) + (float)gx) / (float)gw;
-                    const float by = (sigmoidf_(bf16_to_f32(p[1])) + (float)gy) / (float)gh;
+                    const float sx = h == 0 ? a.sxy[0] : (h == 1 ? a.sxy[1] : a.sxy[2]), so = h == 0 ? a.sxy_off[0] : (h == 1 ? a.sxy_off[1] : a.sxy_off[2]);
+                    const float bx = (sigmoidf_(bf16_to_f32(p[0])) * sx - so + (float)gx) / (float)gw;
+                    const float by = (sigmoidf_(bf16_to_f32(p[1])) * sx - so + (float)gy) / (float)gh;
                     const float bw = expf(bf16_to_f32(p[2])) * a.anchors[(h * 3 + an) * 2 + 0] / (float)a.net_w;
                     const float bh = expf(bf16_to_f32(p[3])) * a.anchors[(h * 3 + an) * 2 + 1] / (float)a.net_h;
                     L.x1[off] = (bx - 0.5f * bw) * (float)a.frame_w; L.x2[off] = (bx + 0.5f * bw) * (float)a.frame_w;
@@ -473,8 +476,9 @@ __global__ __launch_bounds__(DET_TS) void k_yolo_detect_split(YoloArgs a, int* _
                     const int gw = h == 0 ? a.gw[0] : (h == 1 ? a.gw[1] : a.gw[2]), gh = h == 0 ? a.gh[0] : (h == 1 ? a.gh[1] : a.gh[2]);
                     const int gy = cell / gw, gx = cell - gy * gw;
                     const uint16_t* p = ptr[k];
-                    const float bx = (sigmoidf_(bf16_to_f32(p[0])) + (float)gx) / (float)gw;
-                    const float by = (sigmoidf_(bf16_to_f32(p[1])) + (float)gy) / (float)gh;
+                    const float sx = h == 0 ? a.sxy[0] : (h == 1 ? a.sxy[1] : a.sxy[2]), so = h == 0 ? a.sxy_off[0] : (h == 1 ? a.sxy_off[1] : a.sxy_off[2]);
+                    const float bx = (sigmoidf_(bf16_to_f32(p[0])) * sx - so + (float)gx) / (float)gw;
+                    const float by = (sigmoidf_(bf16_to_f32(p[1])) * sx - so + (float)gy) / (float)gh;
                     const float bw = expf(bf16_to_f32(p[2])) * a.anchors[(h * 3 + an) * 2 + 0] / (float)a.net_w;
                     const float bh = expf(bf16_to_f32(p[3])) * a.anchors[(h * 3 + an) * 2 + 1] / (float)a.net_h;
                     seg.x1[off] = (bx - 0.5f * bw) * (float)a.frame_w; seg.x2[off] = (bx + 0.5f * bw) * (float)a.frame_w;
@@ -520,15 +524,17 @@ __global__ __launch_bounds__(DET_TS) void k_yolo_detect_split(YoloArgs a, int* _
 }
 
 static int det_fill_args(YoloArgs& a, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w, const int32_t* chan_stride,
-                         const float* anchors, int net_w, int net_h, int num_classes, int class_id, float score_thresh, float nms_thresh,
+                         const float* anchors, const float* scale_xy, int net_w, int net_h, int num_classes, int class_id, float score_thresh, float nms_thresh,
                          int frame_w, int frame_h, int max_det, float* dev_out, int32_t* dev_count) {
-    if (n_img < 0 || !heads || !grid_h || !grid_w || !chan_stride || !anchors || !dev_out || !dev_count || num_classes <= 0 ||
+    if (n_img < 0 || !heads || !grid_h || !grid_w || !chan_stride || !anchors || !scale_xy || !dev_out || !dev_count || num_classes <= 0 ||
         class_id < 0 || class_id >= num_classes || max_det <= 0 || net_w <= 0 || net_h <= 0 || n_heads < 1 || n_heads > 3)
         return PAM_E_ARG;
     long long total = 0;
     for (int h = 0; h < 3; ++h) {
-        a.head[h] = nullptr; a.gh[h] = 0; a.gw[h] = 0; a.cs[h] = 0;
+        a.head[h] = nullptr; a.gh[h] = 0; a.gw[h] = 0; a.cs[h] = 0; a.sxy[h] = 1.0f; a.sxy_off[h] = 0.0f;
         if (h >= n_heads) continue;
+        if (!(scale_xy[h] >= 1.0f) || !(scale_xy[h] <= 3.4e38f)) return PAM_E_ARG;      // NaN, infinite or < 1
+        a.sxy[h] = scale_xy[h]; a.sxy_off[h] = 0.5f * (scale_xy[h] - 1.0f);
         if (!heads[h] || grid_h[h] <= 0 || grid_w[h] <= 0 || chan_stride[h] < 3 * (5 + num_classes)) return PAM_E_ARG;
         a.head[h] = (const uint16_t*)heads[h]; a.gh[h] = grid_h[h]; a.gw[h] = grid_w[h]; a.cs[h] = chan_stride[h];
         total += (long long)grid_h[h] * grid_w[h] * 3;
@@ -551,12 +557,12 @@ extern "C" long long pam_yolo_detect_heads_workspace_bytes(int n_img, int n_head
     const int runs = det_runs(n_heads, grid_h, grid_w);
     return (long long)(det_ws_head_bytes(n_img, runs) + (size_t)n_img * runs * sizeof(DetSeg));
 }
-extern "C" int pam_yolo_detect_heads_ws(void* stream, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
-                                        const int32_t* chan_stride, const float* anchors, int net_w, int net_h, int num_classes,
+extern "C" int pam_yolo_detect_heads_sxy_ws(void* stream, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
+                                        const int32_t* chan_stride, const float* anchors, const float* scale_xy, int net_w, int net_h, int num_classes,
                                         int class_id, float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det,
                                         float* dev_out, int32_t* dev_count, void* dev_workspace, long long workspace_bytes) {
     YoloArgs a;
-    const int rc = det_fill_args(a, n_img, n_heads, heads, grid_h, grid_w, chan_stride, anchors, net_w, net_h, num_classes, class_id, score_thresh,
+    const int rc = det_fill_args(a, n_img, n_heads, heads, grid_h, grid_w, chan_stride, anchors, scale_xy, net_w, net_h, num_classes, class_id, score_thresh,
                                  nms_thresh, frame_w, frame_h, max_det, dev_out, dev_count);
     if (rc != PAM_OK) return rc;
     if (n_img == 0) return PAM_OK;
@@ -569,17 +575,34 @@ extern "C" int pam_yolo_detect_heads_ws(void* stream, int n_img, int n_heads, co
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
 }
 
-extern "C" int pam_yolo_detect_heads(void* stream, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
-                                     const int32_t* chan_stride, const float* anchors, int net_w, int net_h, int num_classes,
+extern "C" int pam_yolo_detect_heads_sxy(void* stream, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
+                                     const int32_t* chan_stride, const float* anchors, const float* scale_xy, int net_w, int net_h, int num_classes,
                                      int class_id, float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det,
                                      float* dev_out, int32_t* dev_count) {
     YoloArgs a;
-    const int rc = det_fill_args(a, n_img, n_heads, heads, grid_h, grid_w, chan_stride, anchors, net_w, net_h, num_classes, class_id, score_thresh,
+    const int rc = det_fill_args(a, n_img, n_heads, heads, grid_h, grid_w, chan_stride, anchors, scale_xy, net_w, net_h, num_classes, class_id, score_thresh,
                                  nms_thresh, frame_w, frame_h, max_det, dev_out, dev_count);
     if (rc != PAM_OK) return rc;
     if (n_img == 0) return PAM_OK;
     hipLaunchKernelGGL(k_yolo_detect, dim3(n_img), dim3(DET_T), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+}
+
+// YOLOv3's decode: every scale_x_y = 1 (v * 1.0f - 0.0f is exact: the same bytes as before the table existed)
+static const float k_sxy_one[3] = {1.0f, 1.0f, 1.0f};
+extern "C" int pam_yolo_detect_heads_ws(void* stream, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
+                                        const int32_t* chan_stride, const float* anchors, int net_w, int net_h, int num_classes,
+                                        int class_id, float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det,
+                                        float* dev_out, int32_t* dev_count, void* dev_workspace, long long workspace_bytes) {
+    return pam_yolo_detect_heads_sxy_ws(stream, n_img, n_heads, heads, grid_h, grid_w, chan_stride, anchors, k_sxy_one, net_w, net_h, num_classes, class_id,
+                                        score_thresh, nms_thresh, frame_w, frame_h, max_det, dev_out, dev_count, dev_workspace, workspace_bytes);
+}
+extern "C" int pam_yolo_detect_heads(void* stream, int n_img, int n_heads, const void* const* heads, const int32_t* grid_h, const int32_t* grid_w,
+                                     const int32_t* chan_stride, const float* anchors, int net_w, int net_h, int num_classes,
+                                     int class_id, float score_thresh, float nms_thresh, int frame_w, int frame_h, int max_det,
+                                     float* dev_out, int32_t* dev_count) {
+    return pam_yolo_detect_heads_sxy(stream, n_img, n_heads, heads, grid_h, grid_w, chan_stride, anchors, k_sxy_one, net_w, net_h, num_classes, class_id,
+                                     score_thresh, nms_thresh, frame_w, frame_h, max_det, dev_out, dev_count);
 }
 
 // the three-head forms: the entry points above with n_heads = 3

@@ -141,7 +141,7 @@ class ConvEngine(object):
     gen_streamed = True         # Darknet 3x3 layers with Cin 128 / 256 / 512 on k_conv3x3s<.., GEN> (False: the classic k_conv3x3)
     tile_cfg = TileCfg.AUTO
     c96_slab = 0                # 96 -> 96 3x3 layers: 0 = k_conv3x3, 48 / 96 = the streamed kernel with slabs of that many output channels
-    ACT = {None: 0, False: 0, True: 1, 'linear': 0, 'relu': 1, 'leaky': 2}
+    ACT = {None: 0, False: 0, True: 1, 'linear': 0, 'relu': 1, 'leaky': 2, 'mish': 3}
 
     @staticmethod
     def _cached(op, key, build):
@@ -420,6 +420,27 @@ class ConvEngine(object):
             return y
         self._run(a, 'pam_upsample_concat_nhwc_bf16', lambda: self.lib.pam_upsample_concat_nhwc_bf16(
             self._cur(a), ptr(a), ptr(b), ptr(y), n, h, w, ca, cb), nbytes, 0)
+        return y
+
+    def route(self, srcs, c_out):
+        """Darknet's general [route], one launch (k_route): srcs = [(tensor, first channel, channels, nearest-x2 flag)], 1 .. 4 of them;
+        the slices side by side, then zeros up to c_out channels.  An x2 source is the half-size map."""
+        t0, _, _, up0 = srcs[0]
+        n, h, w = t0.shape[0], t0.shape[2] * (2 if up0 else 1), t0.shape[3] * (2 if up0 else 1)
+        y = self._new(n, c_out, h, w, t0.device)
+        nbytes = 2 * (n * h * w * sum(s[2] for s in srcs) + y.numel())
+        if self._tally(t0, nbytes, 0):
+            return y
+        k = len(srcs)
+        for t, off, cnt, up in srcs:
+            assert t.is_contiguous(memory_format=torch.channels_last) and tuple(t.shape[2:]) == ((h // 2, w // 2) if up else (h, w)), (t.shape, (h, w), up)
+        sp = (C.c_void_p * k)(*[ptr(s[0]) for s in srcs])
+        cs = (C.c_int32 * k)(*[s[0].shape[1] for s in srcs])
+        off = (C.c_int32 * k)(*[int(s[1]) for s in srcs]); cnt = (C.c_int32 * k)(*[int(s[2]) for s in srcs])
+        up = (C.c_int32 * k)(*[1 if s[3] else 0 for s in srcs])
+        self._run(t0, 'pam_route_concat_nhwc_bf16', lambda: self.lib.pam_route_concat_nhwc_bf16(
+            self._cur(t0), k, sp, cs, off, cnt, up, ptr(y), n, h, w, c_out), nbytes, 0, 'k_route', (n, h, w, c_out, k),
+            what=(' for %s -> %d channels', [tuple(s[0].shape) + tuple(s[1:]) for s in srcs], c_out))
         return y
 
     def maxpool(self, x, size, stride):

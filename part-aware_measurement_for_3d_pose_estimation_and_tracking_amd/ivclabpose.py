@@ -26,6 +26,9 @@ def _opt(block, key, default=None):
     return block.get(key, default) if isinstance(block, dict) else getattr(block, key, default)
 
 
+# DETECT_MODELS.<KEY>.NAME values that build a person detector: 'YOLOv3' (the reference's; yolov3.YOLOv3) and 'YOLOv4' (yolov4.YOLOv4)
+DETECTOR_NAMES = ('YOLOv3', 'YOLOv4')
+
 # The optional keys of a POSE_MODELS.HRPOSE block that set a decode option of HRNetPose (none of them in the reference's YAMLs):
 # (key, attribute, conversion, set when the key is absent).  Applied in this order: the property setters refuse combinations
 # (HRNetPose._decode_option), so which error a bad YAML gets depends on it.
@@ -163,15 +166,20 @@ class ivclabpose(object):
         self.frames_scheduled = 0
         if self.person_detector is None:
             print("Person Detector : Close.")
-        elif _cfg(self.person_detector, 'NAME') == 'YOLOv3':                        # ivclabpose.py:116-120
+        elif _cfg(self.person_detector, 'NAME') in DETECTOR_NAMES:                  # ivclabpose.py:116-120
             import os
-            from .yolov3 import YOLOv3
             d = self.person_detector
+            v4 = _cfg(d, 'NAME') == 'YOLOv4'        # not in the reference: yolov4.YOLOv4 (YOLOv4 / YOLOv4-tiny and the three v3 networks), same keys
+            if v4:
+                from .yolov4 import YOLOv4 as YOLOv3
+            else:
+                from .yolov3 import YOLOv3
             cfg, weight, names = _cfg(d, 'CFG'), _cfg(d, 'WEIGHT'), _cfg(d, 'CLASS_NAMES')
             # the reference's cfg / weight / names files are not distributed with it: a missing cfg or names file means
             # the standard YOLOv3-416 COCO layout (person = class 0), missing weights mean a seeded random network.
             # ARCH (optional key, not in the reference): 'yolov3' | 'yolov3-tiny' | 'yolov3-spp', the standard network built when the cfg file is missing
-            arch = _opt(d, 'ARCH') or 'yolov3'
+            # (NAME 'YOLOv4': also 'yolov4' | 'yolov4-tiny', default 'yolov4')
+            arch = _opt(d, 'ARCH') or ('yolov4' if v4 else 'yolov3')
             self.bbox_detector = YOLOv3(cfg if cfg and os.path.exists(cfg) else None,
                                         weight if weight and os.path.exists(weight) else None,
                                         names if names and os.path.exists(names) else None,
@@ -249,7 +257,7 @@ class ivclabpose(object):
 
     def PersonDetect(self, imglist, image_id):
         """ivclabpose.py:183-204: per image a list of person dicts, boxes clamped to the image, xywh."""
-        if self.person_detector is None or _cfg(self.person_detector, 'NAME') != 'YOLOv3':
+        if self.person_detector is None or _cfg(self.person_detector, 'NAME') not in DETECTOR_NAMES:
             return None
         return self._person_dicts(imglist, image_id, self.bbox_detector(imglist))
 
@@ -257,7 +265,7 @@ class ivclabpose(object):
         """Not in the reference: PersonDetect split in two so that a driver which already holds the NEXT frame's images (the loader decodes
         ahead) can run that frame's detector under the current frame's pose network -- issue here (a stream of its own, nothing waits),
         collect with ``PersonDetectResult``.  Same boxes as PersonDetect (same replay, same decode)."""
-        if self.person_detector is None or _cfg(self.person_detector, 'NAME') != 'YOLOv3':
+        if self.person_detector is None or _cfg(self.person_detector, 'NAME') not in DETECTOR_NAMES:
             return None
         if getattr(self, '_det_stream', None) is None:
             self._det_stream = torch.cuda.Stream(self.bbox_detector.device)

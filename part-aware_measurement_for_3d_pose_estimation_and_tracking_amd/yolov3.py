@@ -475,9 +475,10 @@ class YOLOv3(object):
         self.device = torch.device('cuda:%d' % device)
         if cfgfile is not None and not os.path.exists(cfgfile):
             raise FileNotFoundError(cfgfile)
-        if cfgfile is None and arch not in ARCHS:
-            raise ValueError('arch %r: expected one of %s' % (arch, ', '.join(sorted(ARCHS))))
-        model = Darknet(open(cfgfile).read() if cfgfile is not None else ARCHS[arch]())
+        archs, model_cls, net_cls = self._flavour()
+        if cfgfile is None and arch not in archs:
+            raise ValueError('arch %r: expected one of %s' % (arch, ', '.join(sorted(archs))))
+        model = model_cls(open(cfgfile).read() if cfgfile is not None else archs[arch]())
         if weightfile is not None:
             model.load_darknet_weights(weightfile)
             self.weights = weightfile
@@ -497,11 +498,23 @@ class YOLOv3(object):
             names = [l.strip() for l in open(namesfile) if l.strip()]
             self.class_id = names.index('person')
         self.score_thresh, self.nms_thresh, self.max_det = float(score_thresh), float(nms_thresh), int(max_det)
-        self.net = HipDarknet(model, self.device)
+        self.scale_xy = np.array([float(y.get('scale_x_y', 1.0)) for y in yl], dtype=np.float32)       # yolov4.YOLOv4's heads; 1 here
+        self.net = net_cls(model, self.device)
         self.use_graph = use_graph
         self._graphs, self._pool = {}, None
         self._det_ws = {}            # views per call -> workspace of pam_yolo_detect_ws (zeroed once; the kernel leaves its tickets zero)
         self._pinned = {}            # (views, fh, fw) -> two pinned (boxes, count) landing buffers of submit()
+
+    @staticmethod
+    def _flavour():
+        """(arch name -> cfg builder, the float32 module's class, the plan builder's class): what a subclass replaces (yolov4.YOLOv4)."""
+        return ARCHS, Darknet, HipDarknet
+
+    def _decode(self, st, n, nh, hp, gh, gw, cs, an, W, H, fw, fh, boxes, count, ws, need):
+        """The decode + NMS launch of _run -> (return code, entry point's name); yolov4.YOLOv4 launches the scale_x_y form."""
+        return self.lib.pam_yolo_detect_heads_ws(C.c_void_p(st), n, nh, hp, gh, gw, cs, an.ctypes.data_as(C.c_void_p), W, H, self.num_classes,
+                                                 self.class_id, self.score_thresh, self.nms_thresh, fw, fh, self.max_det,
+                                                 C.c_void_p(boxes.data_ptr()), C.c_void_p(count.data_ptr()), C.c_void_p(ws.data_ptr()), need), 'pam_yolo_detect_heads_ws'
 
     # -- device path ---------------------------------------------------------------------------------------------------------
     def _run(self, ptrs, n, fh, fw, x8, boxes, count):
@@ -522,11 +535,9 @@ class YOLOv3(object):
         ws = self._det_ws.get(n)
         if ws is None or ws.numel() < need:
             ws = self._det_ws[n] = torch.zeros(need, dtype=torch.uint8, device=self.device)
-        rc = self.lib.pam_yolo_detect_heads_ws(C.c_void_p(st), n, nh, hp, gh, gw, cs, an.ctypes.data_as(C.c_void_p), W, H, self.num_classes,
-                                               self.class_id, self.score_thresh, self.nms_thresh, fw, fh, self.max_det,
-                                               C.c_void_p(boxes.data_ptr()), C.c_void_p(count.data_ptr()), C.c_void_p(ws.data_ptr()), need)
+        rc, name = self._decode(st, n, nh, hp, gh, gw, cs, an, W, H, fw, fh, boxes, count, ws, need)
         if rc != 0:
-            raise _lib.PamError('pam_yolo_detect_heads_ws failed: %d' % rc)
+            raise _lib.PamError('%s failed: %d' % (name, rc))
         return heads
 
     def detect_dev(self, frames):
