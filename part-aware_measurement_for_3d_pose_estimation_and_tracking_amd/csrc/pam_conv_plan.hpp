@@ -225,6 +225,7 @@ inline ConvPlan plan_igemm(int ntw, int Cout, int M, bool gen, int force) {
     }
     static const int wm_of[8] = {1, 1, 2, 2, 4, 1, 1, 2}, wn_of[8] = {1, 2, 1, 2, 1, 3, 4, 3};
     if (cfg > 7 || (ntw == 2 && cfg != 0 && cfg != 2) || nb % wn_of[cfg] != 0) return plan_refused();
+    if ((long long)M * wn_of[cfg] >= (1ll << 32)) return plan_refused();      // grid.x * block.x = M * WN threads: a launch takes fewer than 2^32
     ConvPlan p = {};
     p.kernel = PAM_CONV_KERNEL_IGEMM; p.ntw = ntw; p.WM = wm_of[cfg]; p.WN = wn_of[cfg]; p.gen = gen;
     p.form = (gen ? 1000000 : 0) + 64 * p.WM * 1000 + 16 * ntw * p.WN;
@@ -242,6 +243,25 @@ inline bool c3_whole_tensor(const ConvQuery& q) {       // a 3x3 / stride 1 / pa
     return q.KH == 3 && q.KW == 3 && q.stride == 1 && q.pad == 1 && q.in_cstride == q.Cin && q.relu_from == 0;
 }
 inline bool c3_out_32bit(const ConvQuery& q) { return (size_t)q.N * q.H * q.W * q.Cout * 2 < (1ull << 31); }
+
+// ---- where each family's address arithmetic ends (DESIGN.md section 10v has the table these rest on) -------------------------------------
+// Input through a buffer resource with a 32-bit byte offset, padding taps as OOB_OFFSET = 2^31 (k_conv_igemm, k_conv3x3, k_conv_stem), or
+// through an int byte offset (k_conv_gs): right while the (sliced) input ends below byte 2^31 -- from there the padding offset lies INSIDE
+// the resource and a padding tap reads data.  k_conv3x3s forms its input addresses as 64-bit pointers and takes any size.
+inline size_t conv_in_bytes(const ConvQuery& q) { return (size_t)q.N * q.H * q.W * q.in_cstride * 2; }
+inline bool conv_in_32bit(const ConvQuery& q) { return conv_in_bytes(q) < (1ull << 31); }
+// k_conv_igemm without a padding tap (pad 0) and without a K tail (KH KW Cin a multiple of KC) forms OOB_OFFSET only for pixel rows past M,
+// which it never stores: its input is right up to 2^32 bytes, where the offsets and num_records wrap
+inline bool conv_in_igemm(const ConvQuery& q) {
+    return conv_in_32bit(q) || (q.pad == 0 && (q.KH * q.KW * q.Cin) % KC == 0 && conv_in_bytes(q) < (1ull << 32));
+}
+// Residual rows through a buffer resource with a 32-bit byte offset in every family (OOB_OFFSET only for rows that are never stored): right
+// below 2^32 bytes, where num_records and the offsets wrap.  Every family stores its output through a 64-bit pointer.
+inline bool conv_res_32bit(const ConvQuery& q, int Ho, int Wo) { return !q.residual || (size_t)q.N * Ho * Wo * q.Cout * 2 < (1ull << 32); }
+// Pixel and tile counts the launchers and kernels keep in an int: M = N Ho Wo, N H W (>= N * tiles), and the grids built from them
+inline bool conv_counts_int(const ConvQuery& q, int Ho, int Wo) {
+    return (size_t)q.N * q.H * q.W < (1ull << 31) && (size_t)q.N * Ho * Wo < (1ull << 31);
+}
 // tile_cfg -7: a Darknet layer (activation code > 1 allowed) on the streamed kernel, image packed for c3s_gen_slab (pam_conv3x3_layout_gen)
 inline ConvPlan plan_c3s_gen(const ConvQuery& q) {
     int th = 0, mt = 0, pmax = 0;
@@ -286,13 +306,16 @@ inline ConvPlan conv_plan(const ConvQuery& query) {
         KH < 1 || KW < 1 || KH > 3 || KW > 3 || q.stride < 1)
         return plan_refused();
     const int Ho = (q.H + 2 * q.pad - KH) / q.stride + 1, Wo = (q.W + 2 * q.pad - KW) / q.stride + 1;
+    if (q.H >= 32768 || q.W >= 32768 || Ho < 1 || Wo < 1) return plan_refused();
+    // the addressing frontiers: counts that the kernels keep in an int, the residual's 32-bit offsets (every family); the input's per family below
+    if (!conv_counts_int(q, Ho, Wo) || !conv_res_32bit(q, Ho, Wo)) return plan_refused();
+    const bool in32 = conv_in_32bit(q);
     const int Kpad = (KH * KW * Cin + KC - 1) / KC * KC, M = q.N * Ho * Wo;
-    if (q.H >= 32768 || q.W >= 32768) return plan_refused();
 
     // k_conv_stem: w_img = the pre-permuted A fragments (see pam.h)
     if (stem && (Cout == 64 || Cout == 32) && (q.stride == 1 || q.stride == 2)) {
         const bool mish = (relu & 3) == 3;               // YOLOv4's layer 0: the stride-1 forms have a mish instantiation
-        if (mish && q.stride != 1) return plan_refused();
+        if ((mish && q.stride != 1) || !in32) return plan_refused();
         ConvPlan p = {};
         p.kernel = PAM_CONV_KERNEL_STEM; p.form = (mish ? 1000 : 0) + q.stride * 100 + Cout; p.ntw = Cout / 16; p.mish = mish;
         return p;
@@ -309,6 +332,9 @@ inline ConvPlan conv_plan(const ConvQuery& query) {
         if (picked) return relu > 1 ? plan_refused() : plan_c3s(Cin, ntw, th, mt, pmax, false, true);
     }
 
+    // every family from here on reaches its input with 32-bit offsets: k_conv3x3 (pad 1) and k_conv_gs (gs_ok) below 2^31 bytes; the implicit
+    // GEMM takes over from k_conv_gs up to 2^32 where it forms no padding offset, and nothing takes over from it
+    if (!conv_in_igemm(q)) return plan_refused();
     const bool classic = tile_cfg == -2;                 // -2: the classic kernels (k_conv3x3 / k_conv_igemm), automatic tiles
     if (classic) tile_cfg = -1;
     if (rows3x3 && (tile_cfg < 0 || tile_cfg >= 100) &&

@@ -215,12 +215,38 @@ class ConvEngine(object):
             if kind in (1, 2):
                 return '%s C=%d %dx%d' % ('k_conv3x3s' if kind == 2 else 'k_conv3x3', op.cin, h, w)
             return '%s %dx%d stride %d' % ('k_conv_gs' if kind == 3 else 'k_conv_igemm', op.kh, op.kw, op.stride)
-        self._run(x, 'pam_conv2d_nhwc_bf16', lambda: self.lib.pam_conv2d_nhwc_bf16_ex(
-            self._cur(x), ptr(x), ptr(op.w), ptr(wimg), ptr(op.bias), ptr(res), ptr(y),
-            n, h, w, op.cin, op.cout, op.kh, op.kw, op.stride, op.pad, act, tile_cfg, in_cs, relu_from),
-            nbytes, flops, family, (n, h, w, op.cin, op.cout, res is not None, in_cs, relu_from),
-            what=(' for %s', (x.shape, op.cout, op.kh, op.stride)))
+        # The library refuses a call one of its kernels cannot address (csrc/pam_conv_plan.hpp).  A convolution is
+        # independent per image, so a larger call is issued as slices of N, each below those frontiers, one after the other on the same
+        # stream; the usual call is one slice.  conv_slice states the plan's rules once for the host: the input below 2^31 bytes -- 2^32
+        # where the implicit GEMM forms no padding offset (pad 0, K a multiple of the plan's KC = 64) and no k_conv_gs tile is stated --,
+        # the residual below 2^32, the output of the stated streamed forms (-7 / -8) below 2^31, pixel counts in an int.
+        no_pad_offset = op.pad == 0 and (op.kh * op.kw * op.cin) % 64 == 0 and not 8 <= tile_cfg <= 12
+        step = self.conv_slice(n, 2 * h * w * in_cs, 2 * ho * wo * op.cout if res is not None else 0, max(h * w, ho * wo),
+                               in_frontier=2 ** 32 if no_pad_offset else 2 ** 31,
+                               out_bytes=2 * ho * wo * op.cout if tile_cfg in (T.GEN_STREAMED, T.SLAB32) else 0)
+        for i in range(0, n, step):
+            xs, ys, rs = x[i:i + step], y[i:i + step], (None if res is None else res[i:i + step])
+            self._run(x, 'pam_conv2d_nhwc_bf16', lambda xs=xs, ys=ys, rs=rs: self.lib.pam_conv2d_nhwc_bf16_ex(
+                self._cur(xs), ptr(xs), ptr(op.w), ptr(wimg), ptr(op.bias), ptr(rs), ptr(ys),
+                xs.shape[0], h, w, op.cin, op.cout, op.kh, op.kw, op.stride, op.pad, act, tile_cfg, in_cs, relu_from),
+                nbytes * xs.shape[0] // n, flops * xs.shape[0] // n, family,
+                (xs.shape[0], h, w, op.cin, op.cout, res is not None, in_cs, relu_from),
+                what=(' for %s', (xs.shape, op.cout, op.kh, op.stride)))
         return y
+
+    @staticmethod
+    def conv_slice(n, in_bytes, res_bytes, pixels, in_frontier=2 ** 31, out_bytes=0):
+        """Images per launch for n images of in_bytes (residual: res_bytes, 0 = none; out_bytes: only where the form bounds its output)
+        and `pixels` pixels each: the largest count whose input stays below in_frontier bytes, whose residual stays below 2^32, whose
+        bounded output stays below 2^31 and whose pixels stay below 2^31, as even slices."""
+        cap = min((in_frontier - 1) // max(in_bytes, 1), (2 ** 32 - 1) // max(res_bytes, 1), (2 ** 31 - 1) // max(out_bytes, 1),
+                  (2 ** 31 - 1) // max(pixels, 1))
+        if cap >= n:
+            return n
+        if cap < 1:
+            raise _lib.PamError('one image of this convolution exceeds the 32-bit addressing of the conv kernels')
+        parts = (n + cap - 1) // cap
+        return (n + parts - 1) // parts
 
     down_s = True               # 3x3 stride-2 layers with 96 / 192 input channels on k_down_s (csrc/pam_down.hip); False: the generic kernels
 

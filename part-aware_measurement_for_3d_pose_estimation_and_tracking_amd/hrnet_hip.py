@@ -344,10 +344,23 @@ class HipHRNet(ConvEngine):
         """stem + layer1: one dependent chain on the caller's stream -> the (N, 256, H/4, W/4) tensor the branches start from"""
         self._epoch()
         n8, _, h8, w8 = x8.shape
-        # the fused kernels index with 32 bits: > 606 crops of 384 x 288 (N H W 512 >= 2^31 at a quarter of the resolution) take the
-        # un-fused launches, which address with 64 bits
-        small = n8 * ((h8 + 3) // 4) * ((w8 + 3) // 4) * 512 < 2 ** 31 and n8 * h8 * w8 * 16 < 2 ** 31
-        if self.fuse_stem and self.fuse_tail and self.stop_after != 'stem' and small:
+        # The head's kernels, fused or not, index with 32 bits and refuse a tensor of 2^31 bytes (the 256-channel tensor at a quarter of
+        # the resolution, the stem's 64 channels at half of it, the 8-channel input): > 606 crops of 384 x 288 run as even slices of
+        # at most that many crops, one after the other on this stream, each through the same launches as a smaller batch.
+        h4, w4 = (h8 + 3) // 4, (w8 + 3) // 4
+        step, out = self.conv_slice(n8, max(h4 * w4 * 512, h8 * w8 * 16), 0, h8 * w8), None
+        if step >= n8:
+            return self._head_slice(x8)
+        for i in range(0, n8, step):
+            part = self._head_slice(x8[i:i + step])
+            if out is None:
+                out = self._new(n8, part.shape[1], part.shape[2], part.shape[3], x8.device)
+            out[i:i + step].copy_(part)
+        return out
+
+    def _head_slice(self, x8):
+        """_head for a batch every kernel can address"""
+        if self.fuse_stem and self.fuse_tail and self.stop_after != 'stem':
             x0, y = self.stem_fused(self.stem, x8)
         else:
             x = self.conv(self.conv1, x8, relu=True)
@@ -362,7 +375,7 @@ class HipHRNet(ConvEngine):
             if y is None:
                 y = self.pointwise64(self.pw0, x0)
             for i, b in enumerate(self.layer1):
-                if self.fuse_bneck and small and (i > 0 or self.fuse_bneck0):
+                if self.fuse_bneck and (i > 0 or self.fuse_bneck0):
                     x, y = self.bottleneck_fused(self.bnecks[i], y, res, x0 if i == 0 else None)
                 else:
                     y2 = self.conv(b['c2'], y, relu=True)
@@ -492,7 +505,9 @@ class HipPoseResNet(ConvEngine):
     # -- network ------------------------------------------------------------------------------------------------------------------------
     def _layer1(self, x0):
         n, _, h, w = x0.shape
-        small = n * h * w * 512 < 2 ** 31                                # the fused kernels index with 32 bits (as HipHRNet._head)
+        # the fused bottleneck indexes its 256-channel tensors with 32 bits and refuses 2^31 bytes; a larger batch takes the un-fused
+        # convolutions, which conv() issues as slices of N below the generic kernels' own 32-bit frontiers
+        small = n * h * w * 512 < 2 ** 31
         if self.fuse_layer1 and small:
             y = self.pointwise64(self.pw0, x0)                          # the stem's epoch: block 0 reads x0 and y from the other half
             res = None
