@@ -625,6 +625,34 @@ int pam_resnet_stem_nhwc_bf16(void* stream, const void* in, const void* wfrag, c
  * N 4 H W Cout 2 < 2^31 (32-bit offsets).  PAM_E_ARG otherwise (null pointer included), PAM_E_HIP on a launch error. */
 int pam_deconv4x4s2_nhwc_bf16(void* stream, const void* in, const void* wimg, const float* bias, void* out, int N, int H, int W,
                               int Cin, int Cout, int relu);
+/* ---- ViTPose token kernels (csrc/pam_vit.hip; executor: hrnet_hip.HipViTPose) ---------------------------------------------------
+ * Activations are bf16; a token tensor of M = B T rows and D channels is the NHWC tensor (B, 16, 12, D).  Biases, LayerNorm's gamma / beta
+ * and the position table are float32.  Every entry point answers PAM_E_ARG on a null pointer (residual excepted) or a shape outside
+ * the constraints below, PAM_E_HIP on a launch error.
+ * Linear weight image (packing.PackedLinear), N K bf16: [slab s = N / 64][k-step c = K / 32][n-tile j = 4][lane 64][8]: lane l holds output
+ * channel 64 s + 16 ((l & 15) >> 2) + 4 j + (l & 3) and input channels 32 c + 8 (l >> 4) .. + 7.
+ * pam_vit_linear_bf16: out = bf16(act(x . w^T + bias) [+ residual]), x (M, K), out and residual (M, N); act 0 = linear, 1 = exact GELU
+ * 0.5 v (1 + erff(v 0.70710678f)) in float32; a residual only with act 0.  float32 accumulation (v_mfma_f32_16x16x32_bf16), one bf16
+ * rounding.  Constraints: K % 64 == 0, N % 64 == 0, M >= 1; frontier: M K 2 < 2^31 and M N 2 < 2^31 bytes (32-bit buffer offsets), N <= 128 * 65535. */
+int pam_vit_linear_bf16(void* stream, const void* x, const void* w, const float* bias, const void* residual, void* out, int M, int K, int N,
+                        int act);
+/* pam_vit_patch_embed_bf16: Conv2d(3, D, 16, stride 16, padding 2) of the crop kernel's (N, H, W, 8) bf16 output + the folded position
+ * table: out[n][t][d] = bf16(sum + pos_bias[t][d]), t = ty (W / 16) + tx, out (N, T = H W / 256, D); pos_bias (T, D) float32 =
+ * pos[t + 1] + pos[0] + bias, folded by the host.  Taps in the 2-pixel border outside the crop read zero.  The weights are packed for
+ * ALL 8 channels of a pixel (channels 3 .. 7 zero): the linear image above with K = 2048 in the order (ky, kx, channel).
+ * Constraints: H % 16 == 0, W % 16 == 0, D % 64 == 0; frontier: N H W 16 < 2^31 and N T D 2 < 2^31 bytes, D <= 128 * 65535. */
+int pam_vit_patch_embed_bf16(void* stream, const void* x8, const void* w, const float* pos_bias, void* out, int N, int H, int W, int D);
+/* pam_vit_layernorm_bf16: out = bf16((x - mean) / sqrt(var + eps) * gamma + beta) per row of D channels; mean and the variance of the
+ * centred values in float32 over the row held in registers, one bf16 rounding.  Constraints: D % 64 == 0, D <= 2048, M >= 1, eps >= 0
+ * (offsets are 64-bit: no frontier below M = 2^31). */
+int pam_vit_layernorm_bf16(void* stream, const void* x, const float* gamma, const float* beta, void* out, int M, int D, float eps);
+/* pam_vit_attention_bf16: softmax(Q K^T / 8) V per (crop, head) over all T keys, head dimension 64: qkv (B, T, 3, heads, 64), out
+ * (B, T, heads 64).  Scores in float32 (scale 0.125 applied in float32), the row maximum subtracted, expf, P rounded to bf16 for the
+ * P V product -- as two bf16 terms, the rounding and the rounding of its remainder, so that P's error stays below the 2^-9 sum p |v|
+ * the kernel is tested against (one bf16 rounding alone is up to 2^-8) --, the result divided by the float32 sum of the unrounded
+ * exponentials, one bf16 rounding at the store.  Constraints: T % 16 == 0,
+ * 16 <= T <= 192, B <= 65535, heads <= 65535 (grid dimensions; offsets are 64-bit). */
+int pam_vit_attention_bf16(void* stream, const void* qkv, void* out, int B, int T, int heads);
 /* y = ReLU(W . x + bias), 64 -> 64 channels, pointwise (the first Bottleneck's conv1 on the stem output): w_img [64 rows][64 K] bf16, row
  * 16 jt + qq = output channel 16 (qq >> 2) + 4 jt + (qq & 3), natural K order, the row's 16-byte piece at position p holds K values
  * 8 q .. 8 q + 7 with q = p ^ ((row >> 1) & 7). */

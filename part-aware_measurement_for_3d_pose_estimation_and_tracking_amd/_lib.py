@@ -139,6 +139,10 @@ _SIGS = {
     'pam_bottleneck_fused_nhwc_bf16': (_I, [_P] * 12 + [_I, _I, _I]),
     'pam_resnet_stem_nhwc_bf16': (_I, [_P] * 5 + [_I, _I, _I]),
     'pam_deconv4x4s2_nhwc_bf16': (_I, [_P] * 5 + [_I] * 6),
+    'pam_vit_linear_bf16': (_I, [_P] * 6 + [_I] * 4),
+    'pam_vit_patch_embed_bf16': (_I, [_P] * 5 + [_I] * 4),
+    'pam_vit_layernorm_bf16': (_I, [_P] * 5 + [_I, _I, C.c_float]),
+    'pam_vit_attention_bf16': (_I, [_P] * 3 + [_I] * 3),
     'pam_bottleneck_tail_nhwc_bf16': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_longlong, _I]),
     'pam_conv3x3s2_c48_tile': (_I, [_I, _I, _I, _I, _P]),
     'pam_conv3x3s2_c48_nhwc_bf16': (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I] + [_I] * 9),

@@ -1,4 +1,4 @@
-"""HRNet-W48 / -W32 and PoseResNet top-down 2D pose (a1): the ``HRNetPose(...).predict(...)`` seam of the reference
+"""HRNet-W48 / -W32, PoseResNet and ViTPose top-down 2D pose (a1): the ``HRNetPose(...).predict(...)`` seam of the reference
 (/root/reference/src/ivclabpose.py:125-134,210; the backend itself is git-ignored there).
 
 The conv stack is the hand-written HIP executor of hrnet_hip.py (MFMA kernels of csrc/, bf16 channels-last, BatchNorm folded), replayed
@@ -14,7 +14,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, poseresnet, stages
+from . import _lib, poseresnet, stages, vitpose
 from .dump import DumpResults
 from .replay import ForwardReplay
 # Names that callers outside the package reach as hrnet.X, one line per home.  bench.py: PoseHighResolutionNet, init_random,
@@ -29,11 +29,14 @@ class HRNetPose(ForwardReplay):
     """Mirror of ``backend.HRPose.SimpleHRNet.HRNetPose``: ctor (c, nof_joints, checkpoint, model_name, resolution, ...),
     ``predict(person_bbox_list, batch_size, conf_threshold) -> dump_results`` (ivclabpose.py:131-132,210).
     c: the network width, 48 (HRNet-W48, the reference's configs) or 32 (HRNet-W32, usually at resolution (256, 192)); with
-    model_name='PoseResNet' the ResNet depth, 50 / 101 / 152 (Simple Baselines: poseresnet.py, executor hrnet_hip.HipPoseResNet)."""
+    model_name='PoseResNet' the ResNet depth, 50 / 101 / 152 (Simple Baselines: poseresnet.py, executor hrnet_hip.HipPoseResNet); with
+    model_name='ViTPose' the variant 'B' / 'L' (or 768 / 1024) at resolution (256, 192) (vitpose.py, executor hrnet_hip.HipViTPose)."""
     WIDTHS = (32, 48)
     width = 48                  # the class default: config_for reads it (tests build objects with __new__)
-    model_name = 'HRNet'        # or 'PoseResNet' (model_name 'PoseResNet' / 'poseresnet' / 'ResNet' / 'resnet'; c = depth 50 / 101 / 152)
+    model_name = 'HRNet'        # or 'PoseResNet' (model_name 'PoseResNet' / 'poseresnet' / 'ResNet' / 'resnet'; c = depth 50 / 101 / 152),
+                                # or 'ViTPose' (model_name 'ViTPose' / 'vitpose'; c = 'B' / 'L' / 768 / 1024, resolution (256, 192) only)
     depth = None
+    variant = None              # ViTPose: 'B' | 'L'
     _hd_scratch = None          # head_decode's scratch, grown on demand
 
     def __init__(self, c, nof_joints, checkpoint_path, model_name='HRNet', resolution=(384, 288), hrpose_args=None,
@@ -52,8 +55,14 @@ class HRNetPose(ForwardReplay):
                 raise ValueError('HRNetPose: PoseResNet depth c=%r is not supported (PoseResNet-%s only)' % (
                     c, ' / -'.join(str(d) for d in sorted(poseresnet.DEPTHS))))
             self.model_name, self.depth, self.width = 'PoseResNet', int(c), None
+        elif model_name in vitpose.MODEL_NAMES:
+            # the plain vision transformer: c is the variant, 'B' / 'L' or its width 768 / 1024; one resolution (ValueError otherwise)
+            self.model_name, self.depth, self.width, c = 'ViTPose', None, None, vitpose.variant_of(c)
+            self.variant = c
+            vitpose.check_resolution(resolution)
         elif model_name != 'HRNet':
-            raise ValueError('HRNetPose: unknown model_name %r (HRNet, or PoseResNet as %s)' % (model_name, ' / '.join(poseresnet.MODEL_NAMES)))
+            raise ValueError('HRNetPose: unknown model_name %r (HRNet, PoseResNet as %s, or ViTPose as %s)' % (
+                model_name, ' / '.join(poseresnet.MODEL_NAMES), ' / '.join(vitpose.MODEL_NAMES)))
         assert int(nof_joints) == 17
         if model_name == 'HRNet':
             if int(c) != c or int(c) not in self.WIDTHS:
@@ -82,24 +91,27 @@ class HRNetPose(ForwardReplay):
         self.resolution = tuple(resolution)
         self.dtype = dtype
         self.max_dets = max_dets
-        resnet = self.model_name == 'PoseResNet'
+        resnet, vit = self.model_name == 'PoseResNet', self.model_name == 'ViTPose'
+        family = vitpose if vit else (poseresnet if resnet else None)
         if checkpoint_path and os.path.exists(checkpoint_path):
-            model = (poseresnet.load_folded_checkpoint if resnet else load_folded_checkpoint)(checkpoint_path, c, nof_joints)
+            model = (family.load_folded_checkpoint if family else load_folded_checkpoint)(checkpoint_path, c, nof_joints)
             self.weights = checkpoint_path
         else:
-            model = (poseresnet.folded_random_model if resnet else _folded_random_model)(c, nof_joints, seed)
+            model = (family.folded_random_model if family else _folded_random_model)(c, nof_joints, seed)
             self.weights = 'random(seed=%d)' % seed
-        self.head = model.final_layer.to(self.device).float()           # 1x1 head + decode stay float32
+        holder = model.keypoint_head if vit else model                  # the module that owns the 1x1 head
+        self.head = holder.final_layer.to(self.device).float()          # 1x1 head + decode stay float32
         self.head_w = self.head.weight.detach().reshape(int(nof_joints), -1).contiguous()     # [17][c] for k_head
         self.head_b = self.head.bias.detach().contiguous()
-        model.final_layer = nn.Identity()
+        holder.final_layer = nn.Identity()
         # the conv stack = the hand-written MFMA kernels of csrc/ (hrnet_hip.HipHRNet); there is no other backend in the product: the
         # PyTorch-ROCm form of the same folded module that the tests compare against lives in tests/torch_ref.py
         if backend != 'hip':
             raise ValueError("HRNetPose has one conv backend, 'hip' (got %r)" % (backend,))
         self.backend = backend
-        from .hrnet_hip import HipHRNet, HipHRNetW32, HipPoseResNet
-        self.hip = HipPoseResNet(model, self.device) if resnet else (HipHRNetW32 if self.width == 32 else HipHRNet)(model, self.device)
+        from .hrnet_hip import HipHRNet, HipHRNetW32, HipPoseResNet, HipViTPose
+        self.hip = (HipViTPose(model, self.device) if vit else HipPoseResNet(model, self.device) if resnet else
+                    (HipHRNetW32 if self.width == 32 else HipHRNet)(model, self.device))
         self.in_channels = 8
         self.model = None
         # crop resize: False = plain bilinear (cv2.resize INTER_LINEAR semantics; the default: exact for boxes up to the network input, and what

@@ -1,9 +1,10 @@
-"""HRNet-W48 / -W32 and PoseResNet conv stacks on the hand-written MFMA kernels of csrc/ (no MIOpen in the loop): the executors.
+"""HRNet-W48 / -W32, PoseResNet and ViTPose on the hand-written MFMA kernels of csrc/ (no MIOpen in the loop): the executors.
 
 The folded (conv + bias) PyTorch module of hrnet.py / poseresnet.py is walked once into packed weights (packing.py); a forward then
 issues the launches of engine.ConvEngine -- bias, residual add and ReLU fused into the convolutions' epilogues -- in the executor's
 schedule: HipHRNet runs the branches of an HR module on side streams and orders them by stream events or device-side flags,
-HipPoseResNet is one dependent chain.  The whole forward is hipGraph-capturable."""
+HipPoseResNet and HipViTPose (token kernels of csrc/pam_vit.hip, then PoseResNet's deconvolutions) are one dependent chain each.  The
+whole forward is hipGraph-capturable."""
 import ctypes as C
 
 import torch
@@ -11,8 +12,8 @@ import torch
 from . import _lib
 from .engine import ActivationArena, ConvEngine, TileCfg, ptr  # noqa: F401
 # the packers lived in this module before packing.py: tests and tools reach them as hrnet_hip.X
-from .packing import (PackedBlock, PackedBneck, PackedConv, PackedDeconv, PackedPointwise64, PackedResNetStem, PackedStem,  # noqa: F401
-                      PackedTail, PackedUp, conv64_image, down48_image, streamed_image)
+from .packing import (PackedBlock, PackedBneck, PackedConv, PackedDeconv, PackedLinear, PackedPointwise64, PackedResNetStem,  # noqa: F401
+                      PackedStem, PackedTail, PackedUp, conv64_image, down48_image, streamed_image)
 
 
 class HipHRNet(ConvEngine):
@@ -557,6 +558,132 @@ class HipPoseResNet(ConvEngine):
                 x = self._bottleneck(b, x)
             if stop == 'layer%d' % (k + 2):
                 return x
+        for k, op in enumerate(self.deconvs):
+            self._epoch()
+            x = self.deconv(op, x, relu=True)
+            if stop == 'deconv%d' % k:
+                return x
+        return x
+
+
+class HipViTPose(ConvEngine):
+    """ViTPose-B / -L (vitpose.ViTPose, BN folded) on the token kernels of csrc/pam_vit.hip: ONE dependent chain on the caller's stream.
+    A token tensor (N T rows of D channels) is the channels-last tensor (N, D, 16, 12), so every activation comes from the arena like a
+    feature map.  Patch embedding (+ position table), then per block LayerNorm, qkv, attention, proj + residual, LayerNorm, fc1 + GELU,
+    fc2 + residual -- all four linears through pam_vit_linear_bf16 --, the last LayerNorm and the two k_deconv4x4s2 of the head.
+    ``features`` returns the (N, 256, 64, 48) channels-last bf16 map that HRNetPose's head + decode read.  No branch streams."""
+    CONFIGS = {'vit': dict()}
+    config_name = 'vit'
+    flag_sync = False           # one chain: HRNetPose captures the stream-event form only
+    stop_after = None           # tests / tools: a name of STAGES -> the forward ends there
+    STAGES = ('patch',) + tuple('block%d' % i for i in range(12)) + ('norm', 'deconv0', 'deconv1')     # ViTPose-B's; an object holds its own
+
+    def __init__(self, folded_model, device):
+        self.lib = _lib.load()
+        self.device = device
+        self._pack(folded_model, device)
+        self.count = None
+
+    def _pack(self, m, device):
+        from . import vitpose
+        bb = m.backbone
+        self.dim, self.heads, self.depth = m.dim, m.heads, m.depth
+        self.STAGES = ('patch',) + tuple('block%d' % i for i in range(m.depth)) + ('norm', 'deconv0', 'deconv1')
+        self.patch = PackedLinear(vitpose.patch_matrix(bb.patch_embed.proj), None, device)
+        self.pos_bias = vitpose.position_bias(bb).to(device).contiguous()
+        L = lambda lin: PackedLinear(lin.weight, lin.bias, device)
+        N = lambda ln: (ln.weight.detach().float().to(device).contiguous(), ln.bias.detach().float().to(device).contiguous(), float(ln.eps))
+        self.blocks = [dict(n1=N(b.norm1), qkv=L(b.attn.qkv), proj=L(b.attn.proj), n2=N(b.norm2), fc1=L(b.mlp.fc1), fc2=L(b.mlp.fc2))
+                       for b in bb.blocks]
+        self.last_norm = N(bb.last_norm)
+        dl = m.keypoint_head.deconv_layers
+        self.deconvs = [PackedDeconv(dl[i], device) for i in (0, 3)]
+
+    deconv = HipPoseResNet.deconv
+
+    # -- launches of csrc/pam_vit.hip ---------------------------------------------------------------------------------------------------
+    def patch_embed(self, op, pos_bias, x8):
+        """Conv2d(3, D, 16, stride 16, padding 2) + position table: (N, 8, H, W) -> the token tensor (N, D, H / 16, W / 16)."""
+        n, c, h, w = x8.shape
+        assert c == 8 and h % 16 == 0 and w % 16 == 0, tuple(x8.shape)
+        d, t = op.n, (h // 16) * (w // 16)
+        y = self._new(n, d, h // 16, w // 16, x8.device)
+        nbytes = 2 * (x8.numel() + y.numel() + d * op.k) + 4 * t * d
+        flops = 2 * n * t * d * 3 * 256                                 # counted at the 3 real input channels
+        if self._tally(x8, nbytes, flops):
+            return y
+        assert x8.is_contiguous(memory_format=torch.channels_last) and tuple(pos_bias.shape) == (t, d)
+        self._run(x8, 'pam_vit_patch_embed_bf16', lambda: self.lib.pam_vit_patch_embed_bf16(
+            self._cur(x8), ptr(x8), ptr(op.w), ptr(pos_bias), ptr(y), n, h, w, d),
+            nbytes, flops, 'k_vit_gemm patch embedding', (n, h, w, d), what=(' for %s', tuple(x8.shape)))
+        return y
+
+    def layernorm(self, p, x):
+        """LayerNorm over the channels of every token; p = (gamma, beta, eps)."""
+        n, d, h, w = x.shape
+        y = self._new(n, d, h, w, x.device)
+        nbytes, flops = 2 * 2 * x.numel() + 8 * d, 8 * x.numel()
+        if self._tally(x, nbytes, flops):
+            return y
+        assert x.is_contiguous(memory_format=torch.channels_last)
+        self._run(x, 'pam_vit_layernorm_bf16', lambda: self.lib.pam_vit_layernorm_bf16(
+            self._cur(x), ptr(x), ptr(p[0]), ptr(p[1]), ptr(y), n * h * w, d, C.c_float(p[2])),
+            nbytes, flops, 'k_vit_layernorm D=%d' % d, (n * h * w, d), what=(' for %s', tuple(x.shape)))
+        return y
+
+    def linear(self, op, x, res=None, gelu=False):
+        """bf16(act(x W^T + b) [+ res]) per token: (N, K, h, w) -> (N, N', h, w)."""
+        n, k, h, w = x.shape
+        assert k == op.k and not (gelu and res is not None), (x.shape, op.k)
+        y = self._new(n, op.n, h, w, x.device)
+        nbytes = 2 * (x.numel() + y.numel() + op.n * op.k + (y.numel() if res is not None else 0)) + 4 * op.n
+        flops = 2 * y.numel() * op.k
+        if self._tally(x, nbytes, flops):
+            return y
+        assert x.is_contiguous(memory_format=torch.channels_last) and (res is None or (res.shape == y.shape and res.is_contiguous(memory_format=torch.channels_last)))
+        self._run(x, 'pam_vit_linear_bf16', lambda: self.lib.pam_vit_linear_bf16(
+            self._cur(x), ptr(x), ptr(op.w), ptr(op.bias), ptr(res), ptr(y), n * h * w, op.k, op.n, 1 if gelu else 0),
+            nbytes, flops, 'k_vit_gemm %d->%d' % (op.k, op.n), (n * h * w, op.k, op.n, res is not None, bool(gelu)),
+            what=(' for %s -> %d', tuple(x.shape), op.n))
+        return y
+
+    def attention(self, qkv, heads):
+        """softmax(Q K^T / 8) V per crop and head: (N, 3 heads 64, h, w) -> (N, heads 64, h, w)."""
+        n, c, h, w = qkv.shape
+        assert c == 3 * heads * 64, (qkv.shape, heads)
+        t = h * w
+        y = self._new(n, heads * 64, h, w, qkv.device)
+        nbytes, flops = 2 * (qkv.numel() + y.numel()), 2 * 2 * n * heads * t * t * 64
+        if self._tally(qkv, nbytes, flops):
+            return y
+        assert qkv.is_contiguous(memory_format=torch.channels_last)
+        self._run(qkv, 'pam_vit_attention_bf16', lambda: self.lib.pam_vit_attention_bf16(self._cur(qkv), ptr(qkv), ptr(y), n, t, heads),
+                  nbytes, flops, 'k_vit_attention T=%d' % t, (n, t, heads), what=(' for %s', tuple(qkv.shape)))
+        return y
+
+    # -- network ------------------------------------------------------------------------------------------------------------------------
+    def block(self, b, x):
+        """One pre-norm block: an arena epoch of its own (it reads the previous block's output from the other half)."""
+        self._epoch()
+        a = self.attention(self.linear(b['qkv'], self.layernorm(b['n1'], x)), self.heads)
+        x = self.linear(b['proj'], a, res=x)
+        return self.linear(b['fc2'], self.linear(b['fc1'], self.layernorm(b['n2'], x), gelu=True), res=x)
+
+    def _features(self, x8):
+        """x8: (N, 8, 256, 192) channels-last bf16 (RGB + 5 zero channels) -> (N, 256, 64, 48) channels-last bf16."""
+        stop = self.stop_after
+        self._epoch()
+        x = self.patch_embed(self.patch, self.pos_bias, x8)
+        if stop == 'patch':
+            return x
+        for i, b in enumerate(self.blocks):
+            x = self.block(b, x)
+            if stop == 'block%d' % i:
+                return x
+        self._epoch()
+        x = self.layernorm(self.last_norm, x)
+        if stop == 'norm':
+            return x
         for k, op in enumerate(self.deconvs):
             self._epoch()
             x = self.deconv(op, x, relu=True)

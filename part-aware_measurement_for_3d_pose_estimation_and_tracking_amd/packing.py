@@ -320,3 +320,30 @@ class PackedDeconv(object):
         self.cin, self.cout = int(w.shape[0]), int(w.shape[1])
         self.w = bf16_on(deconv_image(w), device)
         self.bias = bias_of(deconv, n=self.cout).to(device).contiguous()
+
+
+# -- the token kernels' linear layers (csrc/pam_vit.hip) ---------------------------------------------------------------------------------
+def linear_image(w):
+    """(N, K) float32 -> the flat image of pam_vit_linear_bf16 (layout: include/pam.h): [N / 64 slabs s][K / 32 k-steps c][4 n-tiles j]
+    [64 lanes][8]; lane l holds output channel 64 s + 16 ((l & 15) >> 2) + 4 j + (l & 3) and input channels 32 c + 8 (l >> 4) .. + 7."""
+    n, k = w.shape
+    assert n % 64 == 0 and k % 64 == 0, (n, k)
+    w7 = w.reshape(n // 64, 4, 4, 4, k // 32, 4, 8)                        # [s][a = (l & 15) >> 2][j][b = l & 3][c][g = l >> 4][8]
+    return w7.permute(0, 4, 2, 5, 1, 3, 6).reshape(-1)                     # [s][c][j][g][a][b][8]: lane = 16 g + 4 a + b
+
+
+def linear_unimage(img, n, k):
+    """The inverse of ``linear_image``: the flat image -> the (N, K) matrix (the packing round trip of the tests)."""
+    t = img.reshape(n // 64, k // 32, 4, 4, 4, 4, 8)                        # [s][c][j][g][a][b][8]
+    return t.permute(0, 4, 2, 5, 1, 3, 6).reshape(n, k)
+
+
+class PackedLinear(object):
+    """A linear layer y = x W^T + b (weight (N, K), N and K multiples of 64) packed for ``pam_vit_linear_bf16``; with K = 2048 rows in
+    the order (ky, kx, 8 channels) the same image is the patch embedding's (``pam_vit_patch_embed_bf16``; vitpose.patch_matrix)."""
+
+    def __init__(self, weight, bias, device):
+        w = weight.detach().float()
+        self.n, self.k = int(w.shape[0]), int(w.shape[1])
+        self.w = bf16_on(linear_image(w), device)
+        self.bias = (bias.detach().float() if bias is not None else torch.zeros(self.n)).to(device).contiguous()

@@ -50,7 +50,8 @@ class FramePipeline(object):
         graph_bucket) at construction -- `self.warmed` says what that cost -- and pad every frame's forward to its bucket, so that no
         step() ever captures (the reference's call shape has a fixed batch_size = 20, /root/reference/src/ivclabpose.py:208-212).
         width / resolution: the pose network FramePipeline builds when no `net` is given (HRNet-W48 at 384 x 288; 32 / (256, 192) = W32;
-        model_name='PoseResNet' with width = the ResNet depth, as HRNetPose takes it).
+        model_name='PoseResNet' with width = the ResNet depth, model_name='ViTPose' with width = 'B' / 'L' and resolution (256, 192),
+        as HRNetPose takes them).
         flip_test / shift_heatmap / post_process: that network's decode options (HRNetPose: the official test protocol; the flip test
         doubles every forward, prewarm captures the doubled counts).  A shared `net` keeps its own settings.
         dark / blur_kernel: that network's DARK decode (HRNetPose; the forwards keep their size).
