@@ -455,6 +455,47 @@ int pam_head_decode_dark(void* stream, int n, int flip_row0, int hm_h, int hm_w,
                          const float* bias, int J, int flags, int blur_kernel, float* dev_heatmaps_or_null, const int32_t* dev_view_of,
                          const int32_t* dev_slot_of, const float* dev_boxes, int max_dets, double* dev_det, float* dev_kp_xyc,
                          void* dev_scratch);
+/* ---- the UDP protocol (Huang et al., "The Devil is in the Details: Delving into Unbiased Data Processing for Human Pose Estimation",
+ * CVPR 2020; the test protocol of every public ViTPose checkpoint and of the HRNet / Simple Baselines "+UDP" ones) ----
+ * The effective box (xe, ye, We, He) is the one above (UDP's _box2cs is the same function); only the pitch through it changes: crop and
+ * heat-map are align-corners grids whose first and last points are the box's edges.
+ * pam_preprocess_crops_udp: arguments, row layout, flip, antialias, out_c and dev_eff_xywh exactly as pam_preprocess_crops_affine.  In
+ * float32, output pixel (u, v) reads the frame at sx = xe + u * (We / (out_w - 1)), sy = ye + v * (He / (out_h - 1)) (mmpose's
+ * get_warp_matrix(0, 2c, size - 1, 200 s) inverted).  Everything else is the affine form's: integer coordinates are pixel centres,
+ * bilinear over the four neighbours, a tap outside the frame contributes 0, a box with We == 0 is all zero, the antialias branch takes
+ * the new pitch as its scale, the mirror rows are the column reversal bit for bit.  warpAffine's uint8 and fixed-point rounding are not
+ * reproduced and there is no rotation.  PAM_E_ARG: as pam_preprocess_crops_affine, and for out_w < 2 or out_h < 2. */
+int pam_preprocess_crops_udp(void* stream, int n, int n_total, int flip, const void* const* dev_frames, int frame_h, int frame_w,
+                             const int32_t* dev_view_of, const float* dev_boxes, float box_scale, int out_h, int out_w, int out_c,
+                             void* dev_out_bf16, int antialias, float* dev_eff_xywh);
+/* pam_head_decode_udp: mmpose 0.x keypoints_from_heatmaps(use_udp=True, target_type='GaussianHeatmap') in the head pass: the UDP form
+ * of DARK (post_dark_udp) and UDP's transform_preds.  Arguments as pam_head_decode_dark; flags takes PAM_FLIP_MERGE and PAM_FLIP_SHIFT
+ * under the rules of pam_head_decode_flip (the UDP configs run the flip test without the shift) and M is the map they define.
+ * blur_kernel = k is 0, or odd with 9 <= k <= 17; R, sigma and the float64 taps as in pam_head_decode_dark.
+ *   1. (py, px) = arg-max of M, NOT of the blurred map (first maximum; nothing above -inf: cell 0); the score is M[py][px].
+ *   2. blur_kernel == 0: no offset, step 8.
+ *   3. B = GaussianBlur(M, (k, k), 0) with OpenCV's default border, BORDER_REFLECT_101: separable, rows first, then columns, float64
+ *      sums in ascending tap order.  An index i outside [0, n) reads cell r(i): m = i mod 2 (n - 1) taken non-negative,
+ *      r = m < n ? m : 2 (n - 1) - m (also where R >= n and the reflection bounces more than once).  No zero frame, no rescale.
+ *   4. L = log(min(max(B, 0.001), 50)) in float64 (a NaN clamps to 0.001).
+ *   5. L is read edge-replicated: sample (py + dy, px + dx) is taken at the coordinates clamped into the map.  There is NO inside rule:
+ *      a winner on the border or in a corner takes the step too.
+ *   6. Seven samples: the centre, x +- 1, y +- 1, (+1, +1) and (-1, -1).  dx = 0.5 (L[x+1] - L[x-1]), dy alike;
+ *      dxx = L[x+1] - 2 L[0] + L[x-1], dyy alike (+- 1 and no 0.25, unlike DARK);
+ *      dxy = 0.5 (L[+1,+1] - L[x+1] - L[y+1] + 2 L[0] - L[x-1] - L[y-1] + L[-1,-1]).
+ *   7. H' = [[dxx + e, dxy], [dxy, dyy + e]], e = 2^-23 (np.finfo(np.float32).eps).  If det H' is non-zero and finite:
+ *      (ox, oy) = -H'^-1 (dx, dy); otherwise no offset.  Nothing clamps the offset.
+ *   8. UDP's transform_preds, float64 arithmetic with one float32 rounding: x = (double)xe + (px + ox) * ((double)We / (hm_w - 1)),
+ *      y = (double)ye + (py + oy) * ((double)He / (hm_h - 1)), with (xe, ye, We, He) = dev_boxes[crop].  det and kp rows as in every decode.
+ * Not reproduced: mmpose's float32 heat-map arithmetic (float64 here, from the float32 map) and the CombinedTarget offset-map decode.
+ * dev_heatmaps_or_null receives M, as in pam_head_decode_flip.  dev_scratch: pam_head_decode_udp_scratch_bytes(n, hm_h, hm_w) bytes (-1
+ * for a refused shape).  PAM_E_ARG: hm_w < 2 or hm_h < 2, PAM_FLIP_QUARTER or unknown bits, a blur_kernel that is neither 0 nor odd in
+ * [9, 17], and what pam_head_decode_flip refuses.  n == 0: PAM_OK. */
+long long pam_head_decode_udp_scratch_bytes(int n, int hm_h, int hm_w);
+int pam_head_decode_udp(void* stream, int n, int flip_row0, int hm_h, int hm_w, const void* feat_bf16, int C, const float* w,
+                        const float* bias, int J, int flags, int blur_kernel, float* dev_heatmaps_or_null, const int32_t* dev_view_of,
+                        const int32_t* dev_slot_of, const float* dev_boxes, int max_dets, double* dev_det, float* dev_kp_xyc,
+                        void* dev_scratch);
 int pam_decode_heatmaps(void* stream, int n, const float* dev_heatmaps, int nchw, int hm_h, int hm_w,
                         const int32_t* dev_view_of, const int32_t* dev_slot_of, const float* dev_boxes,
                         int max_dets, double* dev_det, float* dev_kp_xyc /*optional n*17*3 (x,y,conf) or NULL*/);

@@ -114,6 +114,7 @@ _SIGS = {
     'pam_preprocess_crops_ex': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I]),
     'pam_preprocess_crops_flip': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I]),
     'pam_preprocess_crops_affine': (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, C.c_float, _I, _I, _I, _P, _I, _P]),
+    'pam_preprocess_crops_udp': (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P, C.c_float, _I, _I, _I, _P, _I, _P]),
     'pam_box_cs': (_I, [_P, _I, _P, _I, _I, C.c_float, _P]),
     'pam_box_cs_host': (_I, [_I, _P, _I, _I, C.c_float, _P]),
     'pam_decode_heatmaps': (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P]),
@@ -175,6 +176,8 @@ _SIGS = {
     'pam_head_decode_flip': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
     'pam_head_decode_dark_scratch_bytes': (C.c_longlong, [_I, _I, _I]),
     'pam_head_decode_dark': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
+    'pam_head_decode_udp_scratch_bytes': (C.c_longlong, [_I, _I, _I]),
+    'pam_head_decode_udp': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
     'pam_head_heatmaps': (_I, [_P, _I, _P, _I, _P, _P, _I, _P]),
     'pam_resize_frames': (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),
     'pam_upsample_concat_nhwc_bf16': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I]),
@@ -722,16 +725,17 @@ def crop_table(stream, boxes, count, frame_w, frame_h, max_dets, view_of, slot_o
         raise PamError('pam_crop_table failed (%d)' % rc)
 
 
-BOX_TRANSFORMS = ('stretch', 'affine')     # HRNetPose(box_transform=): the raw box stretched to the input, or the checkpoints' own transform
+# HRNetPose(box_transform=): the raw box stretched to the input, the checkpoints' own transform, or its UDP form (align-corners grids)
+BOX_TRANSFORMS = ('stretch', 'affine', 'udp')
 BOX_SCALE = 1.25                           # _box2cs's enlargement
 
 
 def check_box_transform(box_transform, box_scale=BOX_SCALE):
-    """(box_transform, box_scale) as HRNetPose takes them -> (name, float scale); anything but 'stretch' / 'affine', or a scale that is
+    """(box_transform, box_scale) as HRNetPose takes them -> (name, float scale); anything but 'stretch' / 'affine' / 'udp', or a scale that is
     not > 0, is a ValueError.  None stands for the default of either (a YAML without the optional keys)."""
     name = 'stretch' if box_transform is None else box_transform
     if name not in BOX_TRANSFORMS:
-        raise ValueError("box_transform must be 'stretch' or 'affine' (got %r)" % (box_transform,))
+        raise ValueError("box_transform must be 'stretch', 'affine' or 'udp' (got %r)" % (box_transform,))
     scale = BOX_SCALE if box_scale is None else float(box_scale)
     if not scale > 0.0:
         raise ValueError('box_scale must be > 0 (got %r)' % (box_scale,))

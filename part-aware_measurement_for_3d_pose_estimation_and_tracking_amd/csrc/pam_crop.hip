@@ -136,6 +136,7 @@ __device__ __forceinline__ void crop_stretch(int n_src, const uint8_t* const* __
 
 // ---- affine: the pose checkpoints' own crop geometry (pam_box_cs.hpp), sampled with ONE scale and a zero border ----------------------------
 // The two kernels' text is pam_crop_affine_kernel.inc, included once per form (see there why it is no template).
+#define CROP_UDP 0
 #define CROP_KERNEL k_preprocess_crops_affine
 #define CROP_FLIP 0
 #include "pam_crop_affine_kernel.inc"
@@ -146,6 +147,20 @@ __device__ __forceinline__ void crop_stretch(int n_src, const uint8_t* const* __
 #include "pam_crop_affine_kernel.inc"
 #undef CROP_KERNEL
 #undef CROP_FLIP
+#undef CROP_UDP
+// udp: the same text on the align-corners grid, pitch We / (ow - 1) (CROP_UDP in the .inc)
+#define CROP_UDP 1
+#define CROP_KERNEL k_preprocess_crops_udp
+#define CROP_FLIP 0
+#include "pam_crop_affine_kernel.inc"
+#undef CROP_KERNEL
+#undef CROP_FLIP
+#define CROP_KERNEL k_preprocess_crops_udp_flip
+#define CROP_FLIP 1
+#include "pam_crop_affine_kernel.inc"
+#undef CROP_KERNEL
+#undef CROP_FLIP
+#undef CROP_UDP
 
 // the stretch kernels' symbols: plain functions, so that a device-code comparison pairs them with any earlier build's
 __global__ __launch_bounds__(256) void k_preprocess_crops(int n_src, const uint8_t* const* __restrict__ frames, int H, int W, const int* __restrict__ view_of,
@@ -202,6 +217,19 @@ extern "C" int pam_preprocess_crops_affine(void* stream, int n, int n_total, int
         return PAM_E_ARG;
     if (n == 0) return PAM_OK;
     hipLaunchKernelGGL(flip ? k_preprocess_crops_affine_flip : k_preprocess_crops_affine, crop_grid(out_h, out_w, n_total), dim3(256), 0,
+                       (hipStream_t)stream, n, (const uint8_t* const*)dev_frames, frame_h, frame_w, dev_view_of, dev_boxes, box_scale, out_h,
+                       out_w, out_c, (uint16_t*)dev_out_bf16, antialias ? 1 : 0, dev_eff_xywh);
+    return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;
+}
+
+extern "C" int pam_preprocess_crops_udp(void* stream, int n, int n_total, int flip, const void* const* dev_frames, int frame_h, int frame_w,
+                                        const int32_t* dev_view_of, const float* dev_boxes, float box_scale, int out_h, int out_w,
+                                        int out_c, void* dev_out_bf16, int antialias, float* dev_eff_xywh) {
+    if (!crop_args_ok(n, n_total, flip ? 2 : 1, dev_frames, dev_view_of, dev_boxes, dev_out_bf16, out_h, out_w, out_c) || !dev_eff_xywh ||
+        !(box_scale > 0.0f) || out_w < 2 || out_h < 2)                 // the pitch divides by out_w - 1, out_h - 1
+        return PAM_E_ARG;
+    if (n == 0) return PAM_OK;
+    hipLaunchKernelGGL(flip ? k_preprocess_crops_udp_flip : k_preprocess_crops_udp, crop_grid(out_h, out_w, n_total), dim3(256), 0,
                        (hipStream_t)stream, n, (const uint8_t* const*)dev_frames, frame_h, frame_w, dev_view_of, dev_boxes, box_scale, out_h,
                        out_w, out_c, (uint16_t*)dev_out_bf16, antialias ? 1 : 0, dev_eff_xywh);
     return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP;

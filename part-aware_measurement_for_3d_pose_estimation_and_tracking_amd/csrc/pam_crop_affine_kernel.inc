@@ -8,6 +8,9 @@
 // Sampling is warpAffine's convention: integer coordinates are pixel centres, output pixel (u, v) reads the frame at
 // sx = xe + u * (We / ow), sy = ye + v * (He / oh) (float32, no half-pixel terms), bilinear over the four neighbours, and a tap outside
 // the frame contributes 0 (BORDER_CONSTANT), it is not the replicated edge.  A box with We == 0 (pam_box_cs.hpp) is all zero.
+// CROP_UDP 1 (Unbiased Data Processing, Huang et al., CVPR 2020): the same box on an align-corners grid, pitch We / (ow - 1), He / (oh - 1):
+// pixel 0 reads the box's left edge and pixel ow - 1 its right edge (the entry point refuses ow < 2 and oh < 2).  Nothing else differs; the
+// antialias branch takes the pitch as its scale.  CROP_UDP 0 leaves the text of the affine kernels as it was.
 __global__ __launch_bounds__(256) void CROP_KERNEL(int n_src, const uint8_t* const* __restrict__ frames, int H, int W,
                                                    const int* __restrict__ view_of, const float* __restrict__ boxes, float box_scale,
                                                    int oh, int ow, int oc, uint16_t* __restrict__ out, int antialias,
@@ -26,7 +29,11 @@ __global__ __launch_bounds__(256) void CROP_KERNEL(int n_src, const uint8_t* con
     const int oy = px / ow, ox = px % ow;
     const uint8_t* __restrict__ img = frames[view_of[src]];
     const float mean[3] = {0.485f, 0.456f, 0.406f}, istd[3] = {1.0f / 0.229f, 1.0f / 0.224f, 1.0f / 0.225f};
+#if CROP_UDP
+    const float scx = e.w / (float)(ow - 1), scy = e.h / (float)(oh - 1);
+#else
     const float scx = e.w / (float)ow, scy = e.h / (float)oh;
+#endif
     const float sx = e.x + (float)ox * scx, sy = e.y + (float)oy * scy;
     const bool live = e.w > 0.0f;
     float val[3] = {0.f, 0.f, 0.f};                // RGB, 0 .. 255, before the normalisation

@@ -537,6 +537,128 @@ __global__ __launch_bounds__(DARK_T) void k_dark_finish(int tiles, const Best* _
     write_keypoint_at(j, (double)py + oy, (double)px + ox, b.v, hm_h, hm_w, boxes + crop * 4, row, kp_row);
 }
 
+// ---- UDP decode (Huang et al., "The Devil is in the Details: Delving into Unbiased Data Processing for Human Pose Estimation", CVPR 2020):
+// the UDP form of DARK and the align-corners cell mapping -- contract in include/pam.h ---------------------------------------------------
+// The mapping: a cell is a point of the grid whose first and last points are the effective box's edges, pitch We / (hm_w - 1).
+__device__ __forceinline__ void write_keypoint_udp(int j, double py, double pxx, float score, int hm_h, int hm_w, const float* box,
+                                                   double* det_row, float* kp_row) {
+    // UDP's transform_preds: pt * (box extent / (size - 1)) + box origin, stored float32
+    const float y = (float)((double)box[1] + py * ((double)box[3] / (double)(hm_h - 1)));
+    const float x = (float)((double)box[0] + pxx * ((double)box[2] / (double)(hm_w - 1)));
+    det_row[j * 3 + 0] = (double)y; det_row[j * 3 + 1] = (double)x; det_row[j * 3 + 2] = (double)score;
+    if (kp_row) { kp_row[j * 3 + 0] = x; kp_row[j * 3 + 1] = y; kp_row[j * 3 + 2] = score; }
+}
+// blur_kernel == 0: k_argmax_finish with the UDP mapping, one lane per joint
+__global__ __launch_bounds__(64) void k_argmax_finish_udp(int tiles, const Best* __restrict__ cand, int hm_h, int hm_w,
+                                                          const int* __restrict__ view_of, const int* __restrict__ slot_of,
+                                                          const float* __restrict__ boxes, int max_dets, double* __restrict__ det,
+                                                          float* __restrict__ kp) {
+    const int crop = blockIdx.x, j = threadIdx.x;
+    if (j >= J) return;
+    Best b; b.v = -__builtin_huge_valf(); b.i = 0x7fffffff;
+    for (int t0 = 0; t0 < tiles; t0 += 8) {
+        Best c[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int t = min(t0 + q, tiles - 1);
+            c[q] = cand[((size_t)crop * tiles + t) * J + j];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if (t0 + q < tiles && c[q].v > b.v) b = c[q];
+    }
+    const int cell = best_cell(b);
+    write_keypoint_udp(j, (double)(cell / hm_w), (double)(cell % hm_w), b.v, hm_h, hm_w, boxes + crop * 4,
+                       det_row_of(det, view_of, slot_of, max_dets, crop), kp_row_of(kp, crop));
+}
+// The plan of k_dark_finish with UDP's step (mmpose post_dark_udp).  The blur reflects at the map's border (BORDER_REFLECT_101) and the log map
+// is read edge-replicated, so every winner takes the step, border and corner winners too: no workgroup leaves before the last barrier.
+// The seven samples sit at the clamped cells (py + dy, px + dx); their taps lie inside the (2R + 3)^2 window round the winner (19 x 19 at
+// k = 17), whose cell (wy, wx) holds M at the REFLECTED cell of (py - R - 1 + wy, px - R - 1 + wx): an in-map cell, never a zero.
+//   1. every thread folds the tile candidates (the same loads)
+//   2. window -> LDS as float32: one chain per thread and step (MERGE: as k_dark_finish)
+//   3. horizontal pass, float64, ascending taps: the 3 clamped columns px - 1, px, px + 1 of all 2R + 3 rows
+//   4. vertical pass over those: the 7 cells
+//   5. thread 0: clamp into [0.001, 50], 7 logarithms, the 2 x 2 solve with e = 2^-23 on the diagonal, write_keypoint_udp
+__device__ __forceinline__ int reflect101(int i, int n) {            // n >= 2; holds however far outside i lies
+    const int p = 2 * (n - 1);
+    int m = i % p;
+    if (m < 0) m += p;
+    return m < n ? m : p - m;
+}
+#define UDP_W 19              // 2 R + 3 at the largest blur, k = 17
+template <bool MERGE>
+__global__ __launch_bounds__(DARK_T) void k_udp_finish(int tiles, const Best* __restrict__ cand, int hm_h, int hm_w,
+                                                       const uint16_t* __restrict__ feat, int C, const float* __restrict__ w,
+                                                       const float* __restrict__ bias, int flip_row0, int shift, int R, DarkTaps taps,
+                                                       const int* __restrict__ view_of, const int* __restrict__ slot_of,
+                                                       const float* __restrict__ boxes, int max_dets, double* __restrict__ det,
+                                                       float* __restrict__ kp) {
+    __shared__ float win[MERGE ? 2 : 1][UDP_W * UDP_W];
+    __shared__ double bh[UDP_W * 3];
+    __shared__ double bv[7];
+    const int crop = blockIdx.x / J, j = blockIdx.x - crop * J, tid = threadIdx.x;
+    Best b; b.v = -__builtin_huge_valf(); b.i = 0x7fffffff;
+    for (int t0 = 0; t0 < tiles; t0 += 8) {
+        Best c[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int t = min(t0 + q, tiles - 1);
+            c[q] = cand[((size_t)crop * tiles + t) * J + j];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if (t0 + q < tiles && c[q].v > b.v) b = c[q];
+    }
+    if (b.i == 0x7fffffff) b.i = 0;        // no value above -inf: cell 0 (it takes the step like any other cell)
+    const int py = b.i / hm_w, px = b.i - py * hm_w, HW = hm_h * hm_w;
+    const int W = 2 * R + 3, cells = W * W, y0 = py - R - 1, x0 = px - R - 1, k = 2 * R + 1;
+    for (int i = tid; i < (MERGE ? 2 : 1) * cells; i += DARK_T) {
+        const int part = i >= cells, c = i - part * cells;
+        const int wy = c / W, wx = c - wy * W, y = reflect101(y0 + wy, hm_h), x = reflect101(x0 + wx, hm_w);
+        win[part][c] = part ? head_chain(feat + ((size_t)(flip_row0 + crop) * HW + y * hm_w + flip_column(x, hm_w, shift)) * C, C, w, bias, flip_pair(j))
+                            : head_chain(feat + ((size_t)crop * HW + y * hm_w + x) * C, C, w, bias, j);
+    }
+    __syncthreads();
+    if constexpr (MERGE) {
+        for (int c = tid; c < cells; c += DARK_T) win[0][c] = 0.5f * (win[0][c] + win[1][c]);
+        __syncthreads();
+    }
+    for (int i = tid; i < W * 3; i += DARK_T) {                        // B_h[row][clamp(px - 1 + d)]: window columns cx - px + 1 .. + 2R
+        const int r = i / 3, d = i - r * 3;
+        const int o = min(max(px - 1 + d, 0), hm_w - 1) - px + 1;
+        double s = 0.0;
+        for (int t = 0; t < k; ++t) s += taps.g[t] * (double)win[0][r * W + o + t];
+        bh[i] = s;
+    }
+    __syncthreads();
+    if (tid < 7) {                                                     // (dy, dx) of cell tid: 0 | x+1 x-1 | y+1 y-1 | ++ --
+        const int dy = tid == 3 || tid == 5 ? 1 : (tid == 4 || tid == 6 ? -1 : 0);
+        const int dx = tid == 1 || tid == 5 ? 1 : (tid == 2 || tid == 6 ? -1 : 0);
+        const int o = min(max(py + dy, 0), hm_h - 1) - py + 1;         // window rows cy - py + 1 .. + 2R
+        double s = 0.0;
+        for (int t = 0; t < k; ++t) s += taps.g[t] * bh[(o + t) * 3 + 1 + dx];
+        bv[tid] = s;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    double L[7];
+#pragma unroll
+    for (int q = 0; q < 7; ++q) L[q] = log(bv[q] > 0.001 ? (bv[q] < 50.0 ? bv[q] : 50.0) : 0.001);      // (a NaN clamps to 0.001)
+    const double gx = 0.5 * (L[1] - L[2]), gy = 0.5 * (L[3] - L[4]);
+    const double dxx = L[1] - 2.0 * L[0] + L[2], dyy = L[3] - 2.0 * L[0] + L[4];
+    const double dxy = 0.5 * (L[5] - L[1] - L[3] + 2.0 * L[0] - L[2] - L[4] + L[6]);
+    const double e = 1.1920928955078125e-07;                           // np.finfo(np.float32).eps on the diagonal
+    const double hxx = dxx + e, hyy = dyy + e, dt = hxx * hyy - dxy * dxy;
+    double ox = 0.0, oy = 0.0;
+    if (dt != 0.0 && isfinite(dt)) {                                   // -H'^-1 g; nothing clamps the step
+        ox = -(hyy * gx - dxy * gy) / dt;
+        oy = -(hxx * gy - dxy * gx) / dt;
+    }
+    write_keypoint_udp(j, (double)py + oy, (double)px + ox, b.v, hm_h, hm_w, boxes + crop * 4,
+                       det_row_of(det, view_of, slot_of, max_dets, crop), kp_row_of(kp, crop));
+}
+
 // ---- entry points ----------------------------------------------------------------------------------------------------------------------
 static bool head_ok(int n, const void* feat, const float* w, int C, int J_) { return n >= 0 && feat && w && C > 0 && C % 8 == 0 && J_ == PAM_J; }
 // what every pam_head_decode* entry requires (bias, the heat-map and the kp pointer may be null)
@@ -554,6 +676,18 @@ static int head_tiles(int hm_h, int hm_w) { return (hm_h * hm_w + HEAD_T - 1) / 
 // measured change of its own.
 static size_t head_stage_lds() { return (size_t)HEAD_T * (J + 1) * sizeof(float); }       // the [HEAD_T][JN + 1] staging of the tile reduction
 static size_t head_argmax_lds(int C) { return (size_t)J * C * sizeof(float) + (size_t)(HEAD_T / 64) * J * sizeof(Best) + head_stage_lds(); }
+static DarkTaps gaussian_taps(int blur_kernel) {                       // OpenCV's getGaussianKernel(k, 0): sigma from k, taps normalised to 1
+    DarkTaps taps;
+    const int R = (blur_kernel - 1) / 2;
+    const double sigma = 0.3 * ((blur_kernel - 1) * 0.5 - 1.0) + 0.8;
+    double sum = 0.0;
+    for (int i = 0; i < 17; ++i) {
+        taps.g[i] = i < blur_kernel ? exp(-(double)((i - R) * (i - R)) / (2.0 * sigma * sigma)) : 0.0;
+        sum += taps.g[i];
+    }
+    for (int i = 0; i < 17; ++i) taps.g[i] /= sum;
+    return taps;
+}
 static int launched() { return hipGetLastError() == hipSuccess ? PAM_OK : PAM_E_HIP; }
 
 // The first pass of every decode: the tile candidates of n crops into `scratch` (Best[n][tiles][J]; beta > 0: also the soft partials,
@@ -645,18 +779,34 @@ extern "C" int pam_head_decode_dark(void* stream, int n, int flip_row0, int hm_h
         return PAM_E_ARG;
     if (n == 0) return PAM_OK;
     const int merge = flags & PAM_FLIP_MERGE, shift = (flags & PAM_FLIP_SHIFT) ? 1 : 0, R = (blur_kernel - 1) / 2;
-    DarkTaps taps;                                                     // OpenCV's getGaussianKernel(k, 0): sigma from k, taps normalised to 1
-    const double sigma = 0.3 * ((blur_kernel - 1) * 0.5 - 1.0) + 0.8;
-    double sum = 0.0;
-    for (int i = 0; i < 17; ++i) {
-        taps.g[i] = i < blur_kernel ? exp(-(double)((i - R) * (i - R)) / (2.0 * sigma * sigma)) : 0.0;
-        sum += taps.g[i];
-    }
-    for (int i = 0; i < 17; ++i) taps.g[i] /= sum;
+    const DarkTaps taps = gaussian_taps(blur_kernel);
     const int tiles = head_first_pass(stream, n, hm_h, hm_w, feat_bf16, C, w, bias, dev_heatmaps_or_null, dev_scratch, 0.0f, merge, flip_row0, shift);
     hipLaunchKernelGGL(merge ? k_dark_finish<true> : k_dark_finish<false>, dim3(n * J), dim3(DARK_T), 0, (hipStream_t)stream, tiles, (const Best*)dev_scratch,
                        hm_h, hm_w, (const uint16_t*)feat_bf16, C, w, bias, merge ? flip_row0 : 0, shift, R, taps, dev_view_of, dev_slot_of, dev_boxes, max_dets,
                        dev_det, dev_kp_xyc);
+    return launched();
+}
+extern "C" long long pam_head_decode_udp_scratch_bytes(int n, int hm_h, int hm_w) {
+    return hm_h < 2 || hm_w < 2 ? -1 : pam_head_decode_scratch_bytes(n, hm_h, hm_w);
+}
+extern "C" int pam_head_decode_udp(void* stream, int n, int flip_row0, int hm_h, int hm_w, const void* feat_bf16, int C, const float* w,
+                                   const float* bias, int J_, int flags, int blur_kernel, float* dev_heatmaps_or_null,
+                                   const int32_t* dev_view_of, const int32_t* dev_slot_of, const float* dev_boxes, int max_dets,
+                                   double* dev_det, float* dev_kp_xyc, void* dev_scratch) {
+    if (!head_decode_ok(n, hm_h, hm_w, feat_bf16, C, w, J_, dev_view_of, dev_slot_of, dev_boxes, dev_det, dev_scratch) ||
+        !flip_flags_ok(flags, PAM_FLIP_MERGE | PAM_FLIP_SHIFT, n, flip_row0) || hm_h < 2 || hm_w < 2 ||
+        (blur_kernel != 0 && (blur_kernel < 9 || blur_kernel > 17 || blur_kernel % 2 == 0)))
+        return PAM_E_ARG;
+    if (n == 0) return PAM_OK;
+    const int merge = flags & PAM_FLIP_MERGE, shift = (flags & PAM_FLIP_SHIFT) ? 1 : 0;
+    const int tiles = head_first_pass(stream, n, hm_h, hm_w, feat_bf16, C, w, bias, dev_heatmaps_or_null, dev_scratch, 0.0f, merge, flip_row0, shift);
+    if (blur_kernel == 0)                                              // no sub-pixel step: the plain arg-max of M through the UDP mapping
+        hipLaunchKernelGGL(k_argmax_finish_udp, dim3(n), dim3(64), 0, (hipStream_t)stream, tiles, (const Best*)dev_scratch, hm_h, hm_w, dev_view_of,
+                           dev_slot_of, dev_boxes, max_dets, dev_det, dev_kp_xyc);
+    else
+        hipLaunchKernelGGL(merge ? k_udp_finish<true> : k_udp_finish<false>, dim3(n * J), dim3(DARK_T), 0, (hipStream_t)stream, tiles,
+                           (const Best*)dev_scratch, hm_h, hm_w, (const uint16_t*)feat_bf16, C, w, bias, merge ? flip_row0 : 0, shift,
+                           (blur_kernel - 1) / 2, gaussian_taps(blur_kernel), dev_view_of, dev_slot_of, dev_boxes, max_dets, dev_det, dev_kp_xyc);
     return launched();
 }
 extern "C" int pam_decode_heatmaps(void* stream, int n, const float* dev_heatmaps, int nchw, int hm_h, int hm_w,

@@ -14,7 +14,7 @@ class DumpResults(list):
     in place.  Until then nobody can have edited the dicts, so the device copy is trivially the truth."""
     device_det = None        # (views, max_dets, 17, 3) float64 rows (y, x, score) at (view, slot)
     device_n_det = None      # (views,) int32
-    device_eff = None        # HRNetPose(box_transform='affine'): (n, 4) float32 effective boxes the call's crops and decode went through
+    device_eff = None        # HRNetPose(box_transform='affine' / 'udp'): (n, 4) float32 effective boxes the call's crops and decode went through
     _poses_host = None       # per view (n, 17, 3) float64 (y, x, score): what ivclabpose._unpack would rebuild from the dicts
     _pending = None          # (pinned host keypoints, event, views, boxes, per-view counts) until the first access
     _nms = None              # HRNetPose(pose_nms=True): (pinned [n_det_out | keep_from], pinned pose_score, views, slots) of the call's filter

@@ -200,21 +200,23 @@ class HRNetPose(ForwardReplay):
         2N rows: N plain crops, their N mirrors, then repeats of the last mirror.
         box_transform='affine': the crops come from the boxes' effective boxes (pam_preprocess_crops_affine; the transform:
         include/pam.h), which the launch leaves in eff (N,4) float32 -- the table ``head_decode`` and the OKS-NMS take in place of
-        ``boxes``; eff=None: a table of the call's own that nobody reads.  'stretch' never touches eff."""
+        ``boxes``; eff=None: a table of the call's own that nobody reads.  'udp': the same table through pam_preprocess_crops_udp (the
+        align-corners grid).  'stretch' never touches eff."""
         H, W = self.resolution
         st = torch.cuda.current_stream(self.device).cuda_stream
-        if self.box_transform == 'affine':
+        if self.uses_effective_box:
             n = int(view_of.numel())
+            name = 'pam_preprocess_crops_' + self.box_transform    # _affine | _udp: one argument list
             if eff is None:
                 eff = torch.empty((max(n, 1), 4), dtype=torch.float32, device=self.device)
             assert eff.is_contiguous() and eff.dtype == torch.float32 and eff.numel() >= 4 * n
-            rc = self.lib.pam_preprocess_crops_affine(C.c_void_p(st), n, int(out.shape[0]), 1 if self.flip_test else 0,
-                                                      C.c_void_p(frame_ptrs.data_ptr()), int(frame_h), int(frame_w),
-                                                      C.c_void_p(view_of.data_ptr()), C.c_void_p(boxes.data_ptr()), float(self.box_scale),
-                                                      H, W, int(out.shape[1]), C.c_void_p(out.data_ptr()), 1 if self.antialias else 0,
-                                                      C.c_void_p(eff.data_ptr()))
+            rc = getattr(self.lib, name)(C.c_void_p(st), n, int(out.shape[0]), 1 if self.flip_test else 0,
+                                         C.c_void_p(frame_ptrs.data_ptr()), int(frame_h), int(frame_w),
+                                         C.c_void_p(view_of.data_ptr()), C.c_void_p(boxes.data_ptr()), float(self.box_scale),
+                                         H, W, int(out.shape[1]), C.c_void_p(out.data_ptr()), 1 if self.antialias else 0,
+                                         C.c_void_p(eff.data_ptr()))
             if rc != 0:
-                raise _lib.PamError('pam_preprocess_crops_affine failed: %d' % rc)
+                raise _lib.PamError('%s failed: %d' % (name, rc))
             return
         fn = self.lib.pam_preprocess_crops_flip if self.flip_test else self.lib.pam_preprocess_crops_ex
         rc = fn(C.c_void_p(st), int(view_of.numel()), int(out.shape[0]), C.c_void_p(frame_ptrs.data_ptr()),
@@ -263,6 +265,13 @@ class HRNetPose(ForwardReplay):
     #                  cells back through the same effective box and pose_nms takes its areas from it (include/pam.h).  The dump's 'bbox'
     #                  stays the caller's box.  Constructor arguments (validated there: _lib.check_box_transform); the forwards keep their
     #                  size.  'stretch': every entry point makes exactly the calls it made without the option.
+    #                  'udp': Unbiased Data Processing (Huang et al., CVPR 2020), the protocol of every public ViTPose checkpoint and of the
+    #                  HRNet / Simple Baselines "+UDP" ones: the same effective box, but crop and heat-map are align-corners grids (pitch
+    #                  We / (W - 1) and We / (hm_w - 1): pam_preprocess_crops_udp), and the decode is ALWAYS pam_head_decode_udp: with dark
+    #                  the UDP form of DARK (post_dark_udp; blur_kernel as for dark), without it the plain arg-max through UDP's mapping.
+    #                  post_process or soft_beta with 'udp' is refused (ValueError): the quarter-cell nudge compensates exactly the bias UDP
+    #                  removes, and there is no UDP soft-arg-max.  shift_heatmap is honoured as given; the UDP configs run the flip test
+    #                  with shift_heatmap=False.
     #   box_scale      _box2cs's enlargement, 1.25.  Boxes that already carry a margin (pam_track_boxes' TRACK_BOX_GROW 1.25) are
     #                  enlarged again: the two factors multiply.
     box_transform, box_scale = 'stretch', _lib.BOX_SCALE
@@ -271,6 +280,11 @@ class HRNetPose(ForwardReplay):
     #                  (pam_undistort_keypoints).  The host keypoints and the dump's dicts stay in raw-image pixels.  None: predict()
     #                  issues exactly the launches it issued without it.
     lens, lens_info = None, None
+
+    @property
+    def uses_effective_box(self):
+        """True where crops, decode and OKS-NMS go through the effective box of include/pam.h ('affine', 'udp'), not the raw box."""
+        return self.box_transform != 'stretch'
 
     def set_lens(self, table):
         """table: (cameras, 10) float64 host rows (_lib.lens_table), view v of a predict() call is camera v; None or all-zero
@@ -297,6 +311,9 @@ class HRNetPose(ForwardReplay):
             if now['soft_beta'] is not None and (now['flip_test'] or now['post_process']):
                 raise ValueError('HRNetPose: soft_beta cannot be combined with flip_test or post_process (got soft_beta=%r, flip_test=%r, '
                                  'post_process=%r)' % (now['soft_beta'], now['flip_test'], now['post_process']))
+            if self.box_transform == 'udp' and (now['post_process'] or now['soft_beta'] is not None):
+                raise ValueError("HRNetPose: box_transform='udp' cannot be combined with post_process or soft_beta (got post_process=%r, "
+                                 'soft_beta=%r)' % (now['post_process'], now['soft_beta']))
             if name == 'flip_test' and value != self._flip_test and getattr(self, '_graphs', None):
                 raise RuntimeError('HRNetPose: flip_test changes the size of every forward; set it before the first capture')
             setattr(self, '_' + name, value)
@@ -329,7 +346,8 @@ class HRNetPose(ForwardReplay):
         channels-last) is given.  n: decode only the first n crops of f.  Under the flip test f is the feature batch of a forward that
         ``preprocess`` filled (n plain crops, then their n mirrors: n defaults to half of f) and the decode runs on the merged maps; with
         ``post_process`` the arg-max carries the quarter-cell offset; with ``dark`` the DARK offset (pam_head_decode_dark, on the merged
-        map under the flip test).  With every option off the launches are pam_head_decode's."""
+        map under the flip test).  With every option off the launches are pam_head_decode's.  box_transform='udp': always
+        pam_head_decode_udp (``boxes`` is the effective table), blur size dark_blur_kernel(h) with ``dark`` and 0 without."""
         nf, c, h, w = f.shape
         flags = self.decode_flags()
         n = (nf // 2 if flags & 1 else nf) if n is None else n
@@ -345,7 +363,10 @@ class HRNetPose(ForwardReplay):
                 C.c_void_p(view_of.data_ptr()), C.c_void_p(slot_of.data_ptr()), C.c_void_p(boxes.data_ptr()),
                 det.shape[1], C.c_void_p(det.data_ptr()), C.c_void_p(kp.data_ptr()) if kp is not None else None,
                 C.c_void_p(self._hd_scratch.data_ptr()))
-        if soft:
+        udp = self.box_transform == 'udp'
+        if udp:                                           # (same scratch size as well: pam_head_decode_udp_scratch_bytes; never soft or quarter)
+            rc = self.lib.pam_head_decode_udp(*(head[:2] + (n,) + head[2:] + (flags & 3, self.dark_blur_kernel(h) if self.dark else 0) + tail))
+        elif soft:
             rc = self.lib.pam_head_decode_soft(*(head + (C.c_float(float(self.soft_beta)),) + tail))
         elif self.dark:                                   # (same scratch size as well: pam_head_decode_dark_scratch_bytes)
             rc = self.lib.pam_head_decode_dark(*(head[:2] + (n,) + head[2:] + (flags & 3, self.dark_blur_kernel(h)) + tail))
@@ -354,7 +375,7 @@ class HRNetPose(ForwardReplay):
         else:
             rc = self.lib.pam_head_decode(*(head + tail))
         if rc != 0:
-            raise _lib.PamError('pam_head_decode%s failed: %d' % ('_soft' if soft else ('_dark' if self.dark else ('_flip' if flags else '')), rc))
+            raise _lib.PamError('pam_head_decode%s failed: %d' % ('_udp' if udp else '_soft' if soft else ('_dark' if self.dark else ('_flip' if flags else '')), rc))
 
     # -- the reference-shaped entry point ------------------------------------------------------------------------------
     def _call_tables(self, person_bbox_list, frame_ptr_of):
@@ -440,9 +461,9 @@ class HRNetPose(ForwardReplay):
         ptrs = m[o_ptr:o_ptr + 2 * V].view(torch.int64)
         det = torch.empty((V, S, 17, 3), dtype=torch.float64, device=self.device)
         kp = torch.empty((n, 17, 3), dtype=torch.float32, device=self.device)
-        # box_transform='affine': the call's effective boxes, written by the crop launches (every row by pam_box_cs first when the crops
+        # box_transform='affine' / 'udp': the call's effective boxes, written by the crop launches (every row by pam_box_cs first when the crops
         # are sharded: a rank crops its share and filters all) and read by the decode and the filter in place of bx
-        affine = self.box_transform == 'affine'
+        affine = self.uses_effective_box
         eff = torch.empty((n, 4), dtype=torch.float32, device=self.device) if affine else None
         dbx = eff if affine else bx
         lo, hi = 0, n

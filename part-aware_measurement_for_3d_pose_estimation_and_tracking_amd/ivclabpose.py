@@ -57,7 +57,7 @@ def one_euro_from_matcher(m):
 
 def box_transform_options(p):
     """The optional keys BOX_TRANSFORM / BOX_SCALE of a POSE_MODELS.HRPOSE block (not in the reference's YAMLs) -> (box_transform,
-    box_scale) as HRNetPose takes them; absent keys give ('stretch', 1.25), a BOX_TRANSFORM other than 'stretch' / 'affine' or a
+    box_scale) as HRNetPose takes them; absent keys give ('stretch', 1.25), a BOX_TRANSFORM other than 'stretch' / 'affine' / 'udp' or a
     BOX_SCALE that is not > 0 is a ValueError (_lib.check_box_transform)."""
     from . import _lib
     return _lib.check_box_transform(_opt(p, 'BOX_TRANSFORM'), _opt(p, 'BOX_SCALE'))
@@ -196,9 +196,11 @@ class ivclabpose(object):
             # ivclabpose.py:107-111: gpu_args = every visible GPU.  One process drives ONE of them (`device`); several GPUs = several
             # ranks of a torch.distributed job, and HRNetPose.predict shards each call's crops over them (see HRNetPose.__init__).
             gpu_args = _Args(gpus=list(range(torch.cuda.device_count())), device=torch.device('cuda:%d' % device))
-            # optional keys BOX_TRANSFORM ('stretch' | 'affine') / BOX_SCALE: the crop geometry; 'affine' = the published checkpoints' own
+            # optional keys BOX_TRANSFORM ('stretch' | 'affine' | 'udp') / BOX_SCALE: the crop geometry; 'affine' = the published checkpoints' own
             # (_box2cs + get_affine_transform: aspect fix about the centre, x BOX_SCALE 1.25, zero border; decode and OKS-NMS through the
-            # same effective box).  Absent: the raw box stretched to the input, as before.  Another value is refused (ValueError).
+            # same effective box); 'udp' = the UDP checkpoints' (ViTPose, HRNet "+UDP": the same box on align-corners grids, decode always
+            # pam_head_decode_udp; with POST_PROCESS or SOFT_ARGMAX_BETA a ValueError).  Absent: the raw box stretched to the input, as
+            # before.  Another value is refused (ValueError).
             box_transform, box_scale = box_transform_options(self.pose_detector)
             self.pose_model = HRNetPose(_cfg(self.pose_detector, 'C'), _cfg(self.pose_detector, 'NUM_JOINTS'),
                                         _cfg(self.pose_detector, 'CHECKPOINT_FILE'),

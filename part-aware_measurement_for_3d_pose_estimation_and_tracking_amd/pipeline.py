@@ -85,7 +85,9 @@ class FramePipeline(object):
         the frame's effective boxes in a device table beside the other per-frame buffers (``eff_table``, sized for the bucket cap, one per
         replay slot) and decode and pose_nms read that table in place of the boxes.  pam_crop_table and pam_track_boxes are unchanged and
         still deliver raw clamped boxes: on a track-box frame TRACK_BOX_GROW 1.25 and BOX_SCALE 1.25 MULTIPLY (a box 1.56 x the
-        keypoints' extent); both defaults are left alone.  A shared `net` keeps its own setting.  'stretch': the launches of before."""
+        keypoints' extent); both defaults are left alone.  'udp': the same table and the same paths with the UDP protocol's align-corners
+        crop and decode (pam_preprocess_crops_udp, pam_head_decode_udp; HRNetPose refuses it with post_process).  A shared `net` keeps
+        its own setting.  'stretch': the launches of before."""
         box_transform, box_scale = _lib.check_box_transform(box_transform, box_scale)
         if overlay is not None and shard == 'crops':
             raise ValueError("overlay needs shard='views': a rank draws the frames of the views it owns")
@@ -179,11 +181,11 @@ class FramePipeline(object):
         if self.bucketed and self.net is not None:
             self.crop_cap = self.net.bucket(self.crop_cap)
         self._tables, self._tb, self.table_n_det = None, None, None
-        # box_transform='affine': the effective boxes of a frame, written by its crop launch and read by its decode and filter; one table
+        # box_transform='affine' / 'udp': the effective boxes of a frame, written by its crop launch and read by its decode and filter; one table
         # per replay slot (two frames in flight), rows for the largest frame this rank can see, rounded up to the bucket as crop_cap is
         # (built here when the network has the option on, else at the first frame of a shared net whose owner switches it on later)
         self.eff_table = None
-        if self.net is not None and self.net.box_transform == 'affine':
+        if self.net is not None and self.net.box_transform != 'stretch':
             self._eff_rows(0, 0)
         self._ct = stages.CropTableInfo()
         self._ev_slot_read, self._table_no, self._table_slot = [None, None], 0, 0
@@ -306,7 +308,7 @@ class FramePipeline(object):
         k = (self._frame_no & 1) if self.pose_streams is not None else 0
         n = int(views.numel())
         x = self.net.input_buffer(self.net.bucket(n) if self.bucketed else n, k)     # a bucket's spare rows repeat the last crop, undecoded
-        eff = self._eff_rows(k, n) if self.net.box_transform == 'affine' else None
+        eff = self._eff_rows(k, n) if self.net.box_transform != 'stretch' else None
         self.net.preprocess(frame_ptrs, self.frame_h, self.frame_w, views, boxes, x, eff=eff)
         if eff is not None:
             boxes = eff                                  # decode and filter go through the effective boxes (transform_preds)
@@ -328,7 +330,7 @@ class FramePipeline(object):
                             lens=(self.lens, self.lens_info, self._lens_views) if self.lens is not None else None, max_dets=self.max_dets)
 
     def _eff_rows(self, k, n):
-        """The first n rows of replay slot k's effective-box table (box_transform='affine'); the tables hold the largest frame this rank
+        """The first n rows of replay slot k's effective-box table (box_transform='affine' / 'udp'); the tables hold the largest frame this rank
         can see -- crop_cap or every view x max_dets, rounded up to the bucket as crop_cap is -- and one grows for a longer caller's table."""
         if self.eff_table is None:
             rows = max(self.crop_cap, self.C * self.max_dets)
